@@ -1,7 +1,11 @@
 """Benchmark of the rasterizer hot path: train iters/sec (fwd+bwd rasterize) @1980x1080, 1M Gaussians.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]      (N > 1: starts N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full]   (N > 1: starts N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, settles and warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the
+headline line.  --full adds everything else the line can carry: per-step distribution, per-kernel table and roofline, the
+other exchange mode, the extras, the CPU baselines and the parity figures.
 
 One "step" = one forward + one backward of the drop-in GaussianRasterizer over one synthetic view
 (inputs resident in HBM).  With N > 1 every rank renders its own view of the replicated scene and
@@ -424,9 +428,17 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3", choices=list(gsr_scene.CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the loss and training-iteration extras (profiling runs)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the whole-training-iteration extra (8f rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the dominant kernel's launch times inside the "
+                         "timed region, the per-step distribution (a second pass of the K steps), the per-kernel table and roofline, the "
+                         "other exchange mode (N > 1), the extras, the CPU baselines and the parity figures against the oracle.  Off: "
+                         "set-up, settling and warm-up steps, the K timed steps, --dump-outputs and the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float32; "
+                         "see dump_outputs())")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the loss and training-iteration extras (profiling runs)")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the whole-training-iteration extra (8f rows)")
     ap.add_argument("--sh-exchange", default="compact", choices=["compact", "allreduce"],
                     help="N > 1: 'compact' all-gathers 3 floats/Gaussian/view and rebuilds the summed SH gradient "
                          "locally (view_parallel.GradientExchange); 'allreduce' sums all 59 floats/Gaussian.  The timed "
@@ -468,7 +480,12 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearsal of the N > 1 plumbing WITHOUT the rasterizer (no GPU needed): ranks are spawned, the "
                          "process group is formed and every step runs only the gradient exchange on synthetic buffers")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the rasterizer; --dry-run has none")
+    return args
 
 
 def _free_port():
@@ -516,6 +533,34 @@ def step_stats(ms):
     return dict(min=round(ms[0], 4), median=round(med, 4), max=round(ms[-1], 4), n=n)
 
 
+DUMP_PIXELS = 3 << 20      # --dump-outputs: the image whole up to this many pixels (C3), else a seeded sample of as many (C5)
+DUMP_GAUSSIANS = 1 << 16   # --dump-outputs: per-Gaussian rows of a seeded sample of this many Gaussians (all when P is smaller)
+
+
+def dump_outputs(out_dir, color, radii, means2D, params):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 DIR/<name>.npy -- the image of the step's
+    (last) view, the radii, the screen-space gradient and the five parameter gradients.  The samples depend on the sizes
+    only (fixed seeds, positions in index order), so two builds run with the same arguments dump the same elements:
+    image.npy is (3, H, W), or (3, DUMP_PIXELS) pixels of the flattened image; the per-Gaussian arrays keep DUMP_GAUSSIANS
+    rows.  At most 55 MB in all (C5: 37.7 MB of image, 16.5 MB of per-Gaussian rows)."""
+    import numpy as np
+
+    def sample(n, cap, seed):
+        if n <= cap:
+            return None
+        return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:cap].sort().values
+
+    os.makedirs(out_dir, exist_ok=True)
+    pix = sample(color.shape[1] * color.shape[2], DUMP_PIXELS, 1)
+    image = color if pix is None else color.reshape(3, -1)[:, pix.to(color.device)]
+    rows = sample(radii.shape[0], DUMP_GAUSSIANS, 2)
+    arrays = dict(radii=radii, means2D_grad=means2D.grad, **{f"{k}_grad": p.grad for k, p in params.items()})
+    if rows is not None:
+        arrays = {k: a[rows.to(a.device)] for k, a in arrays.items()}
+    for name, a in dict(image=image, **arrays).items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().to(torch.float32).cpu().numpy())
+
+
 def valu_issue_fraction(stage, workload, kernel_ms=None):
     """Fraction of the chip's vector-ALU issue roof the kernel reaches, from the committed PMC summary (tools/profile_run.sh ->
     tools/pmc_summary.py): roof time = the kernel's wave64 VALU instructions (SQ_INSTS_VALU, exact: checked against kernels of
@@ -533,6 +578,13 @@ def valu_issue_fraction(stage, workload, kernel_ms=None):
                     source=os.path.basename(PMC_SUMMARY))
     except (OSError, KeyError, ValueError, ZeroDivisionError):
         return None
+
+
+def diagnostic_config(out, args):
+    if args.debug_mask:
+        out["config"]["debug_mask"] = args.debug_mask   # a diagnostic run of an alternate path, not the headline
+    if args.library:
+        out["config"]["library"] = os.path.basename(args.library)   # a diagnostic run of an A/B build, not the headline
 
 
 def main():
@@ -689,7 +741,7 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
             def f():
                 means2D = torch.zeros_like(params["means3D"], requires_grad=True)
                 color, radii = rast(means3D=params["means3D"], means2D=means2D, **{k: v for k, v in params.items() if k != "means3D"})
-                state["radii"] = radii
+                state["radii"], state["means2D"] = radii, means2D
                 return color
             return f
         render_fns = [render_fn(r) for r in rasterizers]
@@ -715,7 +767,7 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
                     color.backward(dp)   # k > 1: autograd accumulates the k local views into .grad
                 if bucket is not None:
                     bucket.all_reduce()  # ONE flat all-reduce of the 59 floats/Gaussian per step, after the k local views
-                state["color"], state["radii"] = color, radii
+                state["color"], state["radii"], state["means2D"] = color, radii, means2D
             return step
         steps = {m: make_step(m) for m in ("compact", "allreduce")}
 
@@ -772,33 +824,39 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
     for _ in range(args.warmup):
         step()
     phase["now"] = "timed steps"
-    # Timed region: HIP events only around the dominant kernel (every event record drains the queue for
-    # ~5 us; bracketing all stages costs ~80 us per step, 4 % of it) plus one event per step boundary.  The full
-    # per-kernel table comes from a second, untimed pass below.
-    elapsed, per_step = timed(step, args.steps, only=DOMINANT_STAGE)
+    # Timed region: the K steps between barriers and nothing else.  With --full the library also times the launches of the
+    # dominant kernel in it (they take their timestamps from their own dispatch packets: bracketing all stages with event
+    # records would cost ~80 us per step, 4 % of it); the per-step distribution and the full per-kernel table come from
+    # further, untimed passes below.
+    elapsed, per_step = timed(step, args.steps, only=DOMINANT_STAGE if args.full else None)
     dom_records = []
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         dom_records = _C.profile_end(capacity=4 * max(args.steps, 1))   # the dominant kernel's launches inside the timed region
-        _, per_step = timed(step, args.steps, per_step=True)            # the per-step distribution: the same K steps once more (see timed())
-    if os.environ.get("GSR_BENCH_DUMP_STEPS") == "1" and rank == 0:
-        print("per-step ms:", " ".join(f"{x:.3f}" for x in per_step), file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:
+        phase["now"] = "writing the outputs of the last timed step"
+        dump_outputs(args.dump_outputs, state["color"], state["radii"], state["means2D"], params)
     dom_times, ktimes, table_steps = [], [], 0
-    if not args.dry_run:
-        dom_times = [ms for name, ms in dom_records if name == DOMINANT_STAGE]
-        table_steps = max(3, min(args.steps, 10))
-        _C.profile_begin()
-        for _ in range(table_steps):
-            step()
-        torch.cuda.synchronize()
-        ktimes = _C.profile_end(capacity=64 * table_steps)
     alt = None
-    phase["now"] = "per-kernel table / alternative exchange mode"
-    if grouped and (args.dry_run or kviews == 1):
-        other = "allreduce" if mode == "compact" else "compact"
-        for _ in range(max(1, args.warmup)):
-            steps[other]()
-        e2, per2 = timed(steps[other], args.steps)
-        alt = dict(mode=other, value=round(world * args.steps / e2, 3), ms_per_step=round(e2 / args.steps * 1e3, 4), step_ms=step_stats(per2))
+    if args.full:
+        if not args.dry_run:
+            _, per_step = timed(step, args.steps, per_step=True)            # the per-step distribution: the same K steps once more (see timed())
+        if os.environ.get("GSR_BENCH_DUMP_STEPS") == "1" and rank == 0:
+            print("per-step ms:", " ".join(f"{x:.3f}" for x in per_step), file=sys.stderr, flush=True)
+        if not args.dry_run:
+            dom_times = [ms for name, ms in dom_records if name == DOMINANT_STAGE]
+            table_steps = max(3, min(args.steps, 10))
+            _C.profile_begin()
+            for _ in range(table_steps):
+                step()
+            torch.cuda.synchronize()
+            ktimes = _C.profile_end(capacity=64 * table_steps)
+        phase["now"] = "per-kernel table / alternative exchange mode"
+        if grouped and (args.dry_run or kviews == 1):
+            other = "allreduce" if mode == "compact" else "compact"
+            for _ in range(max(1, args.warmup)):
+                steps[other]()
+            e2, per2 = timed(steps[other], args.steps)
+            alt = dict(mode=other, value=round(world * args.steps / e2, 3), ms_per_step=round(e2 / args.steps * 1e3, 4), step_ms=step_stats(per2))
 
     gc.enable()
     if rank != 0:
@@ -807,11 +865,12 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
     out = dict(metric="train iters/sec (fwd+bwd rasterize) @1980x1080, 1M Gaussians", value=round(world * kviews * args.steps / elapsed, 3),
                unit="it/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=round(ms_per_step, 4),
                higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-               step_ms=dict(step_stats(per_step) or {}, note="a second pass of the same K steps with one event record per step boundary (each record is a "
-                                                              "barrier packet, 6-8 us in front of the next launch: the timed region runs without them)"),
                settle=dict(steps=settle_steps,
                            note="untimed steps of the same workload before the W warm-up steps (device reaches its steady state: the "
                                 "first ~20 steps of a fresh process run up to 7 % slower); --settle-steps 0 disables"))
+    if args.full:
+        out["step_ms"] = dict(step_stats(per_step) or {}, note="a second pass of the same K steps with one event record per step boundary (each record is a "
+                                                               "barrier packet, 6-8 us in front of the next launch: the timed region runs without them)")
     if alt is not None:
         out["alt_exchange"] = alt
     if parts_note:
@@ -832,6 +891,12 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
     if args.dry_run:
         out.update(data="dry-run: process-group plumbing and gradient exchange only, NO rasterizer (not a measurement)",
                    config=dict(workload=f"{args.config}: exchange buffers of {P} Gaussians", P=P, views_per_step=world * kviews, parallelism=parallelism))
+        print(json.dumps(out), flush=True)
+        return
+    workload = f"{args.config}: {P} Gaussians, SH deg {D}, {W}x{H}, mu={mu}, seed 0"
+    if not args.full:
+        out["config"] = dict(workload=workload, P=P, views_per_step=world * kviews, parallelism=parallelism)
+        diagnostic_config(out, args)
         print(json.dumps(out), flush=True)
         return
 
@@ -928,7 +993,7 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
                         step_algorithmic_bytes=step_bytes,
                         step_GBps=round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
                         step_frac=round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-    out.update(config=dict(workload=f"{args.config}: {P} Gaussians, SH deg {D}, {W}x{H}, mu={mu}, seed 0",
+    out.update(config=dict(workload=workload,
                            P=P, V=V, R=R, R_staged_fwd=Rp, views_per_step=world * kviews, parallelism=parallelism),
                roofline=roofline, kernels=kern,
                kernels_note=f"per-kernel ms: HIP events on the launch stream; '{DOMINANT_STAGE}' over the timed region, the "
@@ -936,10 +1001,7 @@ def run_rank(args, rank, world, dev, phase=None, grouped=None):
                             "would add ~80 us of event drains per step); 'preprocess_color' is timed in line here -- in the "
                             "timed region it runs on the library's helper stream beside 'preprocess' and 'depth_sort', so the "
                             "kernels add up to more than the step")
-    if args.debug_mask:
-        out["config"]["debug_mask"] = args.debug_mask   # a diagnostic run of an alternate path, not the headline
-    if args.library:
-        out["config"]["library"] = os.path.basename(args.library)   # a diagnostic run of an A/B build, not the headline
+    diagnostic_config(out, args)
     if world == 1 and not args.no_extras:
         out["two_views_in_flight"] = bench_views_in_flight(scene, D, W, H, dev)
         out["loss_l1_ssim"] = bench_loss(state["color"].detach(), dev)

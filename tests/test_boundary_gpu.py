@@ -326,12 +326,12 @@ def test_error_return_after_the_fork_still_joins_and_thread_release_frees():
 
 
 def test_bench_line_carries_the_contract_fields():
-    """`python bench.py` prints ONE JSON line with the fields the task statement names, including `roofline` for the
+    """`python bench.py --full` prints ONE JSON line with the fields the task statement names, including `roofline` for the
     dominant kernel and `cpu_baseline` (here at C1, where the CPU legs take a second)."""
     _need_gpu()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "4", "--warmup", "1",
-                        "--settle-steps", "3", "--no-train-step"], env=env, capture_output=True, text=True, timeout=600)
+                        "--settle-steps", "3", "--no-train-step", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -354,6 +354,37 @@ def test_bench_line_carries_the_contract_fields():
     assert d["settle"]["steps"] == 3 and d["step_ms"]["n"] == 4
 
 
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline fields only, and --dump-outputs writes the last timed step's
+    image, radii and gradients as float32 .npy files: the same arrays, bit for bit, from two runs with the same arguments."""
+    _need_gpu()
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C1", "--steps", "5", "--warmup", "1",
+                            "--settle-steps", "2", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert k in d, k
+        assert d["steps"] == 5 and d["warmup"] == 1 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        for k in ("roofline", "kernels", "step_ms", "cpu_baseline", "parity_vs_oracle", "loss_l1_ssim", "two_views_in_flight"):
+            assert k not in d, k
+        dumps.append({f.name: np.load(f) for f in sorted((tmp_path / run).iterdir())})
+    P, W, H, D, _ = gsr_scene.CONFIGS["C1"]
+    M = (D + 1) ** 2
+    shapes = {"image.npy": (3, H, W), "radii.npy": (P,), "means2D_grad.npy": (P, 3), "means3D_grad.npy": (P, 3),
+              "shs_grad.npy": (P, M, 3), "opacities_grad.npy": (P, 1), "scales_grad.npy": (P, 3), "rotations_grad.npy": (P, 4)}
+    assert {k: v.shape for k, v in dumps[0].items()} == shapes
+    assert all(v.dtype == np.float32 for v in dumps[0].values())
+    assert (dumps[0]["radii.npy"] > 0).any() and np.abs(dumps[0]["means3D_grad.npy"]).max() > 0
+    for k, v in dumps[0].items():
+        assert np.array_equal(v, dumps[1][k]), k
+
+
 def test_bench_gpus_2_on_one_gpu_over_gloo():
     """`python bench.py --gpus 2` with no launcher starts two ranks itself; here both share the one GPU of the box and
     exchange over gloo (GSR_BENCH_BACKEND=gloo) -- the rehearsal of the view-parallel step (rasterize_view_parallel,
@@ -361,8 +392,8 @@ def test_bench_gpus_2_on_one_gpu_over_gloo():
     _need_gpu()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["GSR_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "3", "--warmup", "1"],
-                       env=env, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C1", "--steps", "3", "--warmup", "1",
+                        "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -463,7 +494,7 @@ def test_bench_view_parallel_path_over_rccl_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["GSR_BENCH_FORCE_GROUP"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C1", "--steps", "3", "--warmup", "1",
-                        "--settle-steps", "2", "--no-extras", "--no-cpu-baseline", "--collective-timeout-s", "120", "--deadline-s", "400"],
+                        "--settle-steps", "2", "--full", "--no-extras", "--no-cpu-baseline", "--collective-timeout-s", "120", "--deadline-s", "400"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

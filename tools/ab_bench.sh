@@ -6,7 +6,7 @@ for v in "$@"; do
   if [ "$v" = base ]; then LIBARG=""; else LIBARG="--library $PWD/gaussian-splatting_cc-comments_amd/libgsr_hip_$v.so"; fi
   for c in $CFGS; do
     st=30; [ "$c" = C5 ] && st=10
-    python bench.py --config $c --steps $st --warmup 5 --no-cpu-baseline --no-extras $LIBARG 2>/dev/null | python -c "
+    python bench.py --config $c --steps $st --warmup 5 --full --no-cpu-baseline --no-extras $LIBARG 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); k=d['kernels']
 print('$v', d['config']['workload'].split(':')[0], d['ms_per_step'], d['step_ms']['median'], {n:k[n]['ms'] for n in k if n not in ('preprocess','preprocess_color','binning')})"

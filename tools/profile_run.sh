@@ -11,11 +11,11 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $ROOT/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-extras"
+BENCH="python3 $ROOT/bench.py --config $CFG --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH > "$OUT/trace.log" 2>&1 || { tail -5 "$OUT/trace.log"; exit 1; }
 cp "$(ls "$OUT"/trace/*/*kernel_stats.csv | head -1)" "$OUT/kernel_stats.csv"
 python3 "$ROOT/tools/timeline.py" "$(ls "$OUT"/trace/*/*kernel_trace.csv | head -1)" 10 > "$OUT/timeline.txt" 2>&1 || tail -3 "$OUT/timeline.txt"
-BENCH="python3 $ROOT/bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-extras"
+BENCH="python3 $ROOT/bench.py --config $CFG --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras"
 n=0
 for counters in "FETCH_SIZE" "WRITE_SIZE" \
     "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/$TAG.trace
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 $ROOT/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-extras "$@" > "$OUT.log" 2>&1 || { tail -5 "$OUT.log"; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 $ROOT/bench.py --config $CFG --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras "$@" > "$OUT.log" 2>&1 || { tail -5 "$OUT.log"; exit 1; }
 python3 "$ROOT/tools/timeline.py" "$(ls "$OUT"/*/*kernel_trace.csv | head -1)" 10 > "$ROOT/gpurun_out/${TAG}_timeline.txt"
 cp "$(ls "$OUT"/*/*kernel_stats.csv | head -1)" "$ROOT/gpurun_out/${TAG}_kernel_stats.csv"
 rm -rf "$OUT"
