@@ -276,6 +276,35 @@ extern "C" size_t gsr_backward_scratch_bytes(int P, int64_t R)
 	return gsr_align_up((size_t)R * sizeof(GsrGradSlot));
 }
 
+// ---- depth and alpha maps: the scratch the forward leaves for the backward -----------------------
+extern "C" int gsr_aux_layout_of(int64_t R, int W, int H, gsr_aux_layout* o)
+{
+	if (R < 0 || W < 0 || H < 0 || !o) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_aux_layout_of: bad arguments");
+	size_t off = 0;
+	o->ckpt_depth = off; off = gsr_align_up(off + gsr_checkpoint_records(R) * 256 * sizeof(float));
+	o->final_D = off;    off = gsr_align_up(off + (size_t)W * H * sizeof(float));
+	o->total = off;
+	return GSR_OK;
+}
+extern "C" size_t gsr_aux_bytes(int64_t R, int W, int H)
+{
+	gsr_aux_layout l;
+	return gsr_aux_layout_of(R, W, H, &l) == GSR_OK ? l.total : 0;
+}
+static bool gsr_aux_mode_ok(int mode) { return mode == GSR_AUX_DEPTH || mode == GSR_AUX_INVDEPTH; }
+static GsrAuxBlend gsr_aux_view(const gsr_aux_args& x, int64_t R, int W, int H)
+{
+	gsr_aux_layout l;
+	gsr_aux_layout_of(R, W, H, &l);
+	char* b = (char*)x.scratch;
+	GsrAuxBlend a;
+	a.out_depth = x.out_depth; a.out_alpha = x.out_alpha;
+	a.ckpt_depth = (float*)(b + l.ckpt_depth);
+	a.final_D = (float*)(b + l.final_D);
+	a.dL_ddepth = x.dL_ddepth; a.dL_dalpha = x.dL_dalpha;
+	return a;
+}
+
 GsrGeometry gsr_geometry_view(void* blob, int P)
 {
 	gsr_geometry_layout l;
@@ -425,7 +454,7 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
                                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                                        const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
                                        int prefiltered, int* radii, void* geometry, int64_t* num_rendered_host,
-                                       void* stream, int debug)
+                                       void* stream, int debug, int aux = 0)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
@@ -507,7 +536,7 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 	gsr_launch_zero_status(a.g.status, s, beside ? td.aux_fork : nullptr);
 	if (beside) {
 		if ((rc = gsr_check_hip(hipStreamWaitEvent(td.aux_stream, td.aux_fork, 0), "hipStreamWaitEvent(fork)"))) return rc;
-		gsr_launch_preprocess_color(a, td.aux_stream, P <= GSR_COLOR_BESIDE_MAX_P ? GSR_COLOR_BESIDE_WGS : 0);
+		gsr_launch_preprocess_color(a, td.aux_stream, P <= GSR_COLOR_BESIDE_MAX_P ? GSR_COLOR_BESIDE_WGS : 0, aux);
 		if (hipEventRecord(td.aux_join, td.aux_stream) != hipSuccess) {
 			(void)hipStreamSynchronize(td.aux_stream);  // no event to wait for: wait on the host instead, then report
 			return gsr_fail(GSR_ERR_HIP, "hipEventRecord(join) failed");
@@ -534,12 +563,12 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 	}
 	{
 		GsrProfScope p(s, "preprocess");
-		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr);
+		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux);
 	}
 	if ((rc = gsr_stage_done(s, debug, "preprocess"))) return rc;
 	if (color && !beside) {
 		GsrProfScope p(s, "preprocess_color");
-		gsr_launch_preprocess_color(a, s);
+		gsr_launch_preprocess_color(a, s, 0, aux);
 	}
 	if ((rc = gsr_stage_done(s, debug, "preprocess_color"))) return rc;
 
@@ -642,10 +671,39 @@ extern "C" int gsr_forward_preprocess_leaf(int P, int D, int M, int width, int h
 	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug);
 }
 
+extern "C" int gsr_forward_preprocess_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* means3D,
+                                          const float* shs, const float* colors_precomp, const float* opacities,
+                                          const float* scales, float scale_modifier, const float* rotations,
+                                          const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                          int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
+{
+	g_err[0] = 0;
+	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess_aux: aux is NULL or its mode is unknown");
+	return gsr_forward_preprocess_impl(P, D, M, width, height, means3D, shs, nullptr, 0, colors_precomp, opacities, scales,
+	                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
+	                                   tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux->mode);
+}
+
+extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* xyz,
+                                               const float* features_dc, const float* features_rest,
+                                               const float* opacity_logits, const float* log_scales, float scale_modifier,
+                                               const float* raw_rotations, const float* viewmatrix, const float* projmatrix,
+                                               const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                               int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
+                                               int debug)
+{
+	g_err[0] = 0;
+	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess_leaf_aux: aux is NULL or its mode is unknown");
+	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
+	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
+	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux->mode);
+}
+
 // ---- forward, stage 2 --------------------------------------------------------------------------
-extern "C" int gsr_forward_render(int P, int64_t R, int width, int height, const float* background,
-                                  const int* radii, void* geometry, void* binning, void* image, float* out_color,
-                                  void* stream, int debug)
+static int gsr_forward_render_impl(int P, int64_t R, int width, int height, const float* background,
+                                   const int* radii, void* geometry, void* binning, void* image, float* out_color,
+                                   void* stream, int debug, const gsr_aux_args* aux)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
@@ -722,9 +780,33 @@ extern "C" int gsr_forward_render(int P, int64_t R, int width, int height, const
 	if ((rc = gsr_stage_done(s, debug, "tile_order"))) return rc;
 	{
 		GsrProfScope p(s, "render_forward");
+		if (aux) {
+			const GsrAuxBlend x = gsr_aux_view(*aux, R, width, height);
+			gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s, &x);
+		} else {
 				gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s);
+		}
 	}
 	return gsr_stage_done(s, debug, "render_forward");
+}
+
+extern "C" int gsr_forward_render(int P, int64_t R, int width, int height, const float* background,
+                                  const int* radii, void* geometry, void* binning, void* image, float* out_color,
+                                  void* stream, int debug)
+{
+	return gsr_forward_render_impl(P, R, width, height, background, radii, geometry, binning, image, out_color, stream, debug, nullptr);
+}
+
+extern "C" int gsr_forward_render_aux(const gsr_aux_args* aux, int P, int64_t R, int width, int height, const float* background,
+                                      const int* radii, void* geometry, void* binning, void* image, float* out_color,
+                                      void* stream, int debug)
+{
+	g_err[0] = 0;
+	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: aux is NULL or its mode is unknown");
+	if (P > 0 && (!aux->out_depth || !aux->out_alpha || !aux->scratch))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: out_depth, out_alpha and scratch are required");
+	if (!aligned16(aux->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: scratch must be 16-byte aligned");
+	return gsr_forward_render_impl(P, R, width, height, background, radii, geometry, binning, image, out_color, stream, debug, aux);
 }
 
 // ---- backward ----------------------------------------------------------------------------------
@@ -764,7 +846,7 @@ static uint8_t* gsr_slot_valid_of(const gsr_backward_args& a)
 	return (uint8_t*)gsr_binning_view(a.binning, a.P, a.num_rendered, a.width, a.height).tile_keys_alt;
 }
 
-extern "C" int gsr_backward_blend(const gsr_backward_args* args)
+static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_args* aux)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend: args is NULL");
@@ -786,13 +868,38 @@ extern "C" int gsr_backward_blend(const gsr_backward_args* args)
 		hipEvent_t t0 = nullptr, t1 = nullptr;
 		const bool own = gsr_prof_kernel_events(s, "render_backward", &t0, &t1);
 		GsrProfScope p(s, own ? nullptr : "render_backward");
-		gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
-		                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1);
+		if (aux) {
+			const GsrAuxBlend x = gsr_aux_view(*aux, a.num_rendered, a.width, a.height);
+			gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
+			                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1, &x);
+		} else {
+			gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
+			                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1);
+		}
 	}
 	return gsr_stage_done(s, a.debug, "render_backward");
 }
 
-extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
+extern "C" int gsr_backward_blend(const gsr_backward_args* args) { return gsr_backward_blend_impl(args, nullptr); }
+
+static int gsr_aux_check(const gsr_aux_args* aux, const char* who)
+{
+	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: aux is NULL or its mode is unknown", who);
+	if (!aligned16(aux->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	return GSR_OK;
+}
+
+extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_aux_args* aux)
+{
+	g_err[0] = 0;
+	int rc;
+	if ((rc = gsr_aux_check(aux, "gsr_backward_blend_aux"))) return rc;
+	if (args && args->P > 0 && args->num_rendered > 0 && !aux->scratch)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend_aux: scratch is NULL");
+	return gsr_backward_blend_impl(args, aux);
+}
+
+static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
@@ -821,9 +928,22 @@ extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, 
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, s);
+		gsr_launch_gaussian_backward(a, s, aux);
 	}
 	return gsr_stage_done(s, b.debug, "gaussian_backward");
+}
+
+extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
+{
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, 0);
+}
+
+extern "C" int gsr_backward_gaussians_aux(const gsr_backward_args* args, const gsr_aux_args* aux, int first, int count, int out_row0)
+{
+	g_err[0] = 0;
+	int rc;
+	if ((rc = gsr_aux_check(aux, "gsr_backward_gaussians_aux"))) return rc;
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux->mode);
 }
 
 static int gsr_backward_whole(const gsr_backward_args& a)

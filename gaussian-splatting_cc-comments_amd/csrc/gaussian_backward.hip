@@ -158,12 +158,20 @@ __device__ __forceinline__ uint32_t gsr_slot_mask_first(unsigned long long m) { 
 // requested: asking for both at once -- the record of an invalid slot is readable garbage -- saves a round trip per 64 slots and
 // was measured in round 4: per-Gaussian backward 0.120 -> 0.129 ms at C3, 0.63 -> 0.80 at C5 (the records of the invalid slots are
 // traffic, and four more 16-byte registers in flight cost a wave per SIMD).
+// (AUX: the tenth word, dL/dv of the depth-and-alpha variant, is added into acc[9])
+template <int AUX>
 __device__ __forceinline__ void gsr_add_slot(const GsrGradSlot* __restrict__ slots, const uint8_t* __restrict__ valid,
                                              uint32_t s, float* acc)
 {
 	if (!valid[s]) return;
 	const float4* sl = reinterpret_cast<const float4*>(slots + s);
 	const float4 s0 = sl[0], s1 = sl[1];
+	if (AUX) {
+		const float2 s2 = reinterpret_cast<const float2*>(sl + 2)[0];
+		acc[0] += s0.x; acc[1] += s0.y; acc[2] += s0.z; acc[3] += s0.w; acc[4] += s1.x;
+		acc[5] += s1.y; acc[6] += s1.z; acc[7] += s1.w; acc[8] += s2.x; acc[9] += s2.y;
+		return;
+	}
 	const float s2 = sl[2].x;
 	acc[0] += s0.x; acc[1] += s0.y; acc[2] += s0.z; acc[3] += s0.w; acc[4] += s1.x;
 	acc[5] += s1.y; acc[6] += s1.z; acc[7] += s1.w; acc[8] += s2;
@@ -172,8 +180,10 @@ __device__ __forceinline__ void gsr_add_slot(const GsrGradSlot* __restrict__ slo
 // LEAF: inputs are the optimiser's raw leaves and the outputs are gradients w.r.t. them: the backward
 // of exp / sigmoid / normalize / cat (gaussian_model.py:114-135) is applied in the epilogue.
 // workgroup = one wave: waves of a CU then start and retire independently (phases of different waves mix)
+// AUX: 0, or the depth-and-alpha mode (include/gsr.h GSR_AUX_*): the slots' tenth word dL/dv is summed too and chained into dL/dmean3D
+// through v = z (GSR_AUX_DEPTH) or 1 / z (GSR_AUX_INVDEPTH), z the view-space depth: dL/dmean3D += dL/dz (V[2], V[6], V[10]).
 #define GSR_GB_THREADS 64
-template <bool LEAF>
+template <bool LEAF, int AUX>
 __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(GsrGaussianBackwardArgs a, int sh_via_lds, int skip_dsh)
 {
 	// staging of the dL/dsh output block: rows of 13 float4; the packed layout goes out in two halves of 32 rows
@@ -244,13 +254,14 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 	// ---- (E) fixed-order sum of this Gaussian's (Gaussian,tile) slots: its VALID slots in ascending order, six per round;
 	//      the records of a round are all requested before the first add, and only by the lanes that have one (a lane's
 	//      record is a line of its own here too: masked-off lanes cost nothing)
-	float acc[GSR_NACC];
+	constexpr int NACC = AUX ? GSR_NACC + 1 : GSR_NACC;
+	float acc[NACC];
 #pragma unroll
-	for (int i = 0; i < GSR_NACC; i++) acc[i] = 0.f;
+	for (int i = 0; i < NACC; i++) acc[i] = 0.f;
 	GsrSlotMask rem = vmask;
 	while (rem) {
 		float4 s0[GSR_SLOT_ROUND], s1[GSR_SLOT_ROUND];
-		float s2[GSR_SLOT_ROUND];
+		float s2[GSR_SLOT_ROUND], s3[GSR_SLOT_ROUND];   // s3: AUX only
 		bool ok[GSR_SLOT_ROUND];
 #pragma unroll
 		for (int j = 0; j < GSR_SLOT_ROUND; j++) {
@@ -259,7 +270,13 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 			rem &= rem - (GsrSlotMask)1;
 			if (ok[j]) {
 				const float4* sl = reinterpret_cast<const float4*>(a.slots + (base + k));
-				s0[j] = sl[0]; s1[j] = sl[1]; s2[j] = sl[2].x;
+				s0[j] = sl[0]; s1[j] = sl[1];
+				if (AUX) {
+					const float2 t = reinterpret_cast<const float2*>(sl + 2)[0];
+					s2[j] = t.x; s3[j] = t.y;
+				} else {
+					s2[j] = sl[2].x;
+				}
 			}
 		}
 #pragma unroll
@@ -267,6 +284,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 			if (ok[j]) {
 				acc[0] += s0[j].x; acc[1] += s0[j].y; acc[2] += s0[j].z; acc[3] += s0[j].w; acc[4] += s1[j].x;
 				acc[5] += s1[j].y; acc[6] += s1[j].z; acc[7] += s1[j].w; acc[8] += s2[j];
+				if (AUX) acc[NACC - 1] += s3[j];
 			}
 	}
 	unsigned long long big = __builtin_amdgcn_ballot_w64(tiles > GSR_SLOT_COOP);
@@ -274,12 +292,12 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 		const int src = __ffsll((long long)big) - 1;
 		big &= big - 1;
 		const uint32_t s_tiles = __shfl(tiles, src, 64), s_base = __shfl(base, src, 64);
-		float part[GSR_NACC];
+		float part[NACC];
 #pragma unroll
-		for (int i = 0; i < GSR_NACC; i++) part[i] = 0.f;
-		for (uint32_t k = lane; k < s_tiles; k += 64) gsr_add_slot(a.slots, a.slot_valid, s_base + k, part);
+		for (int i = 0; i < NACC; i++) part[i] = 0.f;
+		for (uint32_t k = lane; k < s_tiles; k += 64) gsr_add_slot<AUX>(a.slots, a.slot_valid, s_base + k, part);
 #pragma unroll
-		for (int i = 0; i < GSR_NACC; i++) {
+		for (int i = 0; i < NACC; i++) {
 			const float tot = __shfl(gsr_wave_sum_to_lane63(part[i]), 63, 64);
 			if (lane == src) acc[i] = tot;
 		}
@@ -373,6 +391,13 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 		dmean3D[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
 		dmean3D[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
 		dmean3D[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
+		if (AUX) {   // the depth value's own path: v = z or 1 / z, z = (V mean)_z
+			const float dv = acc[NACC - 1];
+			const float dz = AUX == GSR_AUX_INVDEPTH ? -dv / (t.z * t.z) : dv;
+			dmean3D[0] += dz * vm[2];
+			dmean3D[1] += dz * vm[6];
+			dmean3D[2] += dz * vm[10];
+		}
 
 		if (a.shs) {
 			if (sh_via_lds) {
@@ -492,16 +517,29 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 	}
 }
 
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s)
+template <int AUX>
+static void gsr_launch_gaussian_backward_t(const GsrGaussianBackwardArgs& a, hipStream_t s, int sh_via_lds, int skip_dsh)
+{
+	if (a.leaf) hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, AUX>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+	else hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, AUX>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+}
+
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux)
 {
 	// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
 	const int skip_dsh = (a.shs && !a.dL_dsh) ? 1 : 0;  // view-parallel mode (include/gsr.h)
 	int sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
+	if (aux) {
+		if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH>(a, s, sh_via_lds, skip_dsh);
+		else gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH>(a, s, sh_via_lds, skip_dsh);
+		return;
+	}
 	if (a.leaf) {
 		if (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0)) sh_via_lds = 0;
-		hipLaunchKernelGGL(gsr_gaussian_backward_kernel<true>, dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, 0>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
 	} else {
-		hipLaunchKernelGGL(gsr_gaussian_backward_kernel<false>, dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, 0>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
 	}
 }
 

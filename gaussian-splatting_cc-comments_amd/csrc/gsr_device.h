@@ -34,7 +34,7 @@ struct __attribute__((aligned(16))) GsrSplat {
 	uint32_t rect_min;    // tile rect min: x | y << 16
 	uint32_t rect_wh;     // tile rect size: w | h << 16
 	float r, g, b;        // colour (SH colour clamped at 0, or colors_precomp)
-	uint32_t unused;
+	uint32_t unused;      // 0; the depth-and-alpha variants store the Gaussian's depth value v here (float bits, gsr_aux_value)
 };
 static_assert(sizeof(GsrSplat) == 48, "splat record must be 48 bytes");
 
@@ -44,9 +44,17 @@ struct __attribute__((aligned(16))) GsrGradSlot {
 	float dca, dcb;       // dL/dconic .x .y
 	float dcc, dop;       // dL/dconic .w, dL/dopacity
 	float dr, dg;
-	float db, pad0, pad1, pad2;
+	float db, pad0, pad1, pad2;   // pad0: dL/dv of the depth-and-alpha variant (render_backward.hip); unused otherwise
 };
 static_assert(sizeof(GsrGradSlot) == 48, "grad slot must be 48 bytes");
+
+// Depth value v of a Gaussian in the depth-and-alpha variants (include/gsr.h gsr_aux_args): the view-space z the geometry kernel
+// sorts by (GSR_AUX_DEPTH) or its reciprocal (GSR_AUX_INVDEPTH).  AUX is the mode as a template argument; 0 = the default kernels.
+template <int AUX>
+__device__ __forceinline__ float gsr_aux_value(float z)
+{
+	return AUX == 2 ? 1.0f / z : z;   // 2: GSR_AUX_INVDEPTH
+}
 
 struct GsrMat3 { float m[3][3]; };  // m[col][row] as glm
 struct GsrVec3 { float x, y, z; };

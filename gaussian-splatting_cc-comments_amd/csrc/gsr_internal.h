@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/gsr.h"
+#include "../../include/gsr_aux.h"
 #include "gsr_device.h"
 
 #define GSR_PREPROCESS_BLOCK 256  // Gaussians per workgroup of the binning kernels (granularity of their scans)
@@ -78,6 +79,16 @@ struct GsrBinning {
 	float4* checkpoints;       // [gsr_checkpoint_records(R)][256] depth checkpoints of heavy tiles (see GSR_CKPT_STRIDE)
 };
 
+// Per-call pointers of the depth-and-alpha variants of the blend kernels (include/gsr.h gsr_aux_args)
+struct GsrAuxBlend {
+	float* out_depth;          // [W*H] forward outputs
+	float* out_alpha;
+	float* ckpt_depth;         // [gsr_checkpoint_records(R)][256] per-pixel D beside each (T, C) checkpoint
+	float* final_D;            // [W*H] D of heavy tiles' pixels (as final_C)
+	const float* dL_ddepth;    // [W*H] backward inputs, NULL = zero
+	const float* dL_dalpha;
+};
+
 GsrGeometry gsr_geometry_view(void* blob, int P);
 GsrImage gsr_image_view(void* blob, int W, int H);
 GsrBinning gsr_binning_view(void* blob, int P, int64_t R, int W, int H);
@@ -124,10 +135,11 @@ struct GsrPreprocessArgs {
 };
 
 // preprocess.hip
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done = nullptr);
+// aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the kernels then also store the depth value v in the splat record's last word
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done = nullptr, int aux = 0);
 void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done = nullptr);
 bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a);
-void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu = 0);
+void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu = 0, int aux = 0);
 void gsr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
 
 // binning.hip
@@ -175,12 +187,14 @@ int gsr_tile_key_bytes(int ntiles, size_t num_rendered);
 
 // render_forward.hip
 void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float4* checkpoints,
-                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s);   // ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries
+                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s,
+                               const GsrAuxBlend* aux = nullptr);   // ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries; aux: the depth-and-alpha variant
 
 // render_backward.hip
 void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
                                 const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start = nullptr, hipEvent_t t_stop = nullptr);   // t_*: taken by the kernel's own dispatch packet
+                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start = nullptr, hipEvent_t t_stop = nullptr,
+                                const GsrAuxBlend* aux = nullptr);   // t_*: taken by the kernel's own dispatch packet; aux: the depth-and-alpha variant
 
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
@@ -222,7 +236,8 @@ struct GsrGaussianBackwardArgs {
 	float* stat_denom;               // [P] += 1 for visible Gaussians
 	float* stat_max_radii2D;         // [P] = max(itself, radius) for visible Gaussians
 };
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s);
+// aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the slots' tenth word (dL/dv) is summed and chained into dL/dmean3D
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux = 0);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,
                                    int64_t view_stride, float* dL_dsh, hipStream_t s);
 

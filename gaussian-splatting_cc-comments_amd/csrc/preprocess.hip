@@ -43,7 +43,9 @@ __device__ __forceinline__ float gsr_sh_channel(int deg, const float* sh, int ch
 // Both write disjoint 16-byte-aligned parts of the 48-byte splat record.  Precomputed colours need no second kernel.
 //
 // LEAF: the inputs are the optimiser's raw leaves (gsr_internal.h); activations happen here.
-template <bool LEAF>
+// AUX: 0, or the depth-and-alpha mode (include/gsr.h GSR_AUX_*): the colors_precomp path then stores the depth value v in the
+// record's last word (the colour kernel does it on the SH path).
+template <bool LEAF, int AUX>
 __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(GsrPreprocessArgs a, uint32_t* __restrict__ clear, size_t clear_words,
                                                                               uint32_t* __restrict__ clear2, size_t clear2_words)
 {
@@ -126,7 +128,7 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 			rshape.x = gsr_rect_pack((uint32_t)minx, (uint32_t)miny, (uint32_t)(maxx - minx), (uint32_t)(maxy - miny));
 			if (a.trim) rshape.y = gsr_rect_trim(pix, piy, conic_a, conic_b, conic_c, opacity, minx, miny, maxx - minx, maxy - miny);
 			if (a.colors_precomp) {
-				rec[2] = make_float4(col_in[0], col_in[1], col_in[2], 0.f);
+				rec[2] = make_float4(col_in[0], col_in[1], col_in[2], AUX ? gsr_aux_value<AUX>(p_view.z) : 0.f);
 				a.g.clamped[idx] = 0;
 			}
 		} while (0);
@@ -197,7 +199,7 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 // clamp flags, and the nine derivatives d colour / d direction the backward needs (so that it never reads the 192-byte row
 // again).  Done for every Gaussian in front of the near plane -- a superset of those the geometry kernel keeps (it
 // also drops det == 0 and empty rectangles); what is written for the difference is never read.
-template <bool LEAF>
+template <bool LEAF, int AUX>
 __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_color_kernel(GsrPreprocessArgs a, int sh_via_lds)
 {
 	// staging of the wave's SH block in two halves of 32 rows (6.6 KB per wave, so that 4 waves per SIMD fit): the packed layout
@@ -277,7 +279,9 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_color_ker
 		rgb[ch] = fmaxf(v, 0.0f);
 	}
 	a.g.clamped[idx] = clamp_bits;
-	reinterpret_cast<float4*>(a.g.splat + idx)[2] = make_float4(rgb[0], rgb[1], rgb[2], 0.f);   // the record's last 16 bytes: one aligned store per lane
+	// the record's last 16 bytes: one aligned store per lane (the depth-and-alpha variant: v in the fourth word, same store)
+	reinterpret_cast<float4*>(a.g.splat + idx)[2] =
+		make_float4(rgb[0], rgb[1], rgb[2], AUX ? gsr_aux_value<AUX>(gsr_transform_point_4x3(p_orig, a.viewmatrix).z) : 0.f);
 }
 
 // The status words (instance count and depth range as 64-way partial sums / maxima, the prefiltered flag) start at zero.  A kernel
@@ -297,20 +301,34 @@ void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done)
 
 // done: optional event signalled by the kernel's own dispatch packet when it has finished (hipExtLaunchKernelGGL): a separate
 // hipEventRecord behind the kernel is a barrier packet of its own and costs the stream's next launch ~8 us
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done)
+// the depth-and-alpha variants: one instantiation per (LEAF, mode)
+template <int AUX>
+static void gsr_launch_preprocess_aux(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int nb, uint32_t* clear, size_t clear_words,
+                                      uint32_t* clear2, size_t clear2_words)
+{
+	if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+	else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+}
+
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
 	uint32_t* clear = (uint32_t*)a.g.sort_table;
 	const size_t clear_words = gsr_radix_clear_words((size_t)a.P);
 	uint32_t* clear2 = (uint32_t*)a.g.col_table;
 	const size_t clear2_words = gsr_tilebin_col_clear_words((size_t)a.P);
-	if (done) {
-		if (a.leaf) hipExtLaunchKernelGGL(gsr_preprocess_kernel<true>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-		else hipExtLaunchKernelGGL(gsr_preprocess_kernel<false>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+	if (aux) {
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		else gsr_launch_preprocess_aux<GSR_AUX_DEPTH>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
 		return;
 	}
-	if (a.leaf) hipLaunchKernelGGL(gsr_preprocess_kernel<true>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
-	else hipLaunchKernelGGL(gsr_preprocess_kernel<false>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
+	if (done) {
+		if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+		else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+		return;
+	}
+	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
+	else hipLaunchKernelGGL((gsr_preprocess_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
 }
 
 // the colour kernel exists only for SH colours
@@ -318,7 +336,14 @@ bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a) { return a.shs && !a
 
 // wgs_per_cu: 0 = as many workgroups per CU as fit; else the kernel is held to that many by (unused) dynamic LDS on top of its own
 // staging area (26 KB) -- while it runs beside the depth sort on the helper stream (api.hip)
-void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu)
+template <int AUX>
+static void gsr_launch_preprocess_color_aux(const GsrPreprocessArgs& a, hipStream_t s, int nb, size_t throttle, int sh_via_lds)
+{
+	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_color_kernel<true, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
+	else hipLaunchKernelGGL((gsr_preprocess_color_kernel<false, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
+}
+
+void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu, int aux)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
 	// LDS-transposed SH path: the flagship layout (16 coefficients), 16-byte aligned tensor
@@ -326,11 +351,17 @@ void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int 
 	const size_t own = (size_t)(GSR_PREPROCESS_BLOCK / 64) * 32 * GSR_SH_ROW4 * sizeof(float4);
 	const size_t share = wgs_per_cu > 0 ? (size_t)160 * 1024 / (size_t)wgs_per_cu : 0;
 	const size_t throttle = share > own + 1024 ? share - own - 1024 : 0;   // (1 KB of slack for allocation granularity)
+	if (a.leaf && ((uintptr_t)a.shs_rest & 15u) != 0) sh_via_lds = 0;
+	if (aux) {
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_color_aux<GSR_AUX_INVDEPTH>(a, s, nb, throttle, sh_via_lds);
+		else gsr_launch_preprocess_color_aux<GSR_AUX_DEPTH>(a, s, nb, throttle, sh_via_lds);
+		return;
+	}
 	if (a.leaf) {
 		if (((uintptr_t)a.shs_rest & 15u) != 0) sh_via_lds = 0;
-		hipLaunchKernelGGL(gsr_preprocess_color_kernel<true>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
+		hipLaunchKernelGGL((gsr_preprocess_color_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
 	} else {
-		hipLaunchKernelGGL(gsr_preprocess_color_kernel<false>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
+		hipLaunchKernelGGL((gsr_preprocess_color_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
 	}
 }
 

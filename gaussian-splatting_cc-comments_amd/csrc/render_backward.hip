@@ -33,12 +33,17 @@ __device__ __forceinline__ float gsr_add_halves(v2f a)
 	return r;
 }
 
+// AUX (the depth-and-alpha variant, include/gsr.h gsr_aux_args): the depth channel is a fourth colour channel with background 0 --
+// its accum_rec (restarted from ckpt_depth / final_D by the depth segments), (v - accum_rec_D) dL/dD in dL/dalpha -- dL/dA enters
+// through the background term (A = 1 - T_final: -T_final (bg . dL/dpix - dL/dA)), and dL/dv = sum alpha T dL/dD is a tenth reduced
+// partial, written to the slot's pad0.  Same slots, same order, no atomics.
+template <bool AUX>
 __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) gsr_render_backward_wave_kernel(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
 	const GsrSplat* __restrict__ splat, const float4* __restrict__ checkpoints, const float* __restrict__ final_C, const uint32_t* __restrict__ slot_base, const float* __restrict__ bg,
 	const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,
 	const uint32_t* __restrict__ tile_order, const float* __restrict__ dL_dpixels, GsrGradSlot* __restrict__ slots,
-	uint8_t* __restrict__ slot_valid, int cull)
+	uint8_t* __restrict__ slot_valid, int cull, GsrAuxBlend aux)
 {
 	// per-wave staging of the surviving instances of a batch.  Every per-instance scalar that meets the
 	// float2 pixel pairs is stored TWICE, so a ds_read_b128 delivers it as an aligned register pair ready
@@ -46,7 +51,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	// (ROCm 7.2's compiler does fold a splat into op_sel / op_sel_hi for most packed operands by now; re-measured in round 3
 	// with every scalar stored once -- three ds_read_b128 per instance instead of five and a dword, 119 VGPRs: 0.467 ->
 	// 0.476 ms at C3, 1.616 -> 1.633 at C5, results identical.  The duplicated layout stays.)
-	__shared__ float4 s_rec[GSR_WAVES_PER_WG][5][64];
+	__shared__ float4 s_rec[GSR_WAVES_PER_WG][AUX ? 6 : 5][64];   // AUX: rec[5] = (v, v, -, -)
 	__shared__ uint32_t s_bands[GSR_WAVES_PER_WG][64];
 	// transposition area of the per-instance wave reduction: lane l stores its eight partials at row l (row stride 9 words:
 	// 9 is odd, so the 64 rows of one store instruction fall into 64 different banks), then the eight lanes of group c read
@@ -96,6 +101,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	v2f T[2], tfb[2];                 // running T; -T_final * (bg . dL/dpix)
 	v2f ac0[2], ac1[2], ac2[2];       // accum_rec as the NEXT hit will see it
 	v2f dp0[2], dp1[2], dp2[2];
+	v2f dpD[2], acD[2];               // AUX only: dL/dD, the depth channel's accum_rec
 	int last_contributor[GSR_PIX_PER_LANE];
 	v2f pfy[2];
 #pragma unroll
@@ -110,11 +116,21 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 		last_contributor[k] = inside ? (int)n_contrib[pix_id] : 0;
 		T[k >> 1][k & 1] = Tf;
 		dp0[k >> 1][k & 1] = d0; dp1[k >> 1][k & 1] = d1; dp2[k >> 1][k & 1] = d2;
-		tfb[k >> 1][k & 1] = -Tf * (bg0 * d0 + bg1 * d1 + bg2 * d2);
+		if (AUX) {
+			const float dD = (inside && aux.dL_ddepth) ? aux.dL_ddepth[pix_id] : 0.f;
+			const float dA = (inside && aux.dL_dalpha) ? aux.dL_dalpha[pix_id] : 0.f;
+			dpD[k >> 1][k & 1] = dD;
+			tfb[k >> 1][k & 1] = -Tf * ((bg0 * d0 + bg1 * d1 + bg2 * d2) - dA);
+		} else {
+			tfb[k >> 1][k & 1] = -Tf * (bg0 * d0 + bg1 * d1 + bg2 * d2);
+		}
 		pfy[k >> 1][k & 1] = (float)py;
 	}
 #pragma unroll
-	for (int p = 0; p < 2; p++) ac0[p] = ac1[p] = ac2[p] = v2f{0.f, 0.f};
+	for (int p = 0; p < 2; p++) {
+		ac0[p] = ac1[p] = ac2[p] = v2f{0.f, 0.f};
+		if (AUX) acD[p] = v2f{0.f, 0.f};
+	}
 	if (top < n) {
 		// The walk starts in the middle of the list.  The forward stored every pixel's (T, C) before the instance at position
 		// `top`; what lies behind it blended to C_final - C, seen through T: the running T is the checkpoint's, and accum_rec --
@@ -135,6 +151,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				ac0[k >> 1][k & 1] = (final_C[pix_id] - c.y) * inv;
 				ac1[k >> 1][k & 1] = (final_C[plane + pix_id] - c.z) * inv;
 				ac2[k >> 1][k & 1] = (final_C[2 * plane + pix_id] - c.w) * inv;
+				if (AUX) acD[k >> 1][k & 1] = (aux.final_D[pix_id] - aux.ckpt_depth[((size_t)(range.x + (uint32_t)top) / GSR_CKPT_STRIDE) * 256 + lane + 64 * k]) * inv;
 			}
 		}
 	}
@@ -150,7 +167,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	}
 
 	// back to front: batch position q = base + lane maps to range position top - 1 - q (top = n for a whole tile, the end of the segment otherwise)
-	float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;
+	float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;   // (rc.w: the depth value v in the AUX variant)
 	uint32_t sbase = 0u;  // first gradient slot of the staged Gaussian (dense per-Gaussian array, cache resident)
 	if (lane < nw) {
 		const uint32_t id = plist[top - 1 - lane];
@@ -187,6 +204,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			rec[2][pos] = make_float4(-0.5f * rb.x, -0.5f * rb.x, rb.y, rb.y);  // -0.5 conic c, opacity
 			rec[3][pos] = make_float4(rc.x, rc.x, rc.y, rc.y);  // r, g
 			rec[4][pos] = make_float4(rc.z, rc.z, __int_as_float(top - 1 - (base + lane)), __uint_as_float(slot));  // b, position in the full range, slot
+			if (AUX) rec[5][pos] = make_float4(rc.w, rc.w, 0.f, 0.f);   // depth value v
 			recb[pos] = bands;
 		}
 		if (base + 64 + lane < nw) {
@@ -203,15 +221,17 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			const uint32_t bands = __builtin_amdgcn_readfirstlane(recb[j]);                 // wave-uniform
 			const v2f X = {R0.x, R0.y}, Y = {R0.z, R0.w}, CA = {R1.x, R1.y}, CB = {R1.z, R1.w}, CC = {R2.x, R2.y}, OP = {R2.z, R2.w};
 			const v2f C0 = {R3.x, R3.y}, C1 = {R3.z, R3.w}, C2 = {R4.x, R4.y};
+			v2f V = {0.f, 0.f};
+			if (AUX) { const float4 R5 = rec[5][j]; V = v2f{R5.x, R5.y}; }
 			const v2f dx = X - pfx2;
 			const v2f ax2 = (CA * dx) * dx, bdx = CB * dx;  // this file is compiled with -ffp-contract=off
 			// per-lane partial sums over its pixels (one float2 = two pixels, added at the end).  The
 			// geometric terms are kept as raw moments of f = G * dL/dG (sum f dx, f dy, f dx^2, f dx dy,
 			// f dy^2); the conic and the 0.5*W / 0.5*H / -0.5 factors of backward.cu:574-594 are applied
 			// once per instance after the reduction.
-			v2f acc[GSR_BWD_NV];
+			v2f acc[GSR_BWD_NV + 1];   // [9]: dL/dv (AUX)
 #pragma unroll
-			for (int i = 0; i < GSR_BWD_NV; i++) acc[i] = v2f{-0.f, -0.f};  // x + (-0) is x for every x: the first pair's sums need no add
+			for (int i = 0; i < GSR_BWD_NV + 1; i++) acc[i] = v2f{-0.f, -0.f};  // x + (-0) is x for every x: the first pair's sums need no add
 			unsigned long long any = 0ull;  // lanes with a hit, kept as a scalar mask: the loop's branches test masks, not ballots of bools
 #pragma unroll
 			for (int p = 0; p < 2; p++) {
@@ -249,6 +269,11 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				// exactly as the reference forms them; what follows only accumulates.
 				const v2f d0 = C0 - ac0[p], d1 = C1 - ac1[p], d2 = C2 - ac2[p];
 				v2f dL_dalpha = __builtin_elementwise_fma(d2, dp2[p], __builtin_elementwise_fma(d1, dp1[p], d0 * dp0[p]));
+				v2f dV = {0.f, 0.f};
+				if (AUX) {   // the depth channel: the same term and update as a colour channel
+					dV = V - acD[p];
+					dL_dalpha = __builtin_elementwise_fma(dV, dpD[p], dL_dalpha);
+				}
 				// accum_rec' = last_alpha * last_color + (1 - last_alpha) * accum_rec (backward.cu:553; the reference applies it
 				// lazily at the NEXT hit, from the same operands), written as accum_rec + alpha * (colour - accum_rec) on the
 				// difference above: one FMA per channel instead of two products and a sum, and the smaller rounding error of the
@@ -267,6 +292,10 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				ac0[p] = n0;
 				ac1[p] = n1;
 				ac2[p] = n2;
+				if (AUX) {
+					acD[p] = __builtin_elementwise_fma(alpha, dV, acD[p]);
+					acc[9] = __builtin_elementwise_fma(dch, dpD[p], acc[9]);   // dL/dv = alpha T dL/dD
+				}
 				acc[6] = __builtin_elementwise_fma(dch, dp0[p], acc[6]);
 				acc[7] = __builtin_elementwise_fma(dch, dp1[p], acc[7]);
 				acc[8] = __builtin_elementwise_fma(dch, dp2[p], acc[8]);
@@ -296,6 +325,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				// the ninth value's DPP chain runs while the LDS round trip is under way
 				__builtin_amdgcn_sched_barrier(0);
 				const float t9 = gsr_wave_sum_to_lane63(v[8]);  // lane 63 holds the total of v[8]
+				const float t10 = AUX ? gsr_wave_sum_to_lane63(gsr_add_halves(acc[9])) : 0.f;   // ... and (AUX) of dL/dv
 				__builtin_amdgcn_sched_barrier(0);
 				const float tcol = ((col[0] + col[1]) + (col[2] + col[3])) + ((col[4] + col[5]) + (col[6] + col[7]));
 				const float t8 = gsr_sum8(tcol);                // group c holds the total of v[c]
@@ -309,6 +339,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				if ((lane & 7) == 0) out[out_index] = r;
 				if (lane == 63) {
 					out[8] = t9;
+					if (AUX) out[9] = t10;
 					slot_valid[slot] = 1;
 				}
 			}
@@ -320,19 +351,25 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 
 void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
                                 const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop)
+                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const GsrAuxBlend* aux)
 {
 	const int gx = gsr_grid_x(W), gy = gsr_grid_y(H);
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (int)gsr_tile_order_max_segments(ntiles);   // whole tiles + the extra entries of heavy tiles' depth segments
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
-	if (t_start || t_stop) {
-		hipExtLaunchKernelGGL(gsr_render_backward_wave_kernel, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, 0, W, H, gx, nslots,
+	if (aux) {
+		hipExtLaunchKernelGGL(gsr_render_backward_wave_kernel<true>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, 0, W, H, gx, nslots,
 		                      img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		                      img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0);
+		                      img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, *aux);
 		return;
 	}
-	hipLaunchKernelGGL(gsr_render_backward_wave_kernel, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
+	if (t_start || t_stop) {
+		hipExtLaunchKernelGGL(gsr_render_backward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, 0, W, H, gx, nslots,
+		                      img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
+		                      img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, GsrAuxBlend{});
+		return;
+	}
+	hipLaunchKernelGGL(gsr_render_backward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
 	                   img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-	                   img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0);
+	                   img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, GsrAuxBlend{});
 }

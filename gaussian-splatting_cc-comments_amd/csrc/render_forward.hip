@@ -21,14 +21,24 @@
 #ifndef GSR_FWD_DONE_STRIDE
 #define GSR_FWD_DONE_STRIDE 16
 #endif
+// waves per SIMD of the depth-and-alpha variant: the default kernel's 6 (80 VGPRs) leave its fourth accumulator 12 bytes per lane of
+// scratch, so it runs at 5 (up to 96 VGPRs, no scratch)
+#ifndef GSR_FWD_AUX_WAVES
+#define GSR_FWD_AUX_WAVES 5
+#endif
 
 GSR_TILE_CLOCK_BUFFER(gsr_forward_tile_clock, gsr_debug_tile_clock_forward)
 
-__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(6, 6))) gsr_render_forward_wave_kernel(
+// AUX (the depth-and-alpha variant, include/gsr.h gsr_aux_args): a fourth accumulator per pixel, D += v * alpha * T, with v
+// taken from the record's last word (LDS lane rec[2].w); D and A = 1 - T are written in the epilogue, D beside every depth
+// checkpoint (ckpt_depth) and for heavy tiles in final_D.  Nothing else changes: colour, T, n_contrib are the default kernel's bits.
+template <bool AUX>
+__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(AUX ? GSR_FWD_AUX_WAVES : 6, AUX ? GSR_FWD_AUX_WAVES : 6)))
+gsr_render_forward_wave_kernel(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
 	const GsrSplat* __restrict__ splat, float4* __restrict__ checkpoints, float* __restrict__ final_C, const float* __restrict__ bg, float* __restrict__ final_T,
 	uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_max_contrib, const uint32_t* __restrict__ tile_order,
-	float* __restrict__ out_color, int cull)
+	float* __restrict__ out_color, int cull, GsrAuxBlend aux)
 {
 	__shared__ float4 s_rec[GSR_WAVES_PER_WG][3][64];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -58,6 +68,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	bool walked_deep = false;   // a checkpoint was stored: only then can the backward cut this tile, and only then is final_C read
 
 	float Tout[GSR_PIX_PER_LANE], C0[GSR_PIX_PER_LANE], C1[GSR_PIX_PER_LANE], C2[GSR_PIX_PER_LANE];
+	float Dacc[GSR_PIX_PER_LANE];   // AUX only
 	float pfy[GSR_PIX_PER_LANE];
 	uint32_t last[GSR_PIX_PER_LANE];
 	unsigned long long alive[GSR_PIX_PER_LANE];  // lanes whose pixel of band k still blends: wave-uniform, lives in SGPRs
@@ -69,6 +80,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 		Tout[k] = 1.0f;
 		alive[k] = (only == 0 || only == k + 1) ? __builtin_amdgcn_ballot_w64(px < W && py < H) : 0ull;
 		C0[k] = C1[k] = C2[k] = 0.f;
+		if (AUX) Dacc[k] = 0.f;
 		last[k] = 0u;
 	}
 
@@ -91,6 +103,12 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 #pragma unroll
 			for (int k = 0; k < GSR_PIX_PER_LANE; k++)
 				if (only == 0 || only == k + 1) ck[64 * k] = make_float4(Tout[k], C0[k], C1[k], C2[k]);
+			if (AUX) {
+				float* ckd = aux.ckpt_depth + ((size_t)(range.x + (uint32_t)base) / GSR_CKPT_STRIDE) * 256 + lane;
+#pragma unroll
+				for (int k = 0; k < GSR_PIX_PER_LANE; k++)
+					if (only == 0 || only == k + 1) ckd[64 * k] = Dacc[k];
+			}
 		}
 		const uint32_t bands = (base + lane < n) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
 		const bool keep = bands != 0u;
@@ -101,7 +119,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			const int pos = gsr_mbcnt(mask);
 			rec[0][pos] = make_float4(ra.x, ra.y, -0.5f * ra.z, ra.w);  // conic a, c pre-multiplied by -0.5 (exact)
 			rec[1][pos] = make_float4(-0.5f * rb.x, rb.y, rc.x, rc.y);
-			rec[2][pos] = make_float4(rc.z, __uint_as_float((uint32_t)(base + lane + 1)), __uint_as_float(bands), 0.f);
+			rec[2][pos] = make_float4(rc.z, __uint_as_float((uint32_t)(base + lane + 1)), __uint_as_float(bands), AUX ? rc.w : 0.f);  // AUX: depth value v
 		}
 		if (base + 64 + lane < n) {
 			const float4* p = reinterpret_cast<const float4*>(splat + id_next);
@@ -147,6 +165,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				C0[k] = __builtin_fmaf(B.z, w, C0[k]);
 				C1[k] = __builtin_fmaf(B.w, w, C1[k]);
 				C2[k] = __builtin_fmaf(Cc.x, w, C2[k]);
+				if (AUX) Dacc[k] = __builtin_fmaf(Cc.w, w, Dacc[k]);
 				Tout[k] = pass ? test_T : Tout[k];
 				last[k] = pass ? contributor : last[k];
 			}
@@ -169,6 +188,11 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			out_color[plane + pix_id] = C1[k] + Tout[k] * bg1;
 			out_color[2 * plane + pix_id] = C2[k] + Tout[k] * bg2;
 			if (walked_deep) { final_C[pix_id] = C0[k]; final_C[plane + pix_id] = C1[k]; final_C[2 * plane + pix_id] = C2[k]; }
+			if (AUX) {
+				aux.out_depth[pix_id] = Dacc[k];
+				aux.out_alpha[pix_id] = 1.0f - Tout[k];
+				if (walked_deep) aux.final_D[pix_id] = Dacc[k];
+			}
 			m = max(m, last[k]);
 		}
 	}
@@ -185,13 +209,19 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 }
 
 void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float4* checkpoints,
-                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s)
+                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s, const GsrAuxBlend* aux)
 {
 	const int gx = gsr_grid_x(W), gy = gsr_grid_y(H);
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (ordered ? 3 * (int)gsr_tile_order_max_split(ntiles) : 0);
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
-	hipLaunchKernelGGL(gsr_render_forward_wave_kernel, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
+	if (aux) {
+		hipLaunchKernelGGL(gsr_render_forward_wave_kernel<true>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
+		                   img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
+		                   ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, *aux);
+		return;
+	}
+	hipLaunchKernelGGL(gsr_render_forward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
 	                   img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-	                   ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0);
+	                   ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, GsrAuxBlend{});
 }

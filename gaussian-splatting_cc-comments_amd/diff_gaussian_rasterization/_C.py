@@ -397,3 +397,185 @@ def profile_end(capacity=256, device=None):
     arr = (KernelTime * capacity)()
     n = lib().gsr_profile_end(stream, arr, capacity)
     return [(arr[k].name.decode(), float(arr[k].ms)) for k in range(n)]
+
+
+# ---- depth and alpha maps (include/gsr.h gsr_aux_args; opt-in, kernels of their own) ---------------------------------
+AUX_MODES = {"depth": 1, "invdepth": 2}   # GSR_AUX_DEPTH / GSR_AUX_INVDEPTH
+
+
+class AuxArgs(ctypes.Structure):
+    """include/gsr.h gsr_aux_args"""
+    _fields_ = [("mode", _i), ("out_depth", _vp), ("out_alpha", _vp), ("dL_ddepth", _vp), ("dL_dalpha", _vp), ("scratch", _vp)]
+
+
+class AuxLayout(ctypes.Structure):
+    _fields_ = [(n, _sz) for n in ("ckpt_depth", "final_D", "total")]
+
+
+def aux_mode(name):
+    """"depth" / "invdepth" -> the C ABI's mode; anything else raises ValueError."""
+    if not isinstance(name, str) or name not in AUX_MODES:
+        raise ValueError(f"depth_alpha must be one of {sorted(AUX_MODES)} or None, got {name!r}")
+    return AUX_MODES[name]
+
+
+def _aux_lib():
+    L = lib()
+    if not getattr(L, "_gsr_aux_bound", False):
+        pa = ctypes.POINTER(AuxArgs)
+        L.gsr_aux_bytes.restype = _sz
+        L.gsr_aux_bytes.argtypes = [_i64, _i, _i]
+        L.gsr_aux_layout_of.restype = _i
+        L.gsr_aux_layout_of.argtypes = [_i64, _i, _i, ctypes.POINTER(AuxLayout)]
+        L.gsr_forward_preprocess_aux.restype = _i
+        L.gsr_forward_preprocess_aux.argtypes = [pa] + list(L.gsr_forward_preprocess.argtypes)
+        L.gsr_forward_preprocess_leaf_aux.restype = _i
+        L.gsr_forward_preprocess_leaf_aux.argtypes = [pa] + [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp,
+                                                                                                   ctypes.POINTER(_i64), _vp, _i]
+        L.gsr_forward_render_aux.restype = _i
+        L.gsr_forward_render_aux.argtypes = [pa] + list(L.gsr_forward_render.argtypes)
+        L.gsr_backward_blend_aux.restype = _i
+        L.gsr_backward_blend_aux.argtypes = [ctypes.POINTER(BackwardArgs), pa]
+        L.gsr_backward_gaussians_aux.restype = _i
+        L.gsr_backward_gaussians_aux.argtypes = [ctypes.POINTER(BackwardArgs), pa, _i, _i, _i]
+        L._gsr_aux_bound = True
+    return L
+
+
+def aux_layout(R, W, H):
+    lay = AuxLayout()
+    _check(_aux_lib().gsr_aux_layout_of(int(R), int(W), int(H), ctypes.byref(lay)))
+    return {n: getattr(lay, n) for n, _ in AuxLayout._fields_}
+
+
+def aux_forward_args(mode, P, R, W, H, device):
+    """-> (AuxArgs, depth (1,H,W), alpha (1,H,W), scratch) for a forward with num_rendered R: the maps are fully written by the
+    render call (zeros when P == 0, where nothing is launched)."""
+    f32 = dict(dtype=torch.float32, device=device)
+    alloc = torch.zeros if P == 0 else torch.empty
+    depth, alpha = alloc((1, H, W), **f32), alloc((1, H, W), **f32)
+    scratch = torch.empty((_aux_lib().gsr_aux_bytes(int(R), W, H) if P else 0,), dtype=torch.uint8, device=device)
+    x = AuxArgs()
+    x.mode = aux_mode(mode) if isinstance(mode, str) else int(mode)
+    x.out_depth, x.out_alpha, x.scratch = _ptr(depth), _ptr(alpha), _ptr(scratch)
+    return x, depth, alpha, scratch
+
+
+def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
+    """AuxArgs of a backward: dL_ddepth / dL_dalpha (1,H,W) or None (= zero).  The tensors must stay alive until the calls
+    that use the struct have been enqueued; the contiguous copies are kept on the struct."""
+    x = AuxArgs()
+    x.mode = aux_mode(mode)
+    keep = []
+    for name, t in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
+        if t is not None:
+            t = _dev_f32(t, device, name)
+            keep.append(t)
+        setattr(x, name, _ptr(t))
+    x.scratch = _ptr(scratch)
+    x._keep = keep
+    return x
+
+
+def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                                    cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                                    degree, campos, prefiltered, debug):
+    """rasterize_gaussians() with the depth and alpha maps of mode `depth_alpha` ("depth" / "invdepth") from the same blend pass
+    -> (num_rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, depth (1,H,W), alpha (1,H,W), auxBuffer).
+    Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s."""
+    mode = aux_mode(depth_alpha)
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if not means3D.is_cuda:
+        raise RuntimeError("means3D must be a HIP (cuda) tensor; the HIP rasterizer has no CPU path")
+    L = _aux_lib()
+    dev = means3D.device
+    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    means3D = _dev_f32(means3D, dev, "means3D")
+    background = _dev_f32(background, dev, "bg")
+    colors, opacity, scales, rotations, cov3D_precomp, sh = (
+        _dev_f32(t, dev, n) for t, n in ((colors, "colors_precomp"), (opacity, "opacities"), (scales, "scales"),
+                                         (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"), (sh, "shs")))
+    viewmatrix, projmatrix, campos = (_dev_f32(t, dev, n) for t, n in ((viewmatrix, "viewmatrix"),
+                                                                        (projmatrix, "projmatrix"), (campos, "campos")))
+    byte = dict(dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        out_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev) if P == 0 else \
+            torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        if P == 0:
+            e = torch.empty((0,), **byte)
+            _, depth, alpha, scratch = aux_forward_args(mode, 0, 0, W, H, dev)
+            return 0, out_color, radii, e, e.clone(), e.clone(), depth, alpha, scratch
+        M = int(sh.size(1)) if sh.numel() != 0 else 0
+        geom = torch.empty((L.gsr_geometry_bytes(P),), **byte)
+        img = torch.empty((L.gsr_image_bytes(W, H),), **byte)
+        R = _i64(0)
+        stream = _stream(dev)
+        pre = AuxArgs()
+        pre.mode = mode
+        _check(L.gsr_forward_preprocess_aux(ctypes.byref(pre), P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
+                                            _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations),
+                                            _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                                            float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
+                                            ctypes.byref(R), stream, _dbg(debug)))
+        R = int(R.value)
+        binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
+        x, depth, alpha, scratch = aux_forward_args(mode, P, R, W, H, dev)
+        _check(L.gsr_forward_render_aux(ctypes.byref(x), P, R, W, H, _ptr(background), _ptr(radii), _ptr(geom), _ptr(binning),
+                                        _ptr(img), _ptr(out_color), stream, _dbg(debug)))
+    return R, out_color, radii, geom, binning, img, depth, alpha, scratch
+
+
+def backward_blend_aux(a, x):
+    _check(_aux_lib().gsr_backward_blend_aux(ctypes.byref(a), ctypes.byref(x)))
+
+
+def backward_gaussians_aux(a, x, first, count, out_row0=0):
+    _check(_aux_lib().gsr_backward_gaussians_aux(ctypes.byref(a), ctypes.byref(x), int(first), int(count), int(out_row0)))
+
+
+def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                             cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                             degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
+                                             dL_dalpha, debug, *, stats=None):
+    """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
+    top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
+    precomputed covariances, as rasterize_gaussians_backward(lean=True))."""
+    L = _aux_lib()
+    dev = means3D.device
+    P = int(means3D.size(0))
+    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    f32 = dict(dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        alloc = torch.zeros if P == 0 else torch.empty
+        none = torch.empty((0,), **f32)
+        dL_dmeans3D, dL_dmeans2D = alloc((P, 3), **f32), alloc((P, 3), **f32)
+        dL_dcolors = alloc((P, 3), **f32) if colors.numel() != 0 else none
+        dL_dopacity = alloc((P, 1), **f32)
+        dL_dcov3D = alloc((P, 6), **f32) if cov3D_precomp.numel() != 0 else none
+        dL_dsh = alloc((P, M, 3), **f32)
+        dL_dscales, dL_drotations = alloc((P, 3), **f32), alloc((P, 4), **f32)
+        if P != 0:
+            means3D = _dev_f32(means3D, dev, "means3D")
+            dL_dout_color = _dev_f32(dL_dout_color, dev, "dL_dout_color")
+            background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix, projmatrix, campos = (
+                _dev_f32(t, dev, "input") for t in (background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix,
+                                                    projmatrix, campos))
+            scratch = torch.empty((L.gsr_backward_scratch_bytes(P, int(R)),), dtype=torch.uint8, device=dev)
+            a = backward_args(P=P, D=int(degree), M=M, R=int(R), W=W, H=H, leaf=0, background=background, means3D=means3D,
+                              shs=sh, colors_precomp=colors, scales=scales, scale_modifier=scale_modifier,
+                              rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix,
+                              projmatrix=projmatrix, cam_pos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, radii=radii,
+                              geometry=geomBuffer, binning=binningBuffer, image=imageBuffer, scratch=scratch,
+                              dL_dpix=dL_dout_color, debug=debug, device=dev)
+            set_backward_outputs(a, dL_dmean2D=dL_dmeans2D, dL_dconic=None, dL_dopacity=dL_dopacity, dL_dcolor=dL_dcolors,
+                                 dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh, dL_dscale=dL_dscales,
+                                 dL_drot=dL_drotations)
+            set_backward_stats(a, stats, P, dev)
+            x = aux_backward_args(depth_alpha, auxBuffer, dL_ddepth, dL_dalpha, dev)
+            backward_blend_aux(a, x)
+            backward_gaussians_aux(a, x, 0, P, 0)
+            scratch.record_stream(torch.cuda.current_stream(dev))
+    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations

@@ -138,6 +138,77 @@ class _RasterizeGaussians(torch.autograd.Function):
         return grads
 
 
+def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                    raster_settings, depth_alpha, densify_stats=None):
+    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
+    _C.aux_mode(depth_alpha)
+    return _RasterizeGaussiansDepthAlpha.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                               cov3Ds_precomp, raster_settings, depth_alpha, densify_stats)
+
+
+class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
+    """_RasterizeGaussians plus two differentiable per-pixel outputs from the same blend pass (include/gsr.h gsr_aux_args):
+    depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term) and alpha
+    A = 1 - T_final.  Colour and radii are bit-identical with _RasterizeGaussians'.  When neither map's gradient reaches the
+    backward, the default backward kernels run."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
+                depth_alpha, densify_stats=None):
+        st = raster_settings
+        (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, depth, alpha, auxBuffer) = \
+            _C.rasterize_gaussians_depth_alpha(depth_alpha, st.bg, means3D, colors_precomp, opacities, scales, rotations,
+                                               st.scale_modifier, cov3Ds_precomp, st.viewmatrix, st.projmatrix, st.tanfovx,
+                                               st.tanfovy, st.image_height, st.image_width, sh, st.sh_degree, st.campos,
+                                               st.prefiltered, st.debug)
+        ctx.raster_settings = raster_settings
+        ctx.depth_alpha = depth_alpha
+        ctx.densify_stats = densify_stats
+        ctx.num_rendered = num_rendered
+        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
+                              binningBuffer, imgBuffer, auxBuffer)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
+        st = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
+         auxBuffer) = ctx.saved_tensors
+        if grad_out_color is None:
+            grad_out_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32,
+                                         device=means3D.device)
+        if grad_depth is None and grad_alpha is None:
+            # neither map takes part in the loss: the default backward kernels, at the default cost
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+             grad_rotations) = _C.rasterize_gaussians_backward(
+                st.bg, means3D, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp, st.viewmatrix,
+                st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
+                ctx.num_rendered, binningBuffer, imgBuffer, st.debug, lean=not st.debug, stats=ctx.densify_stats)
+        else:
+            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+             grad_rotations) = _C.rasterize_gaussians_backward_depth_alpha(
+                ctx.depth_alpha, st.bg, means3D, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp,
+                st.viewmatrix, st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
+                ctx.num_rendered, binningBuffer, imgBuffer, auxBuffer,
+                None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
+                None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), st.debug, stats=ctx.densify_stats)
+        return (
+            grad_means3D,
+            grad_means2D,
+            grad_sh if sh.numel() != 0 else None,
+            grad_colors_precomp if colors_precomp.numel() != 0 else None,
+            grad_opacities,
+            grad_scales if scales.numel() != 0 else None,
+            grad_rotations if rotations.numel() != 0 else None,
+            grad_cov3Ds_precomp if cov3Ds_precomp.numel() != 0 else None,
+            None,
+            None,
+            None,
+        )
+
+
 class GaussianRasterizationSettings(NamedTuple):
     """reference __init__.py:168-180"""
     image_height: int
@@ -159,12 +230,20 @@ class GaussianRasterizer(nn.Module):
 
     densify_stats (extension, optional): (xyz_gradient_accum, denom, max_radii2D) float32 [P] tensors that the
     backward's per-Gaussian kernel updates in place for the Gaussians visible in this view -- the bookkeeping of
-    train.py:157-159 / scene/gaussian_model.py:599-602 without separate passes (view_parallel.DensificationStats)."""
+    train.py:157-159 / scene/gaussian_model.py:599-602 without separate passes (view_parallel.DensificationStats).
 
-    def __init__(self, raster_settings, densify_stats=None):
+    depth_alpha (extension, optional): "depth" or "invdepth" -- forward() then returns (color, radii, depth, alpha) with the
+    depth map D = sum_i v_i alpha_i T_i (v_i = view-space z_i, or 1 / z_i; 0 where nothing blends) and the alpha map
+    A = 1 - T_final, both (1, H, W) and differentiable, accumulated in the same blend pass as the colour
+    (_RasterizeGaussiansDepthAlpha).  Expected depth is D / A."""
+
+    def __init__(self, raster_settings, densify_stats=None, depth_alpha=None):
         super().__init__()
+        if depth_alpha is not None:
+            _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
+        self.depth_alpha = depth_alpha
 
     def markVisible(self, positions):
         # Mark visible points (based on frustum culling for camera) with a boolean
@@ -195,5 +274,8 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = torch.Tensor([])
 
+        if self.depth_alpha is not None:
+            return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                   cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats)

@@ -150,11 +150,115 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None
 
 
-def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None):
+def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings):
+    """leaf_forward() with the depth and alpha maps (include/gsr.h gsr_aux_args) -> (num_rendered, color, radii, geom, binning,
+    img, M, contiguous inputs, depth (1,H,W), alpha (1,H,W), aux scratch)."""
+    mode = _C.aux_mode(depth_alpha)
+    if xyz.ndimension() != 2 or xyz.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    L = _C._aux_lib()
+    _lib()
+    dev = xyz.device
+    st = raster_settings
+    P, H, W = int(xyz.size(0)), int(st.image_height), int(st.image_width)
+    xyz, features_dc, opacity, scaling, rotation = (_f32(t, dev, n) for t, n in (
+        (xyz, "xyz"), (features_dc, "features_dc"), (opacity, "opacity"), (scaling, "scaling"), (rotation, "rotation")))
+    M = 1 + (int(features_rest.size(1)) if features_rest.numel() else 0)
+    if features_dc.shape != (P, 1, 3) or (M > 1 and features_rest.shape != (P, M - 1, 3)):
+        raise RuntimeError(f"features_dc must be (P,1,3) and features_rest (P,M-1,3); got {tuple(features_dc.shape)}, "
+                           f"{tuple(features_rest.shape)}")
+    features_rest = _f32(features_rest, dev, "features_rest") if M > 1 else features_rest
+    bg, view, proj, campos = (_f32(t, dev, n) for t, n in ((st.bg, "bg"), (st.viewmatrix, "viewmatrix"),
+                                                           (st.projmatrix, "projmatrix"), (st.campos, "campos")))
+    byte = dict(dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        color = (torch.zeros if P == 0 else torch.empty)((3, H, W), dtype=torch.float32, device=dev)
+        radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        geom = torch.empty((L.gsr_geometry_bytes(P) if P else 0,), **byte)
+        img = torch.empty((L.gsr_image_bytes(W, H) if P else 0,), **byte)
+        binning = torch.empty((0,), **byte)
+        R = 0
+        x, depth, alpha, aux = _C.aux_forward_args(mode, 0, 0, W, H, dev)
+        if P:
+            Rv = _i64(0)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            pre = _C.AuxArgs()
+            pre.mode = mode
+            _C._check(L.gsr_forward_preprocess_leaf_aux(
+                ctypes.byref(pre), P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
+                opacity.data_ptr(), scaling.data_ptr(), float(st.scale_modifier), rotation.data_ptr(), view.data_ptr(),
+                proj.data_ptr(), campos.data_ptr(), float(st.tanfovx), float(st.tanfovy), int(bool(st.prefiltered)),
+                radii.data_ptr(), geom.data_ptr(), ctypes.byref(Rv), stream, _C._dbg(st.debug)))
+            R = int(Rv.value)
+            binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
+            x, depth, alpha, aux = _C.aux_forward_args(mode, P, R, W, H, dev)
+            _C._check(L.gsr_forward_render_aux(ctypes.byref(x), P, R, W, H, bg.data_ptr(), radii.data_ptr(), geom.data_ptr(),
+                                               _C._ptr(binning), img.data_ptr(), color.data_ptr(), stream, _C._dbg(st.debug)))
+    return R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), depth, alpha, aux
+
+
+class _RasterizeLeafGaussiansDepthAlpha(torch.autograd.Function):
+    """_RasterizeLeafGaussians plus the depth and alpha maps of diff_gaussian_rasterization._RasterizeGaussiansDepthAlpha:
+    -> (color, radii, depth (1,H,W), alpha (1,H,W)).  Without gradients for either map the default backward kernels run."""
+
+    @staticmethod
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, depth_alpha, stats=None):
+        R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), depth, alpha, aux = \
+            leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings)
+        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
+        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux)
+        ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def backward(ctx, grad_color, _, grad_depth, grad_alpha):
+        L = _lib()
+        st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
+        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux = ctx.saved_tensors
+        dev = xyz.device
+        if grad_color is None:
+            grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
+        use_aux = grad_depth is not None or grad_alpha is not None
+        P = int(xyz.size(0))
+        f32 = dict(dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            alloc = torch.zeros if P == 0 else torch.empty
+            d_means2D, d_xyz = alloc((P, 3), **f32), alloc((P, 3), **f32)
+            d_dc, d_rest = alloc((P, 1, 3), **f32), alloc((P, M - 1, 3), **f32)
+            d_opacity, d_scaling, d_rotation = alloc((P, 1), **f32), alloc((P, 3), **f32), alloc((P, 4), **f32)
+            if P:
+                grad_color = _f32(grad_color, dev, "dL_dout_color")
+                scratch = torch.empty((L.gsr_backward_scratch_bytes(P, R),), dtype=torch.uint8, device=dev)
+                a = leaf_backward_args(st, R, M, xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
+                                       scratch, grad_color)
+                _C.set_backward_outputs(a, dL_dmean2D=d_means2D, dL_dmean3D=d_xyz, dL_dsh=d_dc, dL_dsh_rest=d_rest,
+                                        dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
+                _C.set_backward_stats(a, ctx.stats, P, dev)
+                if use_aux:
+                    x = _C.aux_backward_args(ctx.depth_alpha, aux,
+                                             None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
+                                             None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), dev)
+                    _C.backward_blend_aux(a, x)
+                    _C.backward_gaussians_aux(a, x, 0, P, 0)
+                else:
+                    _C.backward_blend(a)
+                    _C.backward_gaussians(a, 0, P, 0)
+                scratch.record_stream(torch.cuda.current_stream(dev))
+        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None
+
+
+def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
+                             depth_alpha=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
-    -> (color (3,H,W), radii (P,) int32)."""
+    -> (color (3,H,W), radii (P,) int32); with depth_alpha = "depth" / "invdepth" -> (color, radii, depth, alpha), the maps of
+    GaussianRasterizer(raster_settings, depth_alpha=...)."""
+    if depth_alpha is not None:
+        _C.aux_mode(depth_alpha)
+        return _RasterizeLeafGaussiansDepthAlpha.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
+                                                       raster_settings, depth_alpha, stats)
     return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats)
 
 

@@ -45,13 +45,18 @@ def _python_sh_colors(camera, pc):
     return torch.clamp_min(eval_sh(pc.active_sh_degree, per_channel, view_dir) + 0.5, 0.0)
 
 
-def _result(image, screenspace_points, radii):
-    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+def _result(image, screenspace_points, radii, aux=None):
+    out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+    if aux is not None:
+        out["depth"], out["alpha"] = aux
+    return out
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None):
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
+           depth_alpha=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
-    densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward."""
+    densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
+    depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer."""
     xyz = pc.get_xyz
     # carrier of the screen-space gradient: zeros, a non-leaf that keeps its grad
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
@@ -65,9 +70,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     python_sh = bool(pipe.convert_SHs_python)
     if getattr(pipe, "fused_activations", False) and override_color is None and not python_cov and not python_sh:
         from fused_params import rasterize_leaf_gaussians
-        image, radii = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
-                                                pc._scaling, pc._rotation, settings, densify_stats)
-        return _result(image, screenspace_points, radii)
+        out = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
+                                       pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha)
+        return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)
 
     inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
                   shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None)
@@ -82,5 +87,5 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         inputs["shs"] = pc.get_features
 
-    image, radii = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats)(**inputs)
-    return _result(image, screenspace_points, radii)
+    out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha)(**inputs)
+    return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)
