@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "gsr_internal.h"
+#include "../../include/gsr_aa.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -454,7 +455,7 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
                                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
                                        const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
                                        int prefiltered, int* radii, void* geometry, int64_t* num_rendered_host,
-                                       void* stream, int debug, int aux = 0)
+                                       void* stream, int debug, int aux = 0, int aa = 0)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
@@ -563,7 +564,7 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 	}
 	{
 		GsrProfScope p(s, "preprocess");
-		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux);
+		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux, aa);
 	}
 	if ((rc = gsr_stage_done(s, debug, "preprocess"))) return rc;
 	if (color && !beside) {
@@ -698,6 +699,47 @@ extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, i
 	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
 	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
 	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux->mode);
+}
+
+// the anti-aliased path (include/gsr_aa.h): aux NULL or a known mode; antialiasing 0 or 1
+static int gsr_aa_check(int antialiasing, const gsr_aux_args* aux, const char* who)
+{
+	if (antialiasing != 0 && antialiasing != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: antialiasing must be 0 or 1, got %d", who, antialiasing);
+	if (aux && !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the mode of aux is unknown", who);
+	return GSR_OK;
+}
+
+extern "C" int gsr_forward_preprocess_aa(int antialiasing, const gsr_aux_args* aux, int P, int D, int M, int width, int height,
+                                         const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
+                                         const float* scales, float scale_modifier, const float* rotations,
+                                         const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                         int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
+{
+	g_err[0] = 0;
+	int rc;
+	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_forward_preprocess_aa"))) return rc;
+	return gsr_forward_preprocess_impl(P, D, M, width, height, means3D, shs, nullptr, 0, colors_precomp, opacities, scales,
+	                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
+	                                   tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0,
+	                                   antialiasing);
+}
+
+extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_args* aux, int P, int D, int M, int width, int height,
+                                              const float* xyz, const float* features_dc, const float* features_rest,
+                                              const float* opacity_logits, const float* log_scales, float scale_modifier,
+                                              const float* raw_rotations, const float* viewmatrix, const float* projmatrix,
+                                              const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
+                                              int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
+                                              int debug)
+{
+	g_err[0] = 0;
+	int rc;
+	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_forward_preprocess_leaf_aa"))) return rc;
+	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
+	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
+	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug,
+	                                   aux ? aux->mode : 0, antialiasing);
 }
 
 // ---- forward, stage 2 --------------------------------------------------------------------------
@@ -899,7 +941,9 @@ extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_a
 	return gsr_backward_blend_impl(args, aux);
 }
 
-static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux)
+// aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h); NULL: the default ones
+static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux,
+                                       const float* aa_opacities = nullptr)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
@@ -928,7 +972,14 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, s, aux);
+		if (aa_opacities) {
+			GsrGaussianBackwardArgsAA x;
+			static_cast<GsrGaussianBackwardArgs&>(x) = a;
+			x.opacities = aa_opacities;
+			gsr_launch_gaussian_backward_aa(x, s, aux);
+		} else {
+			gsr_launch_gaussian_backward(a, s, aux);
+		}
 	}
 	return gsr_stage_done(s, b.debug, "gaussian_backward");
 }
@@ -944,6 +995,18 @@ extern "C" int gsr_backward_gaussians_aux(const gsr_backward_args* args, const g
 	int rc;
 	if ((rc = gsr_aux_check(aux, "gsr_backward_gaussians_aux"))) return rc;
 	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux->mode);
+}
+
+extern "C" int gsr_backward_gaussians_aa(const gsr_backward_args* args, int antialiasing, const float* opacities, const gsr_aux_args* aux,
+                                         int first, int count, int out_row0)
+{
+	g_err[0] = 0;
+	int rc;
+	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_backward_gaussians_aa"))) return rc;
+	if (aux && (rc = gsr_aux_check(aux, "gsr_backward_gaussians_aa"))) return rc;
+	if (antialiasing && args && args->P > 0 && count > 0 && !opacities)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians_aa: the opacity input is NULL");
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr);
 }
 
 static int gsr_backward_whole(const gsr_backward_args& a)

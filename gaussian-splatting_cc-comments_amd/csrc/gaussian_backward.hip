@@ -6,6 +6,8 @@
 // (backward.cu:20-139) and covariance (backward.cu:281-345) parts, and the zero fill of
 // rasterize_points.cu:168-178: every output element is written exactly once.
 #include "gsr_internal.h"
+#include "gsr_aa.h"
+#include <type_traits>
 
 __device__ __forceinline__ GsrVec3 gsr_dnormvdv(GsrVec3 v, GsrVec3 dv)  // auxiliary.h:109-120
 {
@@ -182,9 +184,13 @@ __device__ __forceinline__ void gsr_add_slot(const GsrGradSlot* __restrict__ slo
 // workgroup = one wave: waves of a CU then start and retire independently (phases of different waves mix)
 // AUX: 0, or the depth-and-alpha mode (include/gsr.h GSR_AUX_*): the slots' tenth word dL/dv is summed too and chained into dL/dmean3D
 // through v = z (GSR_AUX_DEPTH) or 1 / z (GSR_AUX_INVDEPTH), z the view-space depth: dL/dmean3D += dL/dz (V[2], V[6], V[10]).
+// AA: the anti-aliased path (include/gsr_aa.h): the record holds opacity * rho, so the opacity input comes from a.opacities
+// (GsrGaussianBackwardArgsAA); dL/dopacity = dL/dopacity_record * rho, and dL/drho = dL/dopacity_record * opacity joins dL/da, db, dc
+// (the undilated 2D covariance, gsr_aa.h) before they reach dL/dcov3D and the dL/dT chain.
 #define GSR_GB_THREADS 64
-template <bool LEAF, int AUX>
-__global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(GsrGaussianBackwardArgs a, int sh_via_lds, int skip_dsh)
+template <bool LEAF, int AUX, bool AA>
+__global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
+	typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type a, int sh_via_lds, int skip_dsh)
 {
 	// staging of the dL/dsh output block: rows of 13 float4; the packed layout goes out in two halves of 32 rows
 	// (6.6 KB per wave), the split leaf tensors as one linear 12 KB block
@@ -224,7 +230,8 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 #pragma unroll
 			for (int k = 0; k < 9; k++) ddir9[k] = a.g.sh_ddir[(size_t)k * a.P + idx];  // nine planes; garbage for culled Gaussians: unused
 		}
-		if (LEAF) leaf_opacity = a.g.splat[idx].opacity;
+		if constexpr (AA) leaf_opacity = a.opacities[idx];   // the input (a logit in leaf mode), activated below
+		else if (LEAF) leaf_opacity = a.g.splat[idx].opacity;
 	}
 	const int wave_first = a.first + blockIdx.x * GSR_GB_THREADS + wave * 64;
 	const int nrows = min(64, end - wave_first);  // Gaussians of this wave (<= 0: none)
@@ -346,11 +353,24 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 		const float ca = c2.a, cb = c2.b, cc = c2.c;
 		const float denom = ca * cc - cb * cb;
 		float dL_da = 0, dL_db = 0, dL_dc = 0;
+		GsrAAGrad aa = {};
+		float dL_drho = 0.f;
+		if constexpr (AA) {
+			if (LEAF) leaf_opacity = gsr_act_sigmoid(leaf_opacity);   // the forward's activation, same bits
+			aa = gsr_aa_rho_grad(c2.a0, cb, c2.c0);
+			dL_drho = dop * leaf_opacity;
+			dop = dop * aa.rho;
+		}
 		const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
 		if (denom2inv != 0) {
 			dL_da = denom2inv * (-cc * cc * dcx + 2 * cb * cc * dcy + (denom - ca * cc) * dcz);
 			dL_dc = denom2inv * (-ca * ca * dcz + 2 * ca * cb * dcy + (denom - ca * cc) * dcx);
 			dL_db = denom2inv * 2 * (cb * cc * dcx - (denom + 2 * cb * cb) * dcy + ca * cb * dcz);
+			if constexpr (AA) {
+				dL_da = dL_da + dL_drho * aa.drho_da;
+				dL_db = dL_db + dL_drho * aa.drho_db;
+				dL_dc = dL_dc + dL_drho * aa.drho_dc;
+			}
 			dcov[0] = (T.m[0][0] * T.m[0][0] * dL_da + T.m[0][0] * T.m[1][0] * dL_db + T.m[1][0] * T.m[1][0] * dL_dc);
 			dcov[3] = (T.m[0][1] * T.m[0][1] * dL_da + T.m[0][1] * T.m[1][1] * dL_db + T.m[1][1] * T.m[1][1] * dL_dc);
 			dcov[5] = (T.m[0][2] * T.m[0][2] * dL_da + T.m[0][2] * T.m[1][2] * dL_db + T.m[1][2] * T.m[1][2] * dL_dc);
@@ -517,11 +537,19 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(G
 	}
 }
 
-template <int AUX>
-static void gsr_launch_gaussian_backward_t(const GsrGaussianBackwardArgs& a, hipStream_t s, int sh_via_lds, int skip_dsh)
+template <int AUX, bool AA, typename Args>
+static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int sh_via_lds, int skip_dsh)
 {
-	if (a.leaf) hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, AUX>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
-	else hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, AUX>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+	if (a.leaf) hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, AUX, AA>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+	else hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, AUX, AA>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+}
+
+// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
+static void gsr_gaussian_backward_modes(const GsrGaussianBackwardArgs& a, int& sh_via_lds, int& skip_dsh)
+{
+	skip_dsh = (a.shs && !a.dL_dsh) ? 1 : 0;  // view-parallel mode (include/gsr.h)
+	sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
+	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
 }
 
 void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux)
@@ -531,16 +559,25 @@ void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t 
 	int sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
 	if (aux) {
 		if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH>(a, s, sh_via_lds, skip_dsh);
-		else gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH>(a, s, sh_via_lds, skip_dsh);
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH, false>(a, s, sh_via_lds, skip_dsh);
+		else gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH, false>(a, s, sh_via_lds, skip_dsh);
 		return;
 	}
 	if (a.leaf) {
 		if (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0)) sh_via_lds = 0;
-		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, 0>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, 0, false>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
 	} else {
-		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, 0>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
+		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, 0, false>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
 	}
+}
+
+void gsr_launch_gaussian_backward_aa(const GsrGaussianBackwardArgsAA& a, hipStream_t s, int aux)
+{
+	int sh_via_lds = 0, skip_dsh = 0;
+	gsr_gaussian_backward_modes(a, sh_via_lds, skip_dsh);
+	if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH, true>(a, s, sh_via_lds, skip_dsh);
+	else if (aux) gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH, true>(a, s, sh_via_lds, skip_dsh);
+	else gsr_launch_gaussian_backward_t<0, true>(a, s, sh_via_lds, skip_dsh);
 }
 
 // ---- view-parallel SH gradient (no reference counterpart) ------------------------------

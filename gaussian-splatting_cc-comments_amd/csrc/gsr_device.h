@@ -404,6 +404,7 @@ struct GsrCov2D {
 	GsrVec3 t;
 	float txtz, tytz, limx, limy;
 	float a, b, c;
+	float a0, c0;   // a and c before the 0.3 dilation (the anti-aliased path, gsr_aa.h; dead code elsewhere)
 };
 
 __device__ __forceinline__ void gsr_cov2d(const GsrVec3& mean, float focal_x, float focal_y, float tan_fovx,
@@ -429,6 +430,8 @@ __device__ __forceinline__ void gsr_cov2d(const GsrVec3& mean, float focal_x, fl
 	o.Vrk.m[1][0] = cov3D[1]; o.Vrk.m[1][1] = cov3D[3]; o.Vrk.m[1][2] = cov3D[4];
 	o.Vrk.m[2][0] = cov3D[2]; o.Vrk.m[2][1] = cov3D[4]; o.Vrk.m[2][2] = cov3D[5];
 	GsrMat3 cov = gsr_mat3_mul(gsr_mat3_mul(gsr_mat3_transpose(o.T), gsr_mat3_transpose(o.Vrk)), o.T);
+	o.a0 = cov.m[0][0];
+	o.c0 = cov.m[1][1];
 	o.a = cov.m[0][0] + 0.3f;
 	o.b = cov.m[0][1];
 	o.c = cov.m[1][1] + 0.3f;

@@ -136,7 +136,8 @@ struct GsrPreprocessArgs {
 
 // preprocess.hip
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the kernels then also store the depth value v in the splat record's last word
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done = nullptr, int aux = 0);
+// aa: the anti-aliased path (include/gsr_aa.h): the record's opacity is opacity * rho (gsr_aa.h); the colour kernel has no such variant
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done = nullptr, int aux = 0, int aa = 0);
 void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done = nullptr);
 bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a);
 void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu = 0, int aux = 0);
@@ -236,8 +237,15 @@ struct GsrGaussianBackwardArgs {
 	float* stat_denom;               // [P] += 1 for visible Gaussians
 	float* stat_max_radii2D;         // [P] = max(itself, radius) for visible Gaussians
 };
+// the anti-aliased path (include/gsr_aa.h): the opacity INPUT (activated; the logit in leaf mode), which the record no longer holds --
+// it holds opacity * rho.  A struct of its own so that the default kernels' arguments keep their layout.
+struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
+	const float* opacities;
+};
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the slots' tenth word (dL/dv) is summed and chained into dL/dmean3D
 void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux = 0);
+// the anti-aliased kernels (same aux modes): dL/dopacity = dL/dopacity_record * rho, and dL/drho into dL/dcov3D and dL/dmean3D
+void gsr_launch_gaussian_backward_aa(const GsrGaussianBackwardArgsAA& a, hipStream_t s, int aux = 0);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,
                                    int64_t view_stride, float* dL_dsh, hipStream_t s);
 

@@ -8,6 +8,7 @@
 #include "gsr_internal.h"
 #include <hip/hip_ext.h>
 #include "gsr_rect_trim.h"
+#include "gsr_aa.h"
 
 // forward.cu:21-81 computeColorFromSH, one channel at a time in the glm::vec3 expression order
 __device__ __forceinline__ float gsr_sh_channel(int deg, const float* sh, int ch, float x, float y, float z)
@@ -45,7 +46,8 @@ __device__ __forceinline__ float gsr_sh_channel(int deg, const float* sh, int ch
 // LEAF: the inputs are the optimiser's raw leaves (gsr_internal.h); activations happen here.
 // AUX: 0, or the depth-and-alpha mode (include/gsr.h GSR_AUX_*): the colors_precomp path then stores the depth value v in the
 // record's last word (the colour kernel does it on the SH path).
-template <bool LEAF, int AUX>
+// AA: the anti-aliased path (include/gsr_aa.h): the record and the trim get opacity * rho of the undilated 2D covariance (gsr_aa.h)
+template <bool LEAF, int AUX, bool AA>
 __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(GsrPreprocessArgs a, uint32_t* __restrict__ clear, size_t clear_words,
                                                                               uint32_t* __restrict__ clear2, size_t clear2_words)
 {
@@ -123,7 +125,8 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 			// the geometry part of the record (GsrSplat: x, y, conic a, b | conic c, opacity, rect | colour): two 16-byte stores, 32 contiguous bytes
 			float4* rec = reinterpret_cast<float4*>(a.g.splat + idx);
 			rec[0] = make_float4(pix, piy, conic_a, conic_b);
-			const float opacity = LEAF ? gsr_act_sigmoid(opac) : opac;
+			float opacity = LEAF ? gsr_act_sigmoid(opac) : opac;
+			if (AA) opacity = opacity * gsr_aa_rho(c2.a0, c2.b, c2.c0);   // its Dh is `det` above, the same operations
 			rec[1] = make_float4(conic_c, opacity, __uint_as_float(rect.x), __uint_as_float(rect.y));
 			rshape.x = gsr_rect_pack((uint32_t)minx, (uint32_t)miny, (uint32_t)(maxx - minx), (uint32_t)(maxy - miny));
 			if (a.trim) rshape.y = gsr_rect_trim(pix, piy, conic_a, conic_b, conic_c, opacity, minx, miny, maxx - minx, maxy - miny);
@@ -301,34 +304,40 @@ void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done)
 
 // done: optional event signalled by the kernel's own dispatch packet when it has finished (hipExtLaunchKernelGGL): a separate
 // hipEventRecord behind the kernel is a barrier packet of its own and costs the stream's next launch ~8 us
-// the depth-and-alpha variants: one instantiation per (LEAF, mode)
-template <int AUX>
+// the depth-and-alpha and anti-aliased variants: one instantiation per (LEAF, mode, AA)
+template <int AUX, bool AA>
 static void gsr_launch_preprocess_aux(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int nb, uint32_t* clear, size_t clear_words,
                                       uint32_t* clear2, size_t clear2_words)
 {
-	if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-	else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+	if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, AUX, AA>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+	else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, AUX, AA>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
 }
 
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux)
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
 	uint32_t* clear = (uint32_t*)a.g.sort_table;
 	const size_t clear_words = gsr_radix_clear_words((size_t)a.P);
 	uint32_t* clear2 = (uint32_t*)a.g.col_table;
 	const size_t clear2_words = gsr_tilebin_col_clear_words((size_t)a.P);
+	if (aa) {
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		else if (aux) gsr_launch_preprocess_aux<GSR_AUX_DEPTH, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		else gsr_launch_preprocess_aux<0, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		return;
+	}
 	if (aux) {
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		else gsr_launch_preprocess_aux<GSR_AUX_DEPTH>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH, false>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
+		else gsr_launch_preprocess_aux<GSR_AUX_DEPTH, false>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
 		return;
 	}
 	if (done) {
-		if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-		else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+		if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
+		else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
 		return;
 	}
-	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
-	else hipLaunchKernelGGL((gsr_preprocess_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
+	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_kernel<true, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
+	else hipLaunchKernelGGL((gsr_preprocess_kernel<false, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
 }
 
 // the colour kernel exists only for SH colours

@@ -160,8 +160,10 @@ def _stream(device):
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug):
-    """-> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer)"""
+                        prefiltered, debug, *, antialiasing=False):
+    """-> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer)
+    antialiasing: the screen-space filter (include/gsr_aa.h): the splat records carry opacity * rho"""
+    aa = aa_flag(antialiasing)
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:60-63
     if not means3D.is_cuda:
@@ -189,11 +191,12 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         img = torch.empty((L.gsr_image_bytes(W, H),), **byte)
         R = _i64(0)
         stream = _stream(dev)
-        _check(L.gsr_forward_preprocess(P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity),
-                                        _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                                        _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx),
-                                        float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
-                                        ctypes.byref(R), stream, _dbg(debug)))
+        pre = (L.gsr_forward_preprocess,) if not aa else (_aa_lib().gsr_forward_preprocess_aa, 1, None)
+        _check(pre[0](*pre[1:], P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity),
+                      _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                      _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx),
+                      float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
+                      ctypes.byref(R), stream, _dbg(debug)))
         R = int(R.value)
         binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
         _check(L.gsr_forward_render(P, R, W, H, _ptr(background), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
@@ -204,7 +207,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
-                                 debug_out=None, stats=None):
+                                 debug_out=None, stats=None, antialiasing=False, opacities=None):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -215,7 +218,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 of the view, the input of sh_grad_from_views()
       debug_out dict that receives the internal "dL_dconic" tensor (tests)
       stats     (xyz_gradient_accum, denom, max_radii2D) float32 [P] tensors updated in place for the Gaussians
-                visible in this view (train.py:157-159, gaussian_model.py:599-602); any of them may be None"""
+                visible in this view (train.py:157-159, gaussian_model.py:599-602); any of them may be None
+      antialiasing  the backward of an antialiasing=True forward; `opacities` is then its opacity input (include/gsr_aa.h)"""
+    aa = aa_flag(antialiasing)
+    if aa and opacities is None:
+        raise RuntimeError("rasterize_gaussians_backward: antialiasing=True needs the forward's opacities")
     L = lib()
     dev = means3D.device
     P = int(means3D.size(0))
@@ -244,7 +251,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _dev_f32(t, dev, "input") for t in (background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix,
                                                     projmatrix, campos))
             scratch = torch.empty((L.gsr_backward_scratch_bytes(P, int(R)),), dtype=torch.uint8, device=dev)
-            if stats is None:
+            if stats is None and not aa:
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
                                       _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                       _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -264,7 +271,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
                 backward_blend(a)
-                backward_gaussians(a, 0, P, 0)
+                if aa:
+                    opacities = _dev_f32(opacities, dev, "opacities")
+                    backward_gaussians_aa(a, opacities, None, 0, P, 0)
+                else:
+                    backward_gaussians(a, 0, P, 0)
             scratch.record_stream(torch.cuda.current_stream(dev))
     if debug_out is not None:
         debug_out["dL_dconic"] = dL_dconic
@@ -479,11 +490,12 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
 
 def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                     cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                                    degree, campos, prefiltered, debug):
+                                    degree, campos, prefiltered, debug, *, antialiasing=False):
     """rasterize_gaussians() with the depth and alpha maps of mode `depth_alpha` ("depth" / "invdepth") from the same blend pass
     -> (num_rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, depth (1,H,W), alpha (1,H,W), auxBuffer).
-    Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s."""
+    Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s (with the same `antialiasing`)."""
     mode = aux_mode(depth_alpha)
+    aa = aa_flag(antialiasing)
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     if not means3D.is_cuda:
@@ -514,11 +526,12 @@ def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, op
         stream = _stream(dev)
         pre = AuxArgs()
         pre.mode = mode
-        _check(L.gsr_forward_preprocess_aux(ctypes.byref(pre), P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                                            _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations),
-                                            _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                                            float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
-                                            ctypes.byref(R), stream, _dbg(debug)))
+        fn = (L.gsr_forward_preprocess_aux,) if not aa else (_aa_lib().gsr_forward_preprocess_aa, 1)
+        _check(fn[0](*fn[1:], ctypes.byref(pre), P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
+                     _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations),
+                     _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                     float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
+                     ctypes.byref(R), stream, _dbg(debug)))
         R = int(R.value)
         binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
         x, depth, alpha, scratch = aux_forward_args(mode, P, R, W, H, dev)
@@ -538,10 +551,13 @@ def backward_gaussians_aux(a, x, first, count, out_row0=0):
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
-                                             dL_dalpha, debug, *, stats=None):
+                                             dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
-    precomputed covariances, as rasterize_gaussians_backward(lean=True))."""
+    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities: as there."""
+    aa = aa_flag(antialiasing)
+    if aa and opacities is None:
+        raise RuntimeError("rasterize_gaussians_backward_depth_alpha: antialiasing=True needs the forward's opacities")
     L = _aux_lib()
     dev = means3D.device
     P = int(means3D.size(0))
@@ -576,6 +592,40 @@ def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, r
             set_backward_stats(a, stats, P, dev)
             x = aux_backward_args(depth_alpha, auxBuffer, dL_ddepth, dL_dalpha, dev)
             backward_blend_aux(a, x)
-            backward_gaussians_aux(a, x, 0, P, 0)
+            if aa:
+                opacities = _dev_f32(opacities, dev, "opacities")
+                backward_gaussians_aa(a, opacities, x, 0, P, 0)
+            else:
+                backward_gaussians_aux(a, x, 0, P, 0)
             scratch.record_stream(torch.cuda.current_stream(dev))
     return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+
+
+# ---- anti-aliased rendering (include/gsr_aa.h; opt-in, kernels of their own) ------------------------------------------------
+def aa_flag(antialiasing):
+    """The `antialiasing` keyword -> bool; anything but a bool raises TypeError (a mode string or a number is not a switch here)."""
+    if not isinstance(antialiasing, bool):
+        raise TypeError(f"antialiasing must be True or False, got {antialiasing!r}")
+    return antialiasing
+
+
+def _aa_lib():
+    L = _aux_lib()
+    if not getattr(L, "_gsr_aa_bound", False):
+        pa = ctypes.POINTER(AuxArgs)
+        L.gsr_forward_preprocess_aa.restype = _i
+        L.gsr_forward_preprocess_aa.argtypes = [_i, pa] + list(L.gsr_forward_preprocess.argtypes)
+        L.gsr_forward_preprocess_leaf_aa.restype = _i
+        L.gsr_forward_preprocess_leaf_aa.argtypes = [_i] + list(L.gsr_forward_preprocess_leaf_aux.argtypes)
+        L.gsr_backward_gaussians_aa.restype = _i
+        L.gsr_backward_gaussians_aa.argtypes = [ctypes.POINTER(BackwardArgs), _i, _vp, pa, _i, _i, _i]
+        L._gsr_aa_bound = True
+    return L
+
+
+def backward_gaussians_aa(a, opacities, x, first, count, out_row0=0):
+    """gsr_backward_gaussians_aa with the filter on: `opacities` is the forward's opacity input (tensor or address; the logits in leaf
+    mode), `x` the AuxArgs of a depth-and-alpha backward or None."""
+    addr = opacities if isinstance(opacities, int) else _ptr(opacities)
+    _check(_aa_lib().gsr_backward_gaussians_aa(ctypes.byref(a), 1, addr, None if x is None else ctypes.byref(x), int(first), int(count),
+                                               int(out_row0)))

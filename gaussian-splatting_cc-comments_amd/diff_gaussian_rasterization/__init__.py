@@ -21,8 +21,12 @@ def cpu_deep_copy_tuple(input_tuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None):
-    """reference __init__.py:22-45 (+ the optional densification-statistics tensors, see GaussianRasterizer)"""
+                        raster_settings, densify_stats=None, antialiasing=False):
+    """reference __init__.py:22-45 (+ the optional densification-statistics tensors and the screen-space filter, see
+    GaussianRasterizer)"""
+    if _C.aa_flag(antialiasing):
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, densify_stats, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, densify_stats)
 
@@ -30,7 +34,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, densify_stats=None):
+                raster_settings, densify_stats=None, antialiasing=False):
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
         args = (
             raster_settings.bg,
@@ -53,22 +57,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             raster_settings.prefiltered,
             raster_settings.debug,
         )
+        # the screen-space filter (include/gsr_aa.h): a keyword of the binding, so the debug snapshot holds the same tuple
+        kw = {"antialiasing": True} if antialiasing else {}
         if raster_settings.debug:  # reference __init__.py:87-94
             cpu_args = cpu_deep_copy_tuple(args)
             try:
-                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args, **kw)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
-            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args)
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args, **kw)
 
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
         ctx.num_rendered = num_rendered
+        ctx.antialiasing = bool(antialiasing)
+        # the anti-aliased backward reads the opacity input (the records hold opacity * rho): saved on that path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
+                              binningBuffer, imgBuffer, *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
         ctx.set_materialize_grads(False)
@@ -82,7 +90,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
                                          dtype=torch.float32, device=ctx.saved_tensors[1].device)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
+         imgBuffer) = ctx.saved_tensors[:10]
+        kw = {"antialiasing": True, "opacities": ctx.saved_tensors[10]} if ctx.antialiasing else {}
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
@@ -112,7 +121,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             cpu_args = cpu_deep_copy_tuple(args)
             try:
                 (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-                 grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats)
+                 grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_bw.dump")
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
@@ -120,7 +129,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             # gradients of inputs that were not provided have no consumer below: the binding skips them
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, lean=True, stats=ctx.densify_stats)
+             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, lean=True, stats=ctx.densify_stats, **kw)
 
         # gradient order: reference __init__.py:154-164
         grads = (
@@ -135,38 +144,40 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
         )
-        return grads
+        return grads + ((None,) if ctx.antialiasing else ())
 
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                    raster_settings, depth_alpha, densify_stats=None):
+                                    raster_settings, depth_alpha, densify_stats=None, antialiasing=False):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
     _C.aux_mode(depth_alpha)
     return _RasterizeGaussiansDepthAlpha.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                               cov3Ds_precomp, raster_settings, depth_alpha, densify_stats)
+                                               cov3Ds_precomp, raster_settings, depth_alpha, densify_stats,
+                                               _C.aa_flag(antialiasing))
 
 
 class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
     """_RasterizeGaussians plus two differentiable per-pixel outputs from the same blend pass (include/gsr.h gsr_aux_args):
     depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term) and alpha
     A = 1 - T_final.  Colour and radii are bit-identical with _RasterizeGaussians'.  When neither map's gradient reaches the
-    backward, the default backward kernels run."""
+    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                depth_alpha, densify_stats=None):
+                depth_alpha, densify_stats=None, antialiasing=False):
         st = raster_settings
         (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, depth, alpha, auxBuffer) = \
             _C.rasterize_gaussians_depth_alpha(depth_alpha, st.bg, means3D, colors_precomp, opacities, scales, rotations,
                                                st.scale_modifier, cov3Ds_precomp, st.viewmatrix, st.projmatrix, st.tanfovx,
                                                st.tanfovy, st.image_height, st.image_width, sh, st.sh_degree, st.campos,
-                                               st.prefiltered, st.debug)
+                                               st.prefiltered, st.debug, antialiasing=antialiasing)
         ctx.raster_settings = raster_settings
         ctx.depth_alpha = depth_alpha
         ctx.densify_stats = densify_stats
         ctx.num_rendered = num_rendered
+        ctx.antialiasing = antialiasing
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, auxBuffer)
+                              binningBuffer, imgBuffer, auxBuffer, *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
         return color, radii, depth, alpha
@@ -175,7 +186,8 @@ class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
     def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
         st = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
-         auxBuffer) = ctx.saved_tensors
+         auxBuffer) = ctx.saved_tensors[:11]
+        kw = {"antialiasing": True, "opacities": ctx.saved_tensors[11]} if ctx.antialiasing else {}
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32,
                                          device=means3D.device)
@@ -185,7 +197,7 @@ class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
              grad_rotations) = _C.rasterize_gaussians_backward(
                 st.bg, means3D, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp, st.viewmatrix,
                 st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
-                ctx.num_rendered, binningBuffer, imgBuffer, st.debug, lean=not st.debug, stats=ctx.densify_stats)
+                ctx.num_rendered, binningBuffer, imgBuffer, st.debug, lean=not st.debug, stats=ctx.densify_stats, **kw)
         else:
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
              grad_rotations) = _C.rasterize_gaussians_backward_depth_alpha(
@@ -193,7 +205,7 @@ class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
                 st.viewmatrix, st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
                 ctx.num_rendered, binningBuffer, imgBuffer, auxBuffer,
                 None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
-                None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), st.debug, stats=ctx.densify_stats)
+                None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), st.debug, stats=ctx.densify_stats, **kw)
         return (
             grad_means3D,
             grad_means2D,
@@ -203,6 +215,7 @@ class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
             grad_scales if scales.numel() != 0 else None,
             grad_rotations if rotations.numel() != 0 else None,
             grad_cov3Ds_precomp if cov3Ds_precomp.numel() != 0 else None,
+            None,
             None,
             None,
             None,
@@ -235,12 +248,18 @@ class GaussianRasterizer(nn.Module):
     depth_alpha (extension, optional): "depth" or "invdepth" -- forward() then returns (color, radii, depth, alpha) with the
     depth map D = sum_i v_i alpha_i T_i (v_i = view-space z_i, or 1 / z_i; 0 where nothing blends) and the alpha map
     A = 1 - T_final, both (1, H, W) and differentiable, accumulated in the same blend pass as the colour
-    (_RasterizeGaussiansDepthAlpha).  Expected depth is D / A."""
+    (_RasterizeGaussiansDepthAlpha).  Expected depth is D / A.
 
-    def __init__(self, raster_settings, densify_stats=None, depth_alpha=None):
+    antialiasing (extension, default False): upstream's `antialiasing=True`, the screen-space filter of Mip-Splatting.  The projected
+    covariance keeps its 0.3 px^2 dilation, and the opacity is scaled by rho = sqrt(max(2.5e-5, det(Sigma) / det(Sigma + 0.3 I))), so a
+    sub-pixel Gaussian keeps the footprint integral of its undilated self; gradients include d rho (include/gsr_aa.h).  Combines with
+    depth_alpha.  A bool; anything else raises TypeError."""
+
+    def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
+        self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
         self.depth_alpha = depth_alpha
@@ -276,6 +295,7 @@ class GaussianRasterizer(nn.Module):
 
         if self.depth_alpha is not None:
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                   cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats)
+                                                   cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
+                                                   self.antialiasing)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings, self.densify_stats)
+                                   cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing)

@@ -52,8 +52,9 @@ def _f32(t, dev, what):
     return t.contiguous()
 
 
-def leaf_forward(xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings):
-    """Forward from the raw leaves -> (num_rendered, color, radii, geom, binning, img, M, contiguous inputs)."""
+def leaf_forward(xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing=False):
+    """Forward from the raw leaves -> (num_rendered, color, radii, geom, binning, img, M, contiguous inputs).
+    antialiasing: the screen-space filter (include/gsr_aa.h)."""
     if xyz.ndimension() != 2 or xyz.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")
     L = _lib()
@@ -80,8 +81,9 @@ def leaf_forward(xyz, features_dc, features_rest, opacity, scaling, rotation, ra
         if P:
             Rv = _i64(0)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _C._check(L.gsr_forward_preprocess_leaf(
-                P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
+            pre = (L.gsr_forward_preprocess_leaf,) if not antialiasing else (_C._aa_lib().gsr_forward_preprocess_leaf_aa, 1, None)
+            _C._check(pre[0](
+                *pre[1:], P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
                 opacity.data_ptr(), scaling.data_ptr(), float(st.scale_modifier), rotation.data_ptr(), view.data_ptr(),
                 proj.data_ptr(), campos.data_ptr(), float(st.tanfovx), float(st.tanfovy), int(bool(st.prefiltered)),
                 radii.data_ptr(), geom.data_ptr(), ctypes.byref(Rv), stream, _C._dbg(st.debug)))
@@ -112,11 +114,14 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
     backward for the Gaussians visible in this view (train.py:157-159, gaussian_model.py:599-602)."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
+                antialiasing=False):
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation) = leaf_forward(
-            xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings)
-        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats = raster_settings, R, M, stats
-        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img)
+            xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing)
+        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.antialiasing = raster_settings, R, M, stats, antialiasing
+        # the anti-aliased backward reads the opacity logits (the records hold sigmoid(logit) * rho): saved on that path only
+        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
+                              *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
         return color, radii
@@ -125,7 +130,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
     def backward(ctx, grad_color, _):
         L = _lib()
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
-        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors
+        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors[:9]
         dev = xyz.device
         if grad_color is None:
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
@@ -145,12 +150,16 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                                         dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
                 _C.set_backward_stats(a, ctx.stats, P, dev)
                 _C.backward_blend(a)
-                _C.backward_gaussians(a, 0, P, 0)
+                if ctx.antialiasing:
+                    _C.backward_gaussians_aa(a, _f32(ctx.saved_tensors[9], dev, "opacity"), None, 0, P, 0)
+                else:
+                    _C.backward_gaussians(a, 0, P, 0)
                 scratch.record_stream(torch.cuda.current_stream(dev))
-        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None
+        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None
 
 
-def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings):
+def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                             antialiasing=False):
     """leaf_forward() with the depth and alpha maps (include/gsr.h gsr_aux_args) -> (num_rendered, color, radii, geom, binning,
     img, M, contiguous inputs, depth (1,H,W), alpha (1,H,W), aux scratch)."""
     mode = _C.aux_mode(depth_alpha)
@@ -184,8 +193,9 @@ def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opaci
             stream = torch.cuda.current_stream(dev).cuda_stream
             pre = _C.AuxArgs()
             pre.mode = mode
-            _C._check(L.gsr_forward_preprocess_leaf_aux(
-                ctypes.byref(pre), P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
+            fn = (L.gsr_forward_preprocess_leaf_aux,) if not antialiasing else (_C._aa_lib().gsr_forward_preprocess_leaf_aa, 1)
+            _C._check(fn[0](
+                *fn[1:], ctypes.byref(pre), P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
                 opacity.data_ptr(), scaling.data_ptr(), float(st.scale_modifier), rotation.data_ptr(), view.data_ptr(),
                 proj.data_ptr(), campos.data_ptr(), float(st.tanfovx), float(st.tanfovy), int(bool(st.prefiltered)),
                 radii.data_ptr(), geom.data_ptr(), ctypes.byref(Rv), stream, _C._dbg(st.debug)))
@@ -202,11 +212,15 @@ class _RasterizeLeafGaussiansDepthAlpha(torch.autograd.Function):
     -> (color, radii, depth (1,H,W), alpha (1,H,W)).  Without gradients for either map the default backward kernels run."""
 
     @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, depth_alpha, stats=None):
+    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, depth_alpha, stats=None,
+                antialiasing=False):
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), depth, alpha, aux = \
-            leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings)
+            leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                                     antialiasing)
         ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
-        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux)
+        ctx.antialiasing = antialiasing
+        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux,
+                              *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
         return color, radii, depth, alpha
@@ -215,7 +229,7 @@ class _RasterizeLeafGaussiansDepthAlpha(torch.autograd.Function):
     def backward(ctx, grad_color, _, grad_depth, grad_alpha):
         L = _lib()
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
-        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux = ctx.saved_tensors
+        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux = ctx.saved_tensors[:10]
         dev = xyz.device
         if grad_color is None:
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
@@ -240,25 +254,37 @@ class _RasterizeLeafGaussiansDepthAlpha(torch.autograd.Function):
                                              None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
                                              None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), dev)
                     _C.backward_blend_aux(a, x)
+                else:
+                    x = None
+                    _C.backward_blend(a)
+                if ctx.antialiasing:
+                    _C.backward_gaussians_aa(a, _f32(ctx.saved_tensors[10], dev, "opacity"), x, 0, P, 0)
+                elif use_aux:
                     _C.backward_gaussians_aux(a, x, 0, P, 0)
                 else:
-                    _C.backward_blend(a)
                     _C.backward_gaussians(a, 0, P, 0)
                 scratch.record_stream(torch.cuda.current_stream(dev))
-        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None
+        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None
 
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                             depth_alpha=None):
+                             depth_alpha=None, antialiasing=False):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
     -> (color (3,H,W), radii (P,) int32); with depth_alpha = "depth" / "invdepth" -> (color, radii, depth, alpha), the maps of
-    GaussianRasterizer(raster_settings, depth_alpha=...)."""
+    GaussianRasterizer(raster_settings, depth_alpha=...).  antialiasing: the screen-space filter of
+    GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
+        if _C.aa_flag(antialiasing):
+            return _RasterizeLeafGaussiansDepthAlpha.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
+                                                           raster_settings, depth_alpha, stats, True)
         return _RasterizeLeafGaussiansDepthAlpha.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
                                                        raster_settings, depth_alpha, stats)
+    if _C.aa_flag(antialiasing):
+        return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                                             stats, True)
     return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats)
 
 

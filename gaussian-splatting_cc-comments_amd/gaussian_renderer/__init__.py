@@ -17,6 +17,7 @@ or the reference's own GaussianModel.
 Extension (not in the reference): `pipe.fused_activations = True` renders straight from the optimiser
 leaves (`pc._xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`) with the activations and
 their backward done inside the per-Gaussian kernels (fused_params.py) -- same result dict.
+`pipe.antialiasing = True` (where upstream's PipelineParams keeps it) renders with the screen-space filter (GaussianRasterizer).
 """
 import math
 
@@ -53,10 +54,14 @@ def _result(image, screenspace_points, radii, aux=None):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
-           depth_alpha=None):
+           depth_alpha=None, antialiasing=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
-    depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer."""
+    depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
+    antialiasing: the screen-space filter with opacity compensation (see GaussianRasterizer); None = getattr(pipe, "antialiasing",
+    False)."""
+    if antialiasing is None:
+        antialiasing = getattr(pipe, "antialiasing", False)
     xyz = pc.get_xyz
     # carrier of the screen-space gradient: zeros, a non-leaf that keeps its grad
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
@@ -71,7 +76,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     if getattr(pipe, "fused_activations", False) and override_color is None and not python_cov and not python_sh:
         from fused_params import rasterize_leaf_gaussians
         out = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
-                                       pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha)
+                                       pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha,
+                                       antialiasing=antialiasing)
         return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)
 
     inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
@@ -87,5 +93,6 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     else:
         inputs["shs"] = pc.get_features
 
-    out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha)(**inputs)
+    out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha,
+                             antialiasing=antialiasing)(**inputs)
     return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)

@@ -188,15 +188,17 @@ class _RasterizeViewParallel(torch.autograd.Function):
     views; dL_dmeans2D (the densification carrier) stays this view's own."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats):
+    def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats, antialiasing=False):
         from diff_gaussian_rasterization import _C
         st = raster_settings
         e = torch.empty(0, device=means3D.device)
         R, color, radii, geom, binning, img = _C.rasterize_gaussians(
             st.bg, means3D, e, opacities, scales, rotations, st.scale_modifier, e, st.viewmatrix, st.projmatrix, st.tanfovx,
-            st.tanfovy, st.image_height, st.image_width, shs, st.sh_degree, st.campos, st.prefiltered, st.debug)
-        ctx.st, ctx.R, ctx.exchange, ctx.stats = st, R, exchange, stats
-        ctx.save_for_backward(means3D, shs, scales, rotations, radii, geom, binning, img)
+            st.tanfovy, st.image_height, st.image_width, shs, st.sh_degree, st.campos, st.prefiltered, st.debug,
+            **({"antialiasing": True} if antialiasing else {}))
+        ctx.st, ctx.R, ctx.exchange, ctx.stats, ctx.antialiasing = st, R, exchange, stats, antialiasing
+        # the anti-aliased backward reads the opacity input (include/gsr_aa.h): saved on that path only
+        ctx.save_for_backward(means3D, shs, scales, rotations, radii, geom, binning, img, *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
         return color, radii
@@ -205,7 +207,7 @@ class _RasterizeViewParallel(torch.autograd.Function):
     def backward(ctx, grad_color, _):
         from diff_gaussian_rasterization import _C
         st, R, ex = ctx.st, ctx.R, ctx.exchange
-        means3D, shs, scales, rotations, radii, geom, binning, img = ctx.saved_tensors
+        means3D, shs, scales, rotations, radii, geom, binning, img = ctx.saved_tensors[:8]
         dev = means3D.device
         if grad_color is None:
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
@@ -228,20 +230,29 @@ class _RasterizeViewParallel(torch.autograd.Function):
             # required by the C ABI even when the part buffers are set below (validation happens per call)
             _C.set_backward_outputs(a, dL_dmean2D=d_means2D, **ex.output_pointers(0))
             _C.backward_blend(a)
+            opac = _C._dev_f32(ctx.saved_tensors[8], dev, "opacities") if ctx.antialiasing else None
             for k, (first, count) in enumerate(ex.ranges):
                 _C.set_backward_outputs(a, dL_dmean2D=d_means2D.data_ptr() + first * 12, **ex.output_pointers(k))
-                _C.backward_gaussians(a, first, count, first)
+                if opac is not None:
+                    _C.backward_gaussians_aa(a, opac, None, first, count, first)
+                else:
+                    _C.backward_gaussians(a, first, count, first)
                 ex.submit(k, campos)   # part k's collectives run while part k+1 computes
             scratch.record_stream(torch.cuda.current_stream(dev))
             g = ex.finish(means3D_c.detach(), int(st.sh_degree))
-        return g["dL_dmean3D"], d_means2D, g["dL_dsh"], g["dL_dopacity"], g["dL_dscale"], g["dL_drot"], None, None, None
+        return g["dL_dmean3D"], d_means2D, g["dL_dsh"], g["dL_dopacity"], g["dL_dscale"], g["dL_drot"], None, None, None, None
 
 
-def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None):
+def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
+                            antialiasing=False):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
-    DensificationStats.kernel_tensors())."""
+    DensificationStats.kernel_tensors()).  antialiasing: the screen-space filter of GaussianRasterizer(..., antialiasing=True)."""
+    from diff_gaussian_rasterization import _C
+    if _C.aa_flag(antialiasing):
+        return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
+                                            True)
     return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats)
 
 
