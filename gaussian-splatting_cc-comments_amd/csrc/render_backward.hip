@@ -6,10 +6,13 @@
 // atomics").  Here one wave64 owns the tile (render_common.h): per surviving instance each lane
 // first adds its four pixels' nine partials in registers; the wave then folds them through LDS --
 // lane l stores eight of them as row l of a 64 x 9-word area (odd row stride: 64 rows, 64 banks), the
-// eight lanes of group c add column c (eight rows each) and finish with three DPP steps, the ninth
-// value takes a DPP chain under that round trip (round 3; rounds 1-2 used a v_permlane32/16_swap
-// butterfly on the vector ALU, the port this kernel is bound by) -- and the tile's total for this
-// (Gaussian, tile) instance is written once, with plain stores, into that instance's own 48-byte
+// eight lanes of group c add column c (eight rows each).  What is left -- the three DPP steps over
+// each group's column sums, the ninth value's sum over the wave, the epilogue and the stores -- is
+// done for four reduced instances at a time, by one instruction stream whose 64 lanes are the four
+// instances' 8 values and 8 groups of the ninth (s_pend; the AUX variant finishes every instance on
+// its own: a DPP chain for the ninth and tenth values under the LDS round trip, round 3; rounds 1-2
+// used a v_permlane32/16_swap butterfly on the vector ALU, the port this kernel is bound by) -- and
+// the tile's total for this (Gaussian, tile) instance is written once, with plain stores, into that instance's own 48-byte
 // slot (slot = its position in the depth-ordered, per-Gaussian-contiguous emission order).  The
 // per-Gaussian kernel then adds each Gaussian's contiguous run of slots in a fixed order: no
 // atomics, no workgroup barrier (a wave's LDS operations execute in program order), bitwise
@@ -20,6 +23,7 @@
 #include <hip/hip_ext.h>
 
 #define GSR_BWD_NV 9
+#define GSR_BWD_FLUSH 4   // reduced instances finished together (default variant): 4 x (8 values + 8 groups of the ninth) = 64 lanes
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 GSR_TILE_CLOCK_BUFFER(gsr_backward_tile_clock, gsr_debug_tile_clock_backward)
@@ -57,6 +61,11 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	// 9 is odd, so the 64 rows of one store instruction fall into 64 different banks), then the eight lanes of group c read
 	// column c, eight rows each
 	__shared__ float s_red[GSR_WAVES_PER_WG][64 * 9 + 8];
+	// deferred finish (default variant): per reduced instance, its 64 column sums (lane (g, r) of the transposition at g * 8 + r)
+	// and the 64 lanes' v[8] (at 64 + lane); up to GSR_BWD_FLUSH instances wait here and are finished together (gsr_flush below).
+	// 2 KB more per wave: 9.5 KB x 16 waves still fits one CU's 160 KB at 4 waves per SIMD.  The AUX variant keeps the
+	// per-instance finish (its tenth value would leave fewer lanes per flush and its LDS would not fit 16 waves).
+	__shared__ __attribute__((aligned(16))) float s_pend[GSR_WAVES_PER_WG][AUX ? 4 : GSR_BWD_FLUSH * 128];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const int slot_id = blockIdx.x * GSR_WAVES_PER_WG + wave;
 	if (slot_id >= nslots) return;  // wave-uniform; no barriers below
@@ -186,6 +195,16 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	constexpr int red_step = 72;
 	const float out_scale = (out_index >= 2 && out_index <= 4) ? -0.5f : 1.0f;
 	const float k01 = out_index == 0 ? -ddelx_dx : -ddely_dy;   // backward.cu:574-575: dL/dmean2D is scaled by 0.5 W / 0.5 H
+	// The flush's lanes: lane = 32 h + 8 i + g.  h = 0: value g of pending instance i; h = 1: 8-lane group g of the same instance's
+	// v[8].  Each reads eight consecutive words of s_pend: the column sums (i, g, r = 0..7), or v[8] of lanes 8 g .. 8 g + 7.
+	const int f_inst = (lane >> 3) & 3, f_val = lane & 7;
+	float* const pend_w = s_pend[wave] + lane;
+	const float* const pend_r = s_pend[wave] + f_inst * 128 + (lane >> 5) * 64 + f_val * 8;
+	const float f_scale = (f_val >= 2 && f_val <= 4) ? -0.5f : 1.0f;
+	const float f_k01 = f_val == 0 ? -ddelx_dx : -ddely_dy;
+	const bool f_word = lane < 32 || f_val == 0;   // stores a value word (lanes 0-31) or the ninth word (first lane of each upper group)
+	int npend = 0;          // wave-uniform: reduced instances waiting in s_pend
+	uint32_t pend_j = 0u;   // wave-uniform: their batch indices j, eight bits each (unused bytes 0, so every lane reads inside rec)
 
 	for (int base = 0; base < nw; base += 64) {
 		const uint32_t bands = (base + lane < nw) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
@@ -215,6 +234,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 		id_next = (base + 128 + lane < nw) ? plist[top - 1 - (base + 128 + lane)] : 0u;
 		__builtin_amdgcn_wave_barrier();
 
+#pragma clang loop unroll(disable)
 		for (int j = 0; j < cnt; j++) {
 			const float4 R0 = rec[0][j], R1 = rec[1][j], R2 = rec[2][j], R3 = rec[3][j], R4 = rec[4][j];
 			const int contributor = __builtin_amdgcn_readfirstlane(__float_as_int(R4.z));  // backward.cu:511-515; wave-uniform
@@ -322,26 +342,72 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				float col[8];
 #pragma unroll
 				for (int k = 0; k < 8; k++) col[k] = red_r[red_step * k];
-				// the ninth value's DPP chain runs while the LDS round trip is under way
-				__builtin_amdgcn_sched_barrier(0);
-				const float t9 = gsr_wave_sum_to_lane63(v[8]);  // lane 63 holds the total of v[8]
-				const float t10 = AUX ? gsr_wave_sum_to_lane63(gsr_add_halves(acc[9])) : 0.f;   // ... and (AUX) of dL/dv
-				__builtin_amdgcn_sched_barrier(0);
-				const float tcol = ((col[0] + col[1]) + (col[2] + col[3])) + ((col[4] + col[5]) + (col[6] + col[7]));
-				const float t8 = gsr_sum8(tcol);                // group c holds the total of v[c]
-				// dL/dmean2D: group 0 (sum f dx = sx) needs sy, group 1 (sy) needs sx -- the partner half row, one DPP move; the
-				// same products and the same FMA as the scalar form below (a sx + b sy with a = -2 (-0.5 a)), so the same bits
-				const float other = gsr_dpp_mov<0x128, 0xF, 0xF, true>(t8);  // row_ror:8
-				const float r01 = k01 * __builtin_fmaf(-2.0f, (out_index == 0 ? CA.x : CC.x) * t8, CB.x * other);
-				const uint32_t slot = __builtin_amdgcn_readfirstlane(__float_as_uint(R4.w));
-				float* out = reinterpret_cast<float*>(slots + slot);
-				const float r = out_index < 2 ? r01 : out_scale * t8;   // dL/dconic .x .y .w (x -0.5); opacity and colour as they are
-				if ((lane & 7) == 0) out[out_index] = r;
-				if (lane == 63) {
-					out[8] = t9;
-					if (AUX) out[9] = t10;
-					slot_valid[slot] = 1;
+				if constexpr (AUX) {
+					// the ninth value's DPP chain runs while the LDS round trip is under way
+					__builtin_amdgcn_sched_barrier(0);
+					const float t9 = gsr_wave_sum_to_lane63(v[8]);  // lane 63 holds the total of v[8]
+					const float t10 = gsr_wave_sum_to_lane63(gsr_add_halves(acc[9]));   // ... and of dL/dv
+					__builtin_amdgcn_sched_barrier(0);
+					const float tcol = ((col[0] + col[1]) + (col[2] + col[3])) + ((col[4] + col[5]) + (col[6] + col[7]));
+					const float t8 = gsr_sum8(tcol);                // group c holds the total of v[c]
+					// dL/dmean2D: group 0 (sum f dx = sx) needs sy, group 1 (sy) needs sx -- the partner half row, one DPP move; the
+					// same products and the same FMA as the scalar form below (a sx + b sy with a = -2 (-0.5 a)), so the same bits
+					const float other = gsr_dpp_mov<0x128, 0xF, 0xF, true>(t8);  // row_ror:8
+					const float r01 = k01 * __builtin_fmaf(-2.0f, (out_index == 0 ? CA.x : CC.x) * t8, CB.x * other);
+					const uint32_t slot = __builtin_amdgcn_readfirstlane(__float_as_uint(R4.w));
+					float* out = reinterpret_cast<float*>(slots + slot);
+					const float r = out_index < 2 ? r01 : out_scale * t8;   // dL/dconic .x .y .w (x -0.5); opacity and colour as they are
+					if ((lane & 7) == 0) out[out_index] = r;
+					if (lane == 63) {
+						out[8] = t9;
+						out[9] = t10;
+						slot_valid[slot] = 1;
+					}
+				} else {
+					// Everything after the column sums waits for the flush: this lane's column sum and its v[8] go to the
+					// instance's place in s_pend, its batch index j to pend_j.  The 7 adds below are all the per-instance work left.
+					const float tcol = ((col[0] + col[1]) + (col[2] + col[3])) + ((col[4] + col[5]) + (col[6] + col[7]));
+					pend_w[npend * 128] = tcol;
+					pend_w[npend * 128 + 64] = v[8];
+					pend_j |= (uint32_t)j << (8 * npend);
+					npend++;
 				}
+			}
+			if (!AUX && (npend == GSR_BWD_FLUSH || (npend != 0 && j == cnt - 1))) {  // wave-uniform; rec is restaged only after the batch
+				// gsr_flush: finish up to four reduced instances in one instruction stream over the 64 lanes.  A wave's LDS
+				// operations execute in program order, so the reads below see every s_pend store above, and the next instance's
+				// stores come after them; the wave barriers only keep the compiler from moving LDS accesses across.
+				__builtin_amdgcn_wave_barrier();
+				const float4 q0 = *reinterpret_cast<const float4*>(pend_r), q1 = *reinterpret_cast<const float4*>(pend_r + 4);
+				// the instance's epilogue scalars, still staged in rec: -0.5 conic a and b (rec[1]), -0.5 conic c (rec[2]), slot (rec[4])
+				const uint32_t jf = (pend_j >> (8 * f_inst)) & 0xFFu;
+				const float* const rj = reinterpret_cast<const float*>(&rec[0][jf]);
+				const float ca = rj[4 * 64], cb = rj[4 * 64 + 2], cc = rj[8 * 64];
+				const uint32_t slot = __float_as_uint(rj[16 * 64 + 3]);
+				// one LDS round trip for all six reads: left alone, the compiler sinks the scalars' reads into the store branch below
+				// and waits for them a second time
+				asm volatile("" ::"v"(q0.x), "v"(q1.x), "v"(ca), "v"(cb), "v"(cc), "v"(slot));
+				// lanes 0-31: value g's eight column sums, r = 0..7, added as gsr_sum8 adds the lanes (g, 0..7) of the per-instance
+				// form -- quad_perm [1,0,3,2] pairs (0,1) ... (6,7), quad_perm [2,3,0,1] pairs the pairs, row_half_mirror the
+				// quads: ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)), each add's operand order aside, which fp32 addition does not see.
+				// lanes 32-63: the same tree over v[8] of lanes 8 g .. 8 g + 7 is S_g, the value gsr_wave_sum_to_lane63 has in
+				// every lane of group g after its first three steps.  Its row_mirror step makes R_k = S_2k + S_2k+1, row_bcast:15
+				// leaves R3 + R2 in lane 63, row_bcast:31 adds R1 + R0 (lane 31): (R0+R1)+(R2+R3).  gsr_sum8 over S_0..S_7 is
+				// (S0+S1)+(S2+S3) = R0+R1 in the first quad and R2+R3 in the second, then their sum: the same total, bit for bit.
+				const float t = ((q0.x + q0.y) + (q0.z + q0.w)) + ((q1.x + q1.y) + (q1.z + q1.w));
+				const float t9 = gsr_sum8(t);   // lanes 32-63: the instance's total of v[8]
+				// dL/dmean2D: value 0 (sum f dx = sx) needs sy, value 1 needs sx -- the neighbouring lane, one DPP move; the same
+				// products and the same FMA as the per-instance form (a sx + b sy with a = -2 (-0.5 a))
+				const float other = gsr_dpp_mov<0xB1, 0xF, 0xF, true>(t);  // quad_perm [1,0,3,2]
+				const float r01 = f_k01 * __builtin_fmaf(-2.0f, (f_val == 0 ? ca : cc) * t, cb * other);
+				const float r = f_val < 2 ? r01 : f_scale * t;   // dL/dconic .x .y .w (x -0.5); opacity and colour as they are
+				if (f_inst < npend) {
+					if (f_word) reinterpret_cast<float*>(slots + slot)[lane < 32 ? f_val : 8] = lane < 32 ? r : t9;
+					if (lane >= 32 && f_val == 0) slot_valid[slot] = 1;
+				}
+				npend = 0;
+				pend_j = 0u;
+				__builtin_amdgcn_wave_barrier();
 			}
 		}
 		__builtin_amdgcn_wave_barrier();
