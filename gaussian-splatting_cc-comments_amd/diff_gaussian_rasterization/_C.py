@@ -56,6 +56,18 @@ class BackwardArgs(ctypes.Structure):
                 [("debug", _i)])
 
 
+AUX_MODES = {"depth": 1, "invdepth": 2}   # GSR_AUX_DEPTH / GSR_AUX_INVDEPTH
+
+
+class AuxArgs(ctypes.Structure):
+    """include/gsr_aux.h gsr_aux_args (the depth and alpha maps; opt-in, kernels of their own)"""
+    _fields_ = [("mode", _i), ("out_depth", _vp), ("out_alpha", _vp), ("dL_ddepth", _vp), ("dL_dalpha", _vp), ("scratch", _vp)]
+
+
+class AuxLayout(ctypes.Structure):
+    _fields_ = [(n, _sz) for n in ("ckpt_depth", "final_D", "total")]
+
+
 # bits of the C ABI's `debug` mask (include/gsr.h GSR_DEBUG_*).  The reference's bool `debug` is DEBUG_SYNC; tests pass the
 # diagnostic bits as an int in the same argument, per call -- nothing is read from the environment.
 DEBUG_SYNC, DEBUG_NO_CULL, DEBUG_SERIAL, DEBUG_NO_SPLIT, DEBUG_TILE_SORT, DEBUG_RADIX_DEPTH, DEBUG_NO_TRIM = 1, 2, 4, 8, 16, 32, 64
@@ -127,8 +139,33 @@ def lib():
     L.gsr_profile_begin_only.argtypes = [_vp, ctypes.c_char_p]
     L.gsr_profile_end.restype = _i
     L.gsr_profile_end.argtypes = [_vp, ctypes.POINTER(KernelTime), _i]
+    # include/gsr.h: the leaf-parameter forward (fused_params.py) and the optimiser step (its groups: fused_params.AdamGroup)
+    leaf_pre = [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp, ctypes.POINTER(_i64), _vp, _i]
+    L.gsr_forward_preprocess_leaf.restype = _i
+    L.gsr_forward_preprocess_leaf.argtypes = leaf_pre
+    L.gsr_adam_step.restype = _i
+    L.gsr_adam_step.argtypes = [_i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]
+    # include/gsr_aux.h (depth and alpha maps) and include/gsr_aa.h (screen-space filter): the same calls with leading arguments
+    pa, pb = ctypes.POINTER(AuxArgs), ctypes.POINTER(BackwardArgs)
+    L.gsr_aux_bytes.restype = _sz
+    L.gsr_aux_bytes.argtypes = [_i64, _i, _i]
+    L.gsr_aux_layout_of.restype = _i
+    L.gsr_aux_layout_of.argtypes = [_i64, _i, _i, ctypes.POINTER(AuxLayout)]
+    for name, argtypes in (("gsr_forward_preprocess_aux", [pa] + list(L.gsr_forward_preprocess.argtypes)),
+                           ("gsr_forward_preprocess_leaf_aux", [pa] + leaf_pre),
+                           ("gsr_forward_render_aux", [pa] + list(L.gsr_forward_render.argtypes)),
+                           ("gsr_backward_blend_aux", [pb, pa]),
+                           ("gsr_backward_gaussians_aux", [pb, pa, _i, _i, _i]),
+                           ("gsr_forward_preprocess_aa", [_i, pa] + list(L.gsr_forward_preprocess.argtypes)),
+                           ("gsr_forward_preprocess_leaf_aa", [_i, pa] + leaf_pre),
+                           ("gsr_backward_gaussians_aa", [pb, _i, _vp, pa, _i, _i, _i])):
+        getattr(L, name).restype = _i
+        getattr(L, name).argtypes = argtypes
     _lib = L
     return L
+
+
+_aux_lib = _aa_lib = lib   # every entry point is declared by lib()
 
 
 def _check(rc):
@@ -158,50 +195,234 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, *, antialiasing=False):
-    """-> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer)
-    antialiasing: the screen-space filter (include/gsr_aa.h): the splat records carry opacity * rho"""
+def aux_mode(name):
+    """"depth" / "invdepth" -> the C ABI's mode; anything else raises ValueError."""
+    if not isinstance(name, str) or name not in AUX_MODES:
+        raise ValueError(f"depth_alpha must be one of {sorted(AUX_MODES)} or None, got {name!r}")
+    return AUX_MODES[name]
+
+
+def aa_flag(antialiasing):
+    """The `antialiasing` keyword -> bool; anything but a bool raises TypeError (a mode string or a number is not a switch here)."""
+    if not isinstance(antialiasing, bool):
+        raise TypeError(f"antialiasing must be True or False, got {antialiasing!r}")
+    return antialiasing
+
+
+# ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
+def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None):
+    """-> (function of L, the arguments that precede the default entry point's own).  stage: "preprocess" | "render" (the two forward
+    calls) | "blend" | "gaussians" (the two backward stages: their leading arguments follow the gsr_backward_args pointer); leaf: the
+    inputs are the optimiser's leaves (fused_params.py); x: the AuxArgs of a call with depth and alpha maps, or None; aa: the
+    screen-space filter, whose per-Gaussian backward reads the forward's opacity input at address `opacities`.  The *_aa entry
+    points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice."""
+    xr = None if x is None else ctypes.byref(x)
+    if stage == "preprocess":
+        name = "gsr_forward_preprocess_leaf" if leaf else "gsr_forward_preprocess"
+        name, lead = (name + "_aa", (1, xr)) if aa else (name + "_aux", (xr,)) if x is not None else (name, ())
+    elif stage == "gaussians":
+        name, lead = ("gsr_backward_gaussians_aa", (1, opacities, xr)) if aa else \
+            ("gsr_backward_gaussians_aux", (xr,)) if x is not None else ("gsr_backward_gaussians", ())
+    else:
+        name = {"render": "gsr_forward_render", "blend": "gsr_backward_blend"}[stage]
+        name, lead = (name + "_aux", (xr,)) if x is not None else (name, ())
+    return getattr(L, name), lead
+
+
+# ---- the forward of every variant ------------------------------------------------------------------------------------------------
+def run_forward(leaf, mode, antialiasing, background, named, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug):
+    """Validate, allocate, preprocess, read the count back, allocate the binning state, render.
+    named: the tensor arguments of the preprocess entry point in its order, as (tensor, name in error messages): the Gaussians first
+    (five tensors, means3D leading, before scale_modifier; the rest after it), then viewmatrix, projmatrix, campos.
+    mode: None, or aux_mode() of the depth and alpha maps to produce.
+    -> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer, the contiguous tensors of `named`,
+        () or (depth (1,H,W), alpha (1,H,W), auxBuffer))"""
     aa = aa_flag(antialiasing)
+    means3D = named[0][0]
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:60-63
     if not means3D.is_cuda:
         raise RuntimeError("means3D must be a HIP (cuda) tensor; the HIP rasterizer has no CPU path")
     L = lib()
     dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    means3D = _dev_f32(means3D, dev, "means3D")
+    P, H, W = int(means3D.size(0)), int(H), int(W)
+    tensors = [_dev_f32(t, dev, n) for t, n in named]
     background = _dev_f32(background, dev, "bg")
-    colors, opacity, scales, rotations, cov3D_precomp, sh = (
-        _dev_f32(t, dev, n) for t, n in ((colors, "colors_precomp"), (opacity, "opacities"), (scales, "scales"),
-                                         (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"), (sh, "shs")))
-    viewmatrix, projmatrix, campos = (_dev_f32(t, dev, n) for t, n in ((viewmatrix, "viewmatrix"),
-                                                                        (projmatrix, "projmatrix"), (campos, "campos")))
     byte = dict(dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        out_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev) if P == 0 else \
-            torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        alloc = torch.zeros if P == 0 else torch.empty   # the kernels write every element; nothing is launched for P == 0
+        out_color = alloc((3, H, W), **f32)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
+        maps = () if mode is None else (alloc((1, H, W), **f32), alloc((1, H, W), **f32))
         if P == 0:  # rasterize_points.cu:94
             e = torch.empty((0,), **byte)
-            return 0, out_color, radii, e, e.clone(), e.clone()
-        M = int(sh.size(1)) if sh.numel() != 0 else 0
+            return 0, out_color, radii, e, e.clone(), e.clone(), tensors, maps and maps + (e.clone(),)
         geom = torch.empty((L.gsr_geometry_bytes(P),), **byte)
         img = torch.empty((L.gsr_image_bytes(W, H),), **byte)
+        x = None
+        if mode is not None:
+            x = AuxArgs()
+            x.mode = mode   # all that preprocess reads of it; the outputs are set once the count is known
+        preprocess, pre_lead = _entry(L, "preprocess", leaf, x, aa)
+        render, ren_lead = _entry(L, "render", leaf, x)
         R = _i64(0)
-        stream = _stream(dev)
-        pre = (L.gsr_forward_preprocess,) if not aa else (_aa_lib().gsr_forward_preprocess_aa, 1, None)
-        _check(pre[0](*pre[1:], P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity),
-                      _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                      _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx),
-                      float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
-                      ctypes.byref(R), stream, _dbg(debug)))
+        stream, dbg = _stream(dev), _dbg(debug)
+        p = [_ptr(t) for t in tensors]
+        _check(preprocess(*pre_lead, P, int(degree), int(M), W, H, *p[:5], float(scale_modifier), *p[5:], float(tan_fovx),
+                          float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom), ctypes.byref(R), stream, dbg))
         R = int(R.value)
         binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
-        _check(L.gsr_forward_render(P, R, W, H, _ptr(background), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img),
-                                    _ptr(out_color), stream, _dbg(debug)))
-    return R, out_color, radii, geom, binning, img
+        if x is not None:
+            maps += (torch.empty((L.gsr_aux_bytes(R, W, H),), **byte),)
+            x.out_depth, x.out_alpha, x.scratch = (_ptr(t) for t in maps)
+        _check(render(*ren_lead, P, R, W, H, _ptr(background), _ptr(radii), _ptr(geom), _ptr(binning), _ptr(img), _ptr(out_color),
+                      stream, dbg))
+    return R, out_color, radii, geom, binning, img, tensors, maps
+
+
+def _forward_plain(mode, antialiasing, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                   viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug):
+    """The reference's argument list (rasterize_points.cu:38-59) -> run_forward()'s, in gsr_forward_preprocess's order."""
+    r = run_forward(False, mode, antialiasing, background,
+                    ((means3D, "means3D"), (sh, "shs"), (colors, "colors_precomp"), (opacity, "opacities"), (scales, "scales"),
+                     (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"), (viewmatrix, "viewmatrix"),
+                     (projmatrix, "projmatrix"), (campos, "campos")),
+                    degree, int(sh.size(1)) if sh.numel() != 0 else 0, image_width, image_height, scale_modifier, tan_fovx,
+                    tan_fovy, prefiltered, debug)
+    return r[:6] + r[7]
+
+
+def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                        viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                        prefiltered, debug, *, antialiasing=False):
+    """-> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer)
+    antialiasing: the screen-space filter (include/gsr_aa.h): the splat records carry opacity * rho"""
+    return _forward_plain(None, antialiasing, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                          cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                          prefiltered, debug)
+
+
+def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                                    cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                                    degree, campos, prefiltered, debug, *, antialiasing=False):
+    """rasterize_gaussians() with the depth and alpha maps of mode `depth_alpha` ("depth" / "invdepth") from the same blend pass
+    -> (num_rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, depth (1,H,W), alpha (1,H,W), auxBuffer).
+    Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s (with the same `antialiasing`)."""
+    return _forward_plain(aux_mode(depth_alpha), antialiasing, background, means3D, colors, opacity, scales, rotations,
+                          scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
+                          degree, campos, prefiltered, debug)
+
+
+# ---- the backward of every variant -----------------------------------------------------------------------------------------------
+def backward_scratch(P, R, device):
+    """The scratch of one backward (gsr_backward_args.scratch); hand it back with release_scratch() once the calls are enqueued."""
+    return torch.empty((lib().gsr_backward_scratch_bytes(int(P), int(R)),), dtype=torch.uint8, device=device)
+
+
+def release_scratch(scratch, device):
+    scratch.record_stream(torch.cuda.current_stream(device))
+
+
+def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
+    """AuxArgs of a backward: dL_ddepth / dL_dalpha (1,H,W) or (H,W) or None (= zero).  The tensors must stay alive until the calls
+    that use the struct have been enqueued; the contiguous copies are kept on the struct."""
+    x = AuxArgs()
+    x.mode = aux_mode(mode)
+    keep = []
+    for name, t in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
+        if t is not None:
+            t = _dev_f32(t, device, name)
+            keep.append(t)
+        setattr(x, name, _ptr(t))
+    x.scratch = _ptr(scratch)
+    x._keep = keep
+    return x
+
+
+def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None):
+    """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
+    blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
+    `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
+    logits in leaf mode) when the screen-space filter was on, else None; before_part(k) / after_part(k): called around part k's pass
+    (view_parallel.py sets the part's output pointers and starts its collectives there)."""
+    L = lib()
+    ra = ctypes.byref(a)
+    blend, lead = _entry(L, "blend", x=x)
+    _check(blend(ra, *lead))
+    aa = opacities is not None
+    if aa and not isinstance(opacities, int):
+        opacities = _ptr(_dev_f32(opacities, device, "opacities"))
+    gaussians, lead = _entry(L, "gaussians", x=x, aa=aa, opacities=opacities)
+    for k, (first, count) in enumerate(((0, a.P),) if parts is None else parts):
+        if before_part is not None:
+            before_part(k)
+        _check(gaussians(ra, *lead, int(first), int(count), int(first)))
+        if after_part is not None:
+            after_part(k)
+    release_scratch(scratch, device)
+
+
+def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities):
+    """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
+    132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
+    (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+     dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, debug) = args
+    aa = aa_flag(antialiasing)
+    if aa and opacities is None:
+        raise RuntimeError(f"{who}: antialiasing=True needs the forward's opacities")
+    L = lib()
+    dev = means3D.device
+    P = int(means3D.size(0))
+    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
+    M = int(sh.size(1)) if sh.numel() != 0 else 0
+    f32 = dict(dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        # every element is written by the kernels (no zero-fill pass, unlike rasterize_points.cu:168-178)
+        alloc = torch.zeros if P == 0 else torch.empty
+        dL_dmeans3D = alloc((P, 3), **f32)
+        dL_dmeans2D = alloc((P, 3), **f32)
+        skip_sh = bool(skip_sh) and M > 0
+        lean = bool(lean) and debug_out is None
+        none = torch.empty((0,), **f32)
+        dL_dcolors = alloc((P, 3), **f32) if (not lean or colors.numel() != 0 or skip_sh) else none
+        dL_dconic = alloc((P, 2, 2), **f32) if not lean else none
+        dL_dopacity = alloc((P, 1), **f32)
+        dL_dcov3D = alloc((P, 6), **f32) if (not lean or cov3D_precomp.numel() != 0) else none
+        dL_dsh = None if skip_sh else alloc((P, M, 3), **f32)
+        dL_dscales = alloc((P, 3), **f32)
+        dL_drotations = alloc((P, 4), **f32)
+        if P != 0:
+            background, means3D, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, dL_dout_color, sh, campos = (
+                _dev_f32(t, dev, n) for t, n in (
+                    (background, "bg"), (means3D, "means3D"), (colors, "colors_precomp"), (scales, "scales"), (rotations, "rotations"),
+                    (cov3D_precomp, "cov3D_precomp"), (viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"),
+                    (dL_dout_color, "dL_dout_color"), (sh, "shs"), (campos, "campos")))
+            scratch = backward_scratch(P, R, dev)
+            if stats is None and not aa and aux is None:   # nothing but the reference's backward: one call for both stages
+                _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
+                                      _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                                      _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
+                                      _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(scratch),
+                                      _ptr(dL_dout_color), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
+                                      _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
+                                      _ptr(dL_drotations), _stream(dev), _dbg(debug)))
+                release_scratch(scratch, dev)
+            else:
+                a = backward_args(P=P, D=int(degree), M=M, R=int(R), W=W, H=H, leaf=0, background=background, means3D=means3D,
+                                  shs=sh, colors_precomp=colors, scales=scales, scale_modifier=scale_modifier,
+                                  rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix,
+                                  projmatrix=projmatrix, cam_pos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, radii=radii,
+                                  geometry=geomBuffer, binning=binningBuffer, image=imageBuffer, scratch=scratch,
+                                  dL_dpix=dL_dout_color, debug=debug, device=dev)
+                set_backward_outputs(a, dL_dmean2D=dL_dmeans2D, dL_dconic=dL_dconic, dL_dopacity=dL_dopacity,
+                                     dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh,
+                                     dL_dscale=dL_dscales, dL_drot=dL_drotations)
+                set_backward_stats(a, stats, P, dev)
+                run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None)
+    if debug_out is not None:
+        debug_out["dL_dconic"] = dL_dconic
+    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -220,66 +441,23 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
       stats     (xyz_gradient_accum, denom, max_radii2D) float32 [P] tensors updated in place for the Gaussians
                 visible in this view (train.py:157-159, gaussian_model.py:599-602); any of them may be None
       antialiasing  the backward of an antialiasing=True forward; `opacities` is then its opacity input (include/gsr_aa.h)"""
-    aa = aa_flag(antialiasing)
-    if aa and opacities is None:
-        raise RuntimeError("rasterize_gaussians_backward: antialiasing=True needs the forward's opacities")
-    L = lib()
-    dev = means3D.device
-    P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    f32 = dict(dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        # every element is written by gsr_backward (no zero-fill pass, unlike rasterize_points.cu:168-178)
-        alloc = torch.zeros if P == 0 else torch.empty
-        dL_dmeans3D = alloc((P, 3), **f32)
-        dL_dmeans2D = alloc((P, 3), **f32)
-        skip_sh = bool(skip_sh) and M > 0
-        lean = bool(lean) and debug_out is None
-        none = torch.empty((0,), **f32)
-        dL_dcolors = alloc((P, 3), **f32) if (not lean or colors.numel() != 0 or skip_sh) else none
-        dL_dconic = alloc((P, 2, 2), **f32) if not lean else none
-        dL_dopacity = alloc((P, 1), **f32)
-        dL_dcov3D = alloc((P, 6), **f32) if (not lean or cov3D_precomp.numel() != 0) else none
-        dL_dsh = None if skip_sh else alloc((P, M, 3), **f32)
-        dL_dscales = alloc((P, 3), **f32)
-        dL_drotations = alloc((P, 4), **f32)
-        if P != 0:
-            means3D = _dev_f32(means3D, dev, "means3D")
-            dL_dout_color = _dev_f32(dL_dout_color, dev, "dL_dout_color")
-            background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix, projmatrix, campos = (
-                _dev_f32(t, dev, "input") for t in (background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix,
-                                                    projmatrix, campos))
-            scratch = torch.empty((L.gsr_backward_scratch_bytes(P, int(R)),), dtype=torch.uint8, device=dev)
-            if stats is None and not aa:
-                _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
-                                      _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                                      _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
-                                      _ptr(radii), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer), _ptr(scratch),
-                                      _ptr(dL_dout_color), _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity),
-                                      _ptr(dL_dcolors), _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
-                                      _ptr(dL_drotations), _stream(dev), _dbg(debug)))
-            else:
-                a = backward_args(P=P, D=int(degree), M=M, R=int(R), W=W, H=H, leaf=0, background=background, means3D=means3D,
-                                  shs=sh, colors_precomp=colors, scales=scales, scale_modifier=scale_modifier,
-                                  rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix,
-                                  projmatrix=projmatrix, cam_pos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, radii=radii,
-                                  geometry=geomBuffer, binning=binningBuffer, image=imageBuffer, scratch=scratch,
-                                  dL_dpix=dL_dout_color, debug=debug, device=dev)
-                set_backward_outputs(a, dL_dmean2D=dL_dmeans2D, dL_dconic=dL_dconic, dL_dopacity=dL_dopacity,
-                                     dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh,
-                                     dL_dscale=dL_dscales, dL_drot=dL_drotations)
-                set_backward_stats(a, stats, P, dev)
-                backward_blend(a)
-                if aa:
-                    opacities = _dev_f32(opacities, dev, "opacities")
-                    backward_gaussians_aa(a, opacities, None, 0, P, 0)
-                else:
-                    backward_gaussians(a, 0, P, 0)
-            scratch.record_stream(torch.cuda.current_stream(dev))
-    if debug_out is not None:
-        debug_out["dL_dconic"] = dL_dconic
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    return _backward_plain("rasterize_gaussians_backward", None,
+                           (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                            projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities)
+
+
+def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
+                                             cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
+                                             degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
+                                             dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None):
+    """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
+    top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
+    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities: as there."""
+    return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
+                           (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                            projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
+                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities)
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------
@@ -410,222 +588,7 @@ def profile_end(capacity=256, device=None):
     return [(arr[k].name.decode(), float(arr[k].ms)) for k in range(n)]
 
 
-# ---- depth and alpha maps (include/gsr.h gsr_aux_args; opt-in, kernels of their own) ---------------------------------
-AUX_MODES = {"depth": 1, "invdepth": 2}   # GSR_AUX_DEPTH / GSR_AUX_INVDEPTH
-
-
-class AuxArgs(ctypes.Structure):
-    """include/gsr.h gsr_aux_args"""
-    _fields_ = [("mode", _i), ("out_depth", _vp), ("out_alpha", _vp), ("dL_ddepth", _vp), ("dL_dalpha", _vp), ("scratch", _vp)]
-
-
-class AuxLayout(ctypes.Structure):
-    _fields_ = [(n, _sz) for n in ("ckpt_depth", "final_D", "total")]
-
-
-def aux_mode(name):
-    """"depth" / "invdepth" -> the C ABI's mode; anything else raises ValueError."""
-    if not isinstance(name, str) or name not in AUX_MODES:
-        raise ValueError(f"depth_alpha must be one of {sorted(AUX_MODES)} or None, got {name!r}")
-    return AUX_MODES[name]
-
-
-def _aux_lib():
-    L = lib()
-    if not getattr(L, "_gsr_aux_bound", False):
-        pa = ctypes.POINTER(AuxArgs)
-        L.gsr_aux_bytes.restype = _sz
-        L.gsr_aux_bytes.argtypes = [_i64, _i, _i]
-        L.gsr_aux_layout_of.restype = _i
-        L.gsr_aux_layout_of.argtypes = [_i64, _i, _i, ctypes.POINTER(AuxLayout)]
-        L.gsr_forward_preprocess_aux.restype = _i
-        L.gsr_forward_preprocess_aux.argtypes = [pa] + list(L.gsr_forward_preprocess.argtypes)
-        L.gsr_forward_preprocess_leaf_aux.restype = _i
-        L.gsr_forward_preprocess_leaf_aux.argtypes = [pa] + [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp,
-                                                                                                   ctypes.POINTER(_i64), _vp, _i]
-        L.gsr_forward_render_aux.restype = _i
-        L.gsr_forward_render_aux.argtypes = [pa] + list(L.gsr_forward_render.argtypes)
-        L.gsr_backward_blend_aux.restype = _i
-        L.gsr_backward_blend_aux.argtypes = [ctypes.POINTER(BackwardArgs), pa]
-        L.gsr_backward_gaussians_aux.restype = _i
-        L.gsr_backward_gaussians_aux.argtypes = [ctypes.POINTER(BackwardArgs), pa, _i, _i, _i]
-        L._gsr_aux_bound = True
-    return L
-
-
 def aux_layout(R, W, H):
     lay = AuxLayout()
-    _check(_aux_lib().gsr_aux_layout_of(int(R), int(W), int(H), ctypes.byref(lay)))
+    _check(lib().gsr_aux_layout_of(int(R), int(W), int(H), ctypes.byref(lay)))
     return {n: getattr(lay, n) for n, _ in AuxLayout._fields_}
-
-
-def aux_forward_args(mode, P, R, W, H, device):
-    """-> (AuxArgs, depth (1,H,W), alpha (1,H,W), scratch) for a forward with num_rendered R: the maps are fully written by the
-    render call (zeros when P == 0, where nothing is launched)."""
-    f32 = dict(dtype=torch.float32, device=device)
-    alloc = torch.zeros if P == 0 else torch.empty
-    depth, alpha = alloc((1, H, W), **f32), alloc((1, H, W), **f32)
-    scratch = torch.empty((_aux_lib().gsr_aux_bytes(int(R), W, H) if P else 0,), dtype=torch.uint8, device=device)
-    x = AuxArgs()
-    x.mode = aux_mode(mode) if isinstance(mode, str) else int(mode)
-    x.out_depth, x.out_alpha, x.scratch = _ptr(depth), _ptr(alpha), _ptr(scratch)
-    return x, depth, alpha, scratch
-
-
-def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
-    """AuxArgs of a backward: dL_ddepth / dL_dalpha (1,H,W) or None (= zero).  The tensors must stay alive until the calls
-    that use the struct have been enqueued; the contiguous copies are kept on the struct."""
-    x = AuxArgs()
-    x.mode = aux_mode(mode)
-    keep = []
-    for name, t in (("dL_ddepth", dL_ddepth), ("dL_dalpha", dL_dalpha)):
-        if t is not None:
-            t = _dev_f32(t, device, name)
-            keep.append(t)
-        setattr(x, name, _ptr(t))
-    x.scratch = _ptr(scratch)
-    x._keep = keep
-    return x
-
-
-def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, opacity, scales, rotations, scale_modifier,
-                                    cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                                    degree, campos, prefiltered, debug, *, antialiasing=False):
-    """rasterize_gaussians() with the depth and alpha maps of mode `depth_alpha` ("depth" / "invdepth") from the same blend pass
-    -> (num_rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, depth (1,H,W), alpha (1,H,W), auxBuffer).
-    Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s (with the same `antialiasing`)."""
-    mode = aux_mode(depth_alpha)
-    aa = aa_flag(antialiasing)
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    if not means3D.is_cuda:
-        raise RuntimeError("means3D must be a HIP (cuda) tensor; the HIP rasterizer has no CPU path")
-    L = _aux_lib()
-    dev = means3D.device
-    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
-    means3D = _dev_f32(means3D, dev, "means3D")
-    background = _dev_f32(background, dev, "bg")
-    colors, opacity, scales, rotations, cov3D_precomp, sh = (
-        _dev_f32(t, dev, n) for t, n in ((colors, "colors_precomp"), (opacity, "opacities"), (scales, "scales"),
-                                         (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"), (sh, "shs")))
-    viewmatrix, projmatrix, campos = (_dev_f32(t, dev, n) for t, n in ((viewmatrix, "viewmatrix"),
-                                                                        (projmatrix, "projmatrix"), (campos, "campos")))
-    byte = dict(dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        out_color = torch.zeros((3, H, W), dtype=torch.float32, device=dev) if P == 0 else \
-            torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        if P == 0:
-            e = torch.empty((0,), **byte)
-            _, depth, alpha, scratch = aux_forward_args(mode, 0, 0, W, H, dev)
-            return 0, out_color, radii, e, e.clone(), e.clone(), depth, alpha, scratch
-        M = int(sh.size(1)) if sh.numel() != 0 else 0
-        geom = torch.empty((L.gsr_geometry_bytes(P),), **byte)
-        img = torch.empty((L.gsr_image_bytes(W, H),), **byte)
-        R = _i64(0)
-        stream = _stream(dev)
-        pre = AuxArgs()
-        pre.mode = mode
-        fn = (L.gsr_forward_preprocess_aux,) if not aa else (_aa_lib().gsr_forward_preprocess_aa, 1)
-        _check(fn[0](*fn[1:], ctypes.byref(pre), P, int(degree), M, W, H, _ptr(means3D), _ptr(sh), _ptr(colors),
-                     _ptr(opacity), _ptr(scales), float(scale_modifier), _ptr(rotations),
-                     _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
-                     float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), _ptr(radii), _ptr(geom),
-                     ctypes.byref(R), stream, _dbg(debug)))
-        R = int(R.value)
-        binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
-        x, depth, alpha, scratch = aux_forward_args(mode, P, R, W, H, dev)
-        _check(L.gsr_forward_render_aux(ctypes.byref(x), P, R, W, H, _ptr(background), _ptr(radii), _ptr(geom), _ptr(binning),
-                                        _ptr(img), _ptr(out_color), stream, _dbg(debug)))
-    return R, out_color, radii, geom, binning, img, depth, alpha, scratch
-
-
-def backward_blend_aux(a, x):
-    _check(_aux_lib().gsr_backward_blend_aux(ctypes.byref(a), ctypes.byref(x)))
-
-
-def backward_gaussians_aux(a, x, first, count, out_row0=0):
-    _check(_aux_lib().gsr_backward_gaussians_aux(ctypes.byref(a), ctypes.byref(x), int(first), int(count), int(out_row0)))
-
-
-def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
-                                             cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
-                                             degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
-                                             dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None):
-    """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
-    top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
-    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities: as there."""
-    aa = aa_flag(antialiasing)
-    if aa and opacities is None:
-        raise RuntimeError("rasterize_gaussians_backward_depth_alpha: antialiasing=True needs the forward's opacities")
-    L = _aux_lib()
-    dev = means3D.device
-    P = int(means3D.size(0))
-    H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
-    M = int(sh.size(1)) if sh.numel() != 0 else 0
-    f32 = dict(dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        alloc = torch.zeros if P == 0 else torch.empty
-        none = torch.empty((0,), **f32)
-        dL_dmeans3D, dL_dmeans2D = alloc((P, 3), **f32), alloc((P, 3), **f32)
-        dL_dcolors = alloc((P, 3), **f32) if colors.numel() != 0 else none
-        dL_dopacity = alloc((P, 1), **f32)
-        dL_dcov3D = alloc((P, 6), **f32) if cov3D_precomp.numel() != 0 else none
-        dL_dsh = alloc((P, M, 3), **f32)
-        dL_dscales, dL_drotations = alloc((P, 3), **f32), alloc((P, 4), **f32)
-        if P != 0:
-            means3D = _dev_f32(means3D, dev, "means3D")
-            dL_dout_color = _dev_f32(dL_dout_color, dev, "dL_dout_color")
-            background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix, projmatrix, campos = (
-                _dev_f32(t, dev, "input") for t in (background, colors, scales, rotations, cov3D_precomp, sh, viewmatrix,
-                                                    projmatrix, campos))
-            scratch = torch.empty((L.gsr_backward_scratch_bytes(P, int(R)),), dtype=torch.uint8, device=dev)
-            a = backward_args(P=P, D=int(degree), M=M, R=int(R), W=W, H=H, leaf=0, background=background, means3D=means3D,
-                              shs=sh, colors_precomp=colors, scales=scales, scale_modifier=scale_modifier,
-                              rotations=rotations, cov3D_precomp=cov3D_precomp, viewmatrix=viewmatrix,
-                              projmatrix=projmatrix, cam_pos=campos, tan_fovx=tan_fovx, tan_fovy=tan_fovy, radii=radii,
-                              geometry=geomBuffer, binning=binningBuffer, image=imageBuffer, scratch=scratch,
-                              dL_dpix=dL_dout_color, debug=debug, device=dev)
-            set_backward_outputs(a, dL_dmean2D=dL_dmeans2D, dL_dconic=None, dL_dopacity=dL_dopacity, dL_dcolor=dL_dcolors,
-                                 dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh, dL_dscale=dL_dscales,
-                                 dL_drot=dL_drotations)
-            set_backward_stats(a, stats, P, dev)
-            x = aux_backward_args(depth_alpha, auxBuffer, dL_ddepth, dL_dalpha, dev)
-            backward_blend_aux(a, x)
-            if aa:
-                opacities = _dev_f32(opacities, dev, "opacities")
-                backward_gaussians_aa(a, opacities, x, 0, P, 0)
-            else:
-                backward_gaussians_aux(a, x, 0, P, 0)
-            scratch.record_stream(torch.cuda.current_stream(dev))
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
-
-
-# ---- anti-aliased rendering (include/gsr_aa.h; opt-in, kernels of their own) ------------------------------------------------
-def aa_flag(antialiasing):
-    """The `antialiasing` keyword -> bool; anything but a bool raises TypeError (a mode string or a number is not a switch here)."""
-    if not isinstance(antialiasing, bool):
-        raise TypeError(f"antialiasing must be True or False, got {antialiasing!r}")
-    return antialiasing
-
-
-def _aa_lib():
-    L = _aux_lib()
-    if not getattr(L, "_gsr_aa_bound", False):
-        pa = ctypes.POINTER(AuxArgs)
-        L.gsr_forward_preprocess_aa.restype = _i
-        L.gsr_forward_preprocess_aa.argtypes = [_i, pa] + list(L.gsr_forward_preprocess.argtypes)
-        L.gsr_forward_preprocess_leaf_aa.restype = _i
-        L.gsr_forward_preprocess_leaf_aa.argtypes = [_i] + list(L.gsr_forward_preprocess_leaf_aux.argtypes)
-        L.gsr_backward_gaussians_aa.restype = _i
-        L.gsr_backward_gaussians_aa.argtypes = [ctypes.POINTER(BackwardArgs), _i, _vp, pa, _i, _i, _i]
-        L._gsr_aa_bound = True
-    return L
-
-
-def backward_gaussians_aa(a, opacities, x, first, count, out_row0=0):
-    """gsr_backward_gaussians_aa with the filter on: `opacities` is the forward's opacity input (tensor or address; the logits in leaf
-    mode), `x` the AuxArgs of a depth-and-alpha backward or None."""
-    addr = opacities if isinstance(opacities, int) else _ptr(opacities)
-    _check(_aa_lib().gsr_backward_gaussians_aa(ctypes.byref(a), 1, addr, None if x is None else ctypes.byref(x), int(first), int(count),
-                                               int(out_row0)))

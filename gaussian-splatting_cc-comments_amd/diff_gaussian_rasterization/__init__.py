@@ -24,17 +24,27 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         raster_settings, densify_stats=None, antialiasing=False):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors and the screen-space filter, see
     GaussianRasterizer)"""
-    if _C.aa_flag(antialiasing):
-        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                         cov3Ds_precomp, raster_settings, densify_stats, True)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, densify_stats)
+                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None)
+
+
+def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                    raster_settings, depth_alpha, densify_stats=None, antialiasing=False):
+    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
+    _C.aux_mode(depth_alpha)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
+    """The reference's Function, plus (depth_alpha = "depth" / "invdepth") two differentiable per-pixel outputs from the same blend pass
+    (include/gsr_aux.h): depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term)
+    and alpha A = 1 - T_final.  Colour and radii are bit-identical with and without the maps.  When neither map's gradient reaches the
+    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True)."""
+
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, densify_stats=None, antialiasing=False):
+                raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None):
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
         args = (
             raster_settings.bg,
@@ -59,7 +69,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         )
         # the screen-space filter (include/gsr_aa.h): a keyword of the binding, so the debug snapshot holds the same tuple
         kw = {"antialiasing": True} if antialiasing else {}
-        if raster_settings.debug:  # reference __init__.py:87-94
+        maps = ()
+        if depth_alpha is not None:
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *maps = \
+                _C.rasterize_gaussians_depth_alpha(depth_alpha, *args, **kw)
+        elif raster_settings.debug:  # reference __init__.py:87-94
             cpu_args = cpu_deep_copy_tuple(args)
             try:
                 num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args, **kw)
@@ -73,25 +87,27 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
         ctx.num_rendered = num_rendered
-        ctx.antialiasing = bool(antialiasing)
-        # the anti-aliased backward reads the opacity input (the records hold opacity * rho): saved on that path only
+        ctx.antialiasing = antialiasing
+        ctx.depth_alpha = depth_alpha
+        # after the reference's ten: the aux state of the maps, and the opacity input that the anti-aliased backward reads (the records
+        # hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *((opacities,) if antialiasing else ()))
+                              binningBuffer, imgBuffer, *maps[2:], *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
         ctx.set_materialize_grads(False)
-        return color, radii
+        return (color, radii, *maps[:2])
 
     @staticmethod
-    def backward(ctx, grad_out_color, _):
+    def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
         num_rendered = ctx.num_rendered
         raster_settings = ctx.raster_settings
+        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
+         imgBuffer, *extra) = ctx.saved_tensors
         if grad_out_color is None:  # the image took no part in the loss: the zero gradient autograd would have materialised
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
-                                         dtype=torch.float32, device=ctx.saved_tensors[1].device)
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors[:10]
-        kw = {"antialiasing": True, "opacities": ctx.saved_tensors[10]} if ctx.antialiasing else {}
+                                         dtype=torch.float32, device=means3D.device)
+        kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
@@ -117,99 +133,30 @@ class _RasterizeGaussians(torch.autograd.Function):
             imgBuffer,
             raster_settings.debug,
         )
-        if raster_settings.debug:  # reference __init__.py:141-148
+        if grad_depth is not None or grad_alpha is not None:
+            hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
+            grads = _C.rasterize_gaussians_backward_depth_alpha(ctx.depth_alpha, *args[:-1], extra[0], hw(grad_depth), hw(grad_alpha),
+                                                                raster_settings.debug, stats=ctx.densify_stats, **kw)
+        elif raster_settings.debug and ctx.depth_alpha is None:  # reference __init__.py:141-148
             cpu_args = cpu_deep_copy_tuple(args)
             try:
-                (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-                 grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
+                grads = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_bw.dump")
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                 raise ex
         else:
-            # gradients of inputs that were not provided have no consumer below: the binding skips them
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = _C.rasterize_gaussians_backward(*args, lean=True, stats=ctx.densify_stats, **kw)
+            # gradients of inputs that were not provided have no consumer below: the binding skips them.  (Neither map in the loss:
+            # the default backward kernels, at the default cost.)
+            grads = _C.rasterize_gaussians_backward(*args, lean=not raster_settings.debug, stats=ctx.densify_stats, **kw)
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations) = grads
 
         # gradient order: reference __init__.py:154-164
-        grads = (
-            grad_means3D,
-            grad_means2D,
-            grad_sh if (sh.numel() != 0 and grad_sh is not None) else None,
-            grad_colors_precomp if colors_precomp.numel() != 0 else None,
-            grad_opacities,
-            grad_scales if scales.numel() != 0 else None,
-            grad_rotations if rotations.numel() != 0 else None,
-            grad_cov3Ds_precomp if cov3Ds_precomp.numel() != 0 else None,
-            None,
-            None,
-        )
-        return grads + ((None,) if ctx.antialiasing else ())
-
-
-def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                    raster_settings, depth_alpha, densify_stats=None, antialiasing=False):
-    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
-    _C.aux_mode(depth_alpha)
-    return _RasterizeGaussiansDepthAlpha.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                               cov3Ds_precomp, raster_settings, depth_alpha, densify_stats,
-                                               _C.aa_flag(antialiasing))
-
-
-class _RasterizeGaussiansDepthAlpha(torch.autograd.Function):
-    """_RasterizeGaussians plus two differentiable per-pixel outputs from the same blend pass (include/gsr.h gsr_aux_args):
-    depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term) and alpha
-    A = 1 - T_final.  Colour and radii are bit-identical with _RasterizeGaussians'.  When neither map's gradient reaches the
-    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                depth_alpha, densify_stats=None, antialiasing=False):
-        st = raster_settings
-        (num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, depth, alpha, auxBuffer) = \
-            _C.rasterize_gaussians_depth_alpha(depth_alpha, st.bg, means3D, colors_precomp, opacities, scales, rotations,
-                                               st.scale_modifier, cov3Ds_precomp, st.viewmatrix, st.projmatrix, st.tanfovx,
-                                               st.tanfovy, st.image_height, st.image_width, sh, st.sh_degree, st.campos,
-                                               st.prefiltered, st.debug, antialiasing=antialiasing)
-        ctx.raster_settings = raster_settings
-        ctx.depth_alpha = depth_alpha
-        ctx.densify_stats = densify_stats
-        ctx.num_rendered = num_rendered
-        ctx.antialiasing = antialiasing
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, auxBuffer, *((opacities,) if antialiasing else ()))
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _, grad_depth, grad_alpha):
-        st = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer, imgBuffer,
-         auxBuffer) = ctx.saved_tensors[:11]
-        kw = {"antialiasing": True, "opacities": ctx.saved_tensors[11]} if ctx.antialiasing else {}
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32,
-                                         device=means3D.device)
-        if grad_depth is None and grad_alpha is None:
-            # neither map takes part in the loss: the default backward kernels, at the default cost
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-             grad_rotations) = _C.rasterize_gaussians_backward(
-                st.bg, means3D, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp, st.viewmatrix,
-                st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
-                ctx.num_rendered, binningBuffer, imgBuffer, st.debug, lean=not st.debug, stats=ctx.densify_stats, **kw)
-        else:
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-             grad_rotations) = _C.rasterize_gaussians_backward_depth_alpha(
-                ctx.depth_alpha, st.bg, means3D, radii, colors_precomp, scales, rotations, st.scale_modifier, cov3Ds_precomp,
-                st.viewmatrix, st.projmatrix, st.tanfovx, st.tanfovy, grad_out_color, sh, st.sh_degree, st.campos, geomBuffer,
-                ctx.num_rendered, binningBuffer, imgBuffer, auxBuffer,
-                None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
-                None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), st.debug, stats=ctx.densify_stats, **kw)
         return (
             grad_means3D,
             grad_means2D,
-            grad_sh if sh.numel() != 0 else None,
+            grad_sh if (sh.numel() != 0 and grad_sh is not None) else None,
             grad_colors_precomp if colors_precomp.numel() != 0 else None,
             grad_opacities,
             grad_scales if scales.numel() != 0 else None,
@@ -247,8 +194,7 @@ class GaussianRasterizer(nn.Module):
 
     depth_alpha (extension, optional): "depth" or "invdepth" -- forward() then returns (color, radii, depth, alpha) with the
     depth map D = sum_i v_i alpha_i T_i (v_i = view-space z_i, or 1 / z_i; 0 where nothing blends) and the alpha map
-    A = 1 - T_final, both (1, H, W) and differentiable, accumulated in the same blend pass as the colour
-    (_RasterizeGaussiansDepthAlpha).  Expected depth is D / A.
+    A = 1 - T_final, both (1, H, W) and differentiable, accumulated in the same blend pass as the colour.  Expected depth is D / A.
 
     antialiasing (extension, default False): upstream's `antialiasing=True`, the screen-space filter of Mip-Splatting.  The projected
     covariance keeps its 0.3 px^2 dilation, and the opacity is scaled by rho = sqrt(max(2.5e-5, det(Sigma) / det(Sigma + 0.3 I))), so a

@@ -20,7 +20,7 @@ import torch
 
 from diff_gaussian_rasterization import _C
 
-_vp, _i, _i64, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+_vp, _i64, _d = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
 ADAM_MAX_GROUPS = 8
 
 
@@ -30,74 +30,40 @@ class AdamGroup(ctypes.Structure):
                 ("lr", _d), ("row", ctypes.c_int32)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_leaf_bound", False):
-        L.gsr_forward_preprocess_leaf.restype = _i
-        L.gsr_forward_preprocess_leaf.argtypes = [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp,
-                                                                                           ctypes.POINTER(_i64), _vp, _i]
-        L.gsr_backward_leaf.restype = _i
-        L.gsr_backward_leaf.argtypes = [_i, _i, _i, _i64, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f] + [_vp] * 15 + [_i]
-        L.gsr_adam_step.restype = _i
-        L.gsr_adam_step.argtypes = [_i, ctypes.POINTER(AdamGroup), _d, _d, _d, _vp, _vp]
-        L._gsr_leaf_bound = True
-    return L
-
-
-def _f32(t, dev, what):
-    if not t.is_cuda or t.device != dev:
-        raise RuntimeError(f"{what} must be a HIP (cuda) tensor on {dev}; leaf mode has no CPU path")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{what} must be float32 (got {t.dtype})")
-    return t.contiguous()
+def _leaf_forward(mode, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing):
+    st = raster_settings
+    P = int(xyz.size(0))
+    M = 1 + (int(features_rest.size(1)) if features_rest.numel() else 0)
+    if features_dc.shape != (P, 1, 3) or (M > 1 and features_rest.shape != (P, M - 1, 3)):
+        raise RuntimeError(f"features_dc must be (P,1,3) and features_rest (P,M-1,3); got {tuple(features_dc.shape)}, "
+                           f"{tuple(features_rest.shape)}")
+    R, color, radii, geom, binning, img, (xyz, features_dc, features_rest, _, scaling, rotation, *_), maps = _C.run_forward(
+        True, mode, antialiasing, st.bg,
+        ((xyz, "xyz"), (features_dc, "features_dc"), (features_rest, "features_rest"), (opacity, "opacity"), (scaling, "scaling"),
+         (rotation, "rotation"), (st.viewmatrix, "viewmatrix"), (st.projmatrix, "projmatrix"), (st.campos, "campos")),
+        st.sh_degree, M, st.image_width, st.image_height, st.scale_modifier, st.tanfovx, st.tanfovy, st.prefiltered, st.debug)
+    return (R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps)
 
 
 def leaf_forward(xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing=False):
     """Forward from the raw leaves -> (num_rendered, color, radii, geom, binning, img, M, contiguous inputs).
     antialiasing: the screen-space filter (include/gsr_aa.h)."""
-    if xyz.ndimension() != 2 or xyz.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    L = _lib()
-    dev = xyz.device
-    st = raster_settings
-    P, H, W = int(xyz.size(0)), int(st.image_height), int(st.image_width)
-    xyz, features_dc, opacity, scaling, rotation = (_f32(t, dev, n) for t, n in (
-        (xyz, "xyz"), (features_dc, "features_dc"), (opacity, "opacity"), (scaling, "scaling"), (rotation, "rotation")))
-    M = 1 + (int(features_rest.size(1)) if features_rest.numel() else 0)
-    if features_dc.shape != (P, 1, 3) or (M > 1 and features_rest.shape != (P, M - 1, 3)):
-        raise RuntimeError(f"features_dc must be (P,1,3) and features_rest (P,M-1,3); got {tuple(features_dc.shape)}, "
-                           f"{tuple(features_rest.shape)}")
-    features_rest = _f32(features_rest, dev, "features_rest") if M > 1 else features_rest
-    bg, view, proj, campos = (_f32(t, dev, n) for t, n in ((st.bg, "bg"), (st.viewmatrix, "viewmatrix"),
-                                                           (st.projmatrix, "projmatrix"), (st.campos, "campos")))
-    byte = dict(dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        color = (torch.zeros if P == 0 else torch.empty)((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty((L.gsr_geometry_bytes(P) if P else 0,), **byte)
-        img = torch.empty((L.gsr_image_bytes(W, H) if P else 0,), **byte)
-        binning = torch.empty((0,), **byte)
-        R = 0
-        if P:
-            Rv = _i64(0)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            pre = (L.gsr_forward_preprocess_leaf,) if not antialiasing else (_C._aa_lib().gsr_forward_preprocess_leaf_aa, 1, None)
-            _C._check(pre[0](
-                *pre[1:], P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
-                opacity.data_ptr(), scaling.data_ptr(), float(st.scale_modifier), rotation.data_ptr(), view.data_ptr(),
-                proj.data_ptr(), campos.data_ptr(), float(st.tanfovx), float(st.tanfovy), int(bool(st.prefiltered)),
-                radii.data_ptr(), geom.data_ptr(), ctypes.byref(Rv), stream, _C._dbg(st.debug)))
-            R = int(Rv.value)
-            binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
-            _C._check(L.gsr_forward_render(P, R, W, H, bg.data_ptr(), radii.data_ptr(), geom.data_ptr(), _C._ptr(binning),
-                                           img.data_ptr(), color.data_ptr(), stream, _C._dbg(st.debug)))
-    return R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation)
+    return _leaf_forward(None, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing)
+
+
+def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                             antialiasing=False):
+    """leaf_forward() with the depth and alpha maps (include/gsr_aux.h) -> (num_rendered, color, radii, geom, binning,
+    img, M, contiguous inputs, depth (1,H,W), alpha (1,H,W), aux scratch)."""
+    return _leaf_forward(_C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
+                         antialiasing)
 
 
 def leaf_backward_args(st, R, M, xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, scratch, grad_color):
     """gsr_backward_args (leaf = 1) for a state produced by leaf_forward(); gradient pointers still unset."""
     dev = xyz.device
-    bg, view, proj, campos = (_f32(t, dev, "settings") for t in (st.bg, st.viewmatrix, st.projmatrix, st.campos))
+    bg, view, proj, campos = (_C._dev_f32(t, dev, n) for t, n in ((st.bg, "bg"), (st.viewmatrix, "viewmatrix"),
+                                                                  (st.projmatrix, "projmatrix"), (st.campos, "campos")))
     a = _C.backward_args(P=int(xyz.size(0)), D=int(st.sh_degree), M=M, R=R, W=int(st.image_width), H=int(st.image_height), leaf=1,
                          background=bg, means3D=xyz, shs=features_dc, shs_rest=features_rest, scales=scaling,
                          scale_modifier=st.scale_modifier, rotations=rotation, viewmatrix=view, projmatrix=proj, cam_pos=campos,
@@ -109,28 +75,31 @@ def leaf_backward_args(st, R, M, xyz, features_dc, features_rest, scaling, rotat
 
 class _RasterizeLeafGaussians(torch.autograd.Function):
     """(xyz, means2D, _features_dc, _features_rest, _opacity, _scaling, _rotation) -> (color, radii); the same
-    contract as diff_gaussian_rasterization._RasterizeGaussians with the activations folded in.
+    contract as diff_gaussian_rasterization._RasterizeGaussians with the activations folded in, its depth and alpha maps included:
+    with depth_alpha -> (color, radii, depth (1,H,W), alpha (1,H,W)); without gradients for either map the default backward kernels run.
     `stats` (optional): (xyz_gradient_accum, denom, max_radii2D) float32 [P] tensors updated in place by the
     backward for the Gaussians visible in this view (train.py:157-159, gaussian_model.py:599-602)."""
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                antialiasing=False):
-        R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation) = leaf_forward(
-            xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing)
-        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.antialiasing = raster_settings, R, M, stats, antialiasing
-        # the anti-aliased backward reads the opacity logits (the records hold sigmoid(logit) * rho): saved on that path only
-        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
+                depth_alpha=None, antialiasing=False):
+        R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps = _leaf_forward(
+            None if depth_alpha is None else _C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation,
+            raster_settings, antialiasing)
+        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
+        ctx.antialiasing = antialiasing
+        # after the state: the aux state of the maps, and the opacity logits that the anti-aliased backward reads (the records hold
+        # sigmoid(logit) * rho), each saved on its path only
+        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *maps[2:],
                               *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
-        return color, radii
+        return (color, radii, *maps[:2])
 
     @staticmethod
-    def backward(ctx, grad_color, _):
-        L = _lib()
+    def backward(ctx, grad_color, _, grad_depth=None, grad_alpha=None):
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
-        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img = ctx.saved_tensors[:9]
+        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *extra = ctx.saved_tensors
         dev = xyz.device
         if grad_color is None:
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
@@ -142,128 +111,18 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             d_dc, d_rest = alloc((P, 1, 3), **f32), alloc((P, M - 1, 3), **f32)
             d_opacity, d_scaling, d_rotation = alloc((P, 1), **f32), alloc((P, 3), **f32), alloc((P, 4), **f32)
             if P:
-                grad_color = _f32(grad_color, dev, "dL_dout_color")
-                scratch = torch.empty((L.gsr_backward_scratch_bytes(P, R),), dtype=torch.uint8, device=dev)
+                grad_color = _C._dev_f32(grad_color, dev, "dL_dout_color")
+                scratch = _C.backward_scratch(P, R, dev)
                 a = leaf_backward_args(st, R, M, xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
                                        scratch, grad_color)
                 _C.set_backward_outputs(a, dL_dmean2D=d_means2D, dL_dmean3D=d_xyz, dL_dsh=d_dc, dL_dsh_rest=d_rest,
                                         dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
                 _C.set_backward_stats(a, ctx.stats, P, dev)
-                _C.backward_blend(a)
-                if ctx.antialiasing:
-                    _C.backward_gaussians_aa(a, _f32(ctx.saved_tensors[9], dev, "opacity"), None, 0, P, 0)
-                else:
-                    _C.backward_gaussians(a, 0, P, 0)
-                scratch.record_stream(torch.cuda.current_stream(dev))
-        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None
-
-
-def leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                             antialiasing=False):
-    """leaf_forward() with the depth and alpha maps (include/gsr.h gsr_aux_args) -> (num_rendered, color, radii, geom, binning,
-    img, M, contiguous inputs, depth (1,H,W), alpha (1,H,W), aux scratch)."""
-    mode = _C.aux_mode(depth_alpha)
-    if xyz.ndimension() != 2 or xyz.size(1) != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
-    L = _C._aux_lib()
-    _lib()
-    dev = xyz.device
-    st = raster_settings
-    P, H, W = int(xyz.size(0)), int(st.image_height), int(st.image_width)
-    xyz, features_dc, opacity, scaling, rotation = (_f32(t, dev, n) for t, n in (
-        (xyz, "xyz"), (features_dc, "features_dc"), (opacity, "opacity"), (scaling, "scaling"), (rotation, "rotation")))
-    M = 1 + (int(features_rest.size(1)) if features_rest.numel() else 0)
-    if features_dc.shape != (P, 1, 3) or (M > 1 and features_rest.shape != (P, M - 1, 3)):
-        raise RuntimeError(f"features_dc must be (P,1,3) and features_rest (P,M-1,3); got {tuple(features_dc.shape)}, "
-                           f"{tuple(features_rest.shape)}")
-    features_rest = _f32(features_rest, dev, "features_rest") if M > 1 else features_rest
-    bg, view, proj, campos = (_f32(t, dev, n) for t, n in ((st.bg, "bg"), (st.viewmatrix, "viewmatrix"),
-                                                           (st.projmatrix, "projmatrix"), (st.campos, "campos")))
-    byte = dict(dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        color = (torch.zeros if P == 0 else torch.empty)((3, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        geom = torch.empty((L.gsr_geometry_bytes(P) if P else 0,), **byte)
-        img = torch.empty((L.gsr_image_bytes(W, H) if P else 0,), **byte)
-        binning = torch.empty((0,), **byte)
-        R = 0
-        x, depth, alpha, aux = _C.aux_forward_args(mode, 0, 0, W, H, dev)
-        if P:
-            Rv = _i64(0)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            pre = _C.AuxArgs()
-            pre.mode = mode
-            fn = (L.gsr_forward_preprocess_leaf_aux,) if not antialiasing else (_C._aa_lib().gsr_forward_preprocess_leaf_aa, 1)
-            _C._check(fn[0](
-                *fn[1:], ctypes.byref(pre), P, int(st.sh_degree), M, W, H, xyz.data_ptr(), features_dc.data_ptr(), _C._ptr(features_rest),
-                opacity.data_ptr(), scaling.data_ptr(), float(st.scale_modifier), rotation.data_ptr(), view.data_ptr(),
-                proj.data_ptr(), campos.data_ptr(), float(st.tanfovx), float(st.tanfovy), int(bool(st.prefiltered)),
-                radii.data_ptr(), geom.data_ptr(), ctypes.byref(Rv), stream, _C._dbg(st.debug)))
-            R = int(Rv.value)
-            binning = torch.empty((L.gsr_binning_bytes(P, R, W, H),), **byte)
-            x, depth, alpha, aux = _C.aux_forward_args(mode, P, R, W, H, dev)
-            _C._check(L.gsr_forward_render_aux(ctypes.byref(x), P, R, W, H, bg.data_ptr(), radii.data_ptr(), geom.data_ptr(),
-                                               _C._ptr(binning), img.data_ptr(), color.data_ptr(), stream, _C._dbg(st.debug)))
-    return R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), depth, alpha, aux
-
-
-class _RasterizeLeafGaussiansDepthAlpha(torch.autograd.Function):
-    """_RasterizeLeafGaussians plus the depth and alpha maps of diff_gaussian_rasterization._RasterizeGaussiansDepthAlpha:
-    -> (color, radii, depth (1,H,W), alpha (1,H,W)).  Without gradients for either map the default backward kernels run."""
-
-    @staticmethod
-    def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, depth_alpha, stats=None,
-                antialiasing=False):
-        R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), depth, alpha, aux = \
-            leaf_forward_depth_alpha(depth_alpha, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                                     antialiasing)
-        ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
-        ctx.antialiasing = antialiasing
-        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux,
-                              *((opacity,) if antialiasing else ()))
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)
-        return color, radii, depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_color, _, grad_depth, grad_alpha):
-        L = _lib()
-        st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
-        xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, aux = ctx.saved_tensors[:10]
-        dev = xyz.device
-        if grad_color is None:
-            grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
-        use_aux = grad_depth is not None or grad_alpha is not None
-        P = int(xyz.size(0))
-        f32 = dict(dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            alloc = torch.zeros if P == 0 else torch.empty
-            d_means2D, d_xyz = alloc((P, 3), **f32), alloc((P, 3), **f32)
-            d_dc, d_rest = alloc((P, 1, 3), **f32), alloc((P, M - 1, 3), **f32)
-            d_opacity, d_scaling, d_rotation = alloc((P, 1), **f32), alloc((P, 3), **f32), alloc((P, 4), **f32)
-            if P:
-                grad_color = _f32(grad_color, dev, "dL_dout_color")
-                scratch = torch.empty((L.gsr_backward_scratch_bytes(P, R),), dtype=torch.uint8, device=dev)
-                a = leaf_backward_args(st, R, M, xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
-                                       scratch, grad_color)
-                _C.set_backward_outputs(a, dL_dmean2D=d_means2D, dL_dmean3D=d_xyz, dL_dsh=d_dc, dL_dsh_rest=d_rest,
-                                        dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
-                _C.set_backward_stats(a, ctx.stats, P, dev)
-                if use_aux:
-                    x = _C.aux_backward_args(ctx.depth_alpha, aux,
-                                             None if grad_depth is None else grad_depth.reshape(grad_depth.shape[-2:]),
-                                             None if grad_alpha is None else grad_alpha.reshape(grad_alpha.shape[-2:]), dev)
-                    _C.backward_blend_aux(a, x)
-                else:
-                    x = None
-                    _C.backward_blend(a)
-                if ctx.antialiasing:
-                    _C.backward_gaussians_aa(a, _f32(ctx.saved_tensors[10], dev, "opacity"), x, 0, P, 0)
-                elif use_aux:
-                    _C.backward_gaussians_aux(a, x, 0, P, 0)
-                else:
-                    _C.backward_gaussians(a, 0, P, 0)
-                scratch.record_stream(torch.cuda.current_stream(dev))
+                x = None
+                if grad_depth is not None or grad_alpha is not None:
+                    hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
+                    x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
+                _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None)
         return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None
 
 
@@ -277,15 +136,8 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
-        if _C.aa_flag(antialiasing):
-            return _RasterizeLeafGaussiansDepthAlpha.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                                           raster_settings, depth_alpha, stats, True)
-        return _RasterizeLeafGaussiansDepthAlpha.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation,
-                                                       raster_settings, depth_alpha, stats)
-    if _C.aa_flag(antialiasing):
-        return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings,
-                                             stats, True)
-    return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats)
+    return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats,
+                                         depth_alpha, _C.aa_flag(antialiasing))
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -331,7 +183,7 @@ class FusedAdam(torch.optim.Optimizer):
                 key = (p.device, tuple(float(b) for b in group["betas"]), float(group["eps"]))
                 batches.setdefault(key, []).append(AdamGroup(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step,
                                                              float(group["lr"]), row))
-        L = _lib()
+        L = _C.lib()
         for (dev, betas, eps), groups in batches.items():
             radii_ptr = None
             if visible_radii is not None:

@@ -217,28 +217,23 @@ class _RasterizeViewParallel(torch.autograd.Function):
         with torch.cuda.device(dev):
             d_means2D = torch.empty((P, 3), dtype=torch.float32, device=dev)
             ex.begin_step()
-            tensors = [_C._dev_f32(t, dev, "input") for t in (means3D, shs, scales, rotations, grad_color, st.bg, st.viewmatrix,
-                                                             st.projmatrix, st.campos)]
-            means3D_c, shs_c, scales_c, rot_c, dpix, bg, view, proj, campos = tensors
-            scratch = torch.empty((_C.lib().gsr_backward_scratch_bytes(P, int(R)),), dtype=torch.uint8, device=dev)
+            means3D_c, shs_c, scales_c, rot_c, dpix, bg, view, proj, campos = (_C._dev_f32(t, dev, n) for t, n in (
+                (means3D, "means3D"), (shs, "shs"), (scales, "scales"), (rotations, "rotations"), (grad_color, "dL_dout_color"),
+                (st.bg, "bg"), (st.viewmatrix, "viewmatrix"), (st.projmatrix, "projmatrix"), (st.campos, "campos")))
+            scratch = _C.backward_scratch(P, R, dev)
             a = _C.backward_args(P=P, D=int(st.sh_degree), M=M, R=int(R), W=int(st.image_width), H=int(st.image_height), leaf=0,
                                  background=bg, means3D=means3D_c, shs=shs_c, scales=scales_c, scale_modifier=st.scale_modifier,
                                  rotations=rot_c, viewmatrix=view, projmatrix=proj, cam_pos=campos, tan_fovx=st.tanfovx,
                                  tan_fovy=st.tanfovy, radii=radii, geometry=geom, binning=binning, image=img, scratch=scratch,
                                  dL_dpix=dpix, debug=st.debug, device=dev)
             _C.set_backward_stats(a, ctx.stats, P, dev)
-            # required by the C ABI even when the part buffers are set below (validation happens per call)
-            _C.set_backward_outputs(a, dL_dmean2D=d_means2D, **ex.output_pointers(0))
-            _C.backward_blend(a)
-            opac = _C._dev_f32(ctx.saved_tensors[8], dev, "opacities") if ctx.antialiasing else None
-            for k, (first, count) in enumerate(ex.ranges):
-                _C.set_backward_outputs(a, dL_dmean2D=d_means2D.data_ptr() + first * 12, **ex.output_pointers(k))
-                if opac is not None:
-                    _C.backward_gaussians_aa(a, opac, None, first, count, first)
-                else:
-                    _C.backward_gaussians(a, first, count, first)
-                ex.submit(k, campos)   # part k's collectives run while part k+1 computes
-            scratch.record_stream(torch.cuda.current_stream(dev))
+
+            def part_outputs(k):   # where part k's rows go: its exchange buffers, and its rows of this view's own dL_dmeans2D
+                _C.set_backward_outputs(a, dL_dmean2D=d_means2D.data_ptr() + ex.ranges[k][0] * 12, **ex.output_pointers(k))
+            part_outputs(0)   # required by the C ABI for the blend pass too (validation happens per call)
+            # part k's collectives run while part k+1 computes
+            _C.run_backward(a, scratch, dev, None, ctx.saved_tensors[8] if ctx.antialiasing else None, ex.ranges, part_outputs,
+                            lambda k: ex.submit(k, campos))
             g = ex.finish(means3D_c.detach(), int(st.sh_degree))
         return g["dL_dmean3D"], d_means2D, g["dL_dsh"], g["dL_dopacity"], g["dL_dscale"], g["dL_drot"], None, None, None, None
 
@@ -250,10 +245,8 @@ def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations,
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
     DensificationStats.kernel_tensors()).  antialiasing: the screen-space filter of GaussianRasterizer(..., antialiasing=True)."""
     from diff_gaussian_rasterization import _C
-    if _C.aa_flag(antialiasing):
-        return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
-                                            True)
-    return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats)
+    return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
+                                        _C.aa_flag(antialiasing))
 
 
 def exchange_sh_gradient(means3D: torch.Tensor, campos: torch.Tensor, dL_dRGB: torch.Tensor, sh_degree: int,
@@ -352,7 +345,7 @@ class ViewsInFlight:
     another stream fills both: its stage 1 and binning run under the first view's blend kernels.  Views are independent until
     their gradients are added (train.py:105-119 renders one view per step), and PyTorch's autograd adds them into
     the parameters' .grad in the order of the backward calls -- the order of the sequential loop -- so the accumulated gradients
-    are bit for bit those of rendering the views one after the other (tests/test_boundary_gpu.py).
+    are bit for bit those of rendering the views one after the other (pinned by the views-in-flight test of the GPU suite).
 
         vif = ViewsInFlight(device, in_flight=2)
         vif.forward_backward(render_fns, upstream_grads)      # render_fns[v]() -> image of view v (calls the rasterizer)
