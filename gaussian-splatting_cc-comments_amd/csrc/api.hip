@@ -91,15 +91,9 @@ static ProfRecorder* prof_find(hipStream_t s, bool create)
 	return r;
 }
 
-// Single-stage recording of a stage that is ONE kernel: the events its launcher hands to hipExtLaunchKernelGGL as start / stop
-// events -- the kernel's own dispatch packet takes the two timestamps, no hipEventRecord (a barrier packet that costs the
-// stream's next launch 6-8 us) stands in front of or behind it.  false: not recording this stage that way.
-bool gsr_prof_kernel_events(hipStream_t s, const char* name, hipEvent_t* a, hipEvent_t* b)
+// the next event pair of the pool, which grows when all are in use
+static ProfEntry& prof_next(ProfRecorder* r, const char* name)
 {
-	if (g_prof_active.load(std::memory_order_relaxed) == 0) return false;
-	std::lock_guard<std::mutex> lk(g_prof_mu);
-	ProfRecorder* r = prof_find(s, false);
-	if (!r || !r->on || !r->only[0] || strcmp(r->only, name) != 0) return false;
 	if (r->used == r->ev.size()) {
 		ProfEntry e;
 		e.name = name;
@@ -109,6 +103,19 @@ bool gsr_prof_kernel_events(hipStream_t s, const char* name, hipEvent_t* a, hipE
 	}
 	ProfEntry& e = r->ev[r->used++];
 	e.name = name;
+	return e;
+}
+
+// Single-stage recording of a stage that is ONE kernel: the events its launcher hands to gsr_launch as start / stop events -- the
+// kernel's own dispatch packet takes the two timestamps, no hipEventRecord stands in front of or behind it.  false: not recording
+// this stage that way.
+bool gsr_prof_kernel_events(hipStream_t s, const char* name, hipEvent_t* a, hipEvent_t* b)
+{
+	if (g_prof_active.load(std::memory_order_relaxed) == 0) return false;
+	std::lock_guard<std::mutex> lk(g_prof_mu);
+	ProfRecorder* r = prof_find(s, false);
+	if (!r || !r->on || !r->only[0] || strcmp(r->only, name) != 0) return false;
+	ProfEntry& e = prof_next(r, name);
 	r->open = false;
 	*a = e.a;
 	*b = e.b;
@@ -124,16 +131,7 @@ void gsr_prof_mark_begin(hipStream_t s, const char* name)
 	r->open = false;
 	if (r->only[0] && strcmp(r->only, name) != 0) return;
 	r->open = true;
-	if (r->used == r->ev.size()) {
-		ProfEntry e;
-		e.name = name;
-		(void)hipEventCreate(&e.a);
-		(void)hipEventCreate(&e.b);
-		r->ev.push_back(e);
-	}
-	ProfEntry& e = r->ev[r->used++];
-	e.name = name;
-	(void)hipEventRecord(e.a, s);
+	(void)hipEventRecord(prof_next(r, name).a, s);
 }
 
 void gsr_prof_mark_end(hipStream_t s)
@@ -292,18 +290,40 @@ extern "C" size_t gsr_aux_bytes(int64_t R, int W, int H)
 	gsr_aux_layout l;
 	return gsr_aux_layout_of(R, W, H, &l) == GSR_OK ? l.total : 0;
 }
-static bool gsr_aux_mode_ok(int mode) { return mode == GSR_AUX_DEPTH || mode == GSR_AUX_INVDEPTH; }
-static GsrAuxBlend gsr_aux_view(const gsr_aux_args& x, int64_t R, int W, int H)
+// what the blend launchers take: NULL without the maps, else `a` filled from the caller's arguments
+static const GsrAuxBlend* gsr_aux_view(const gsr_aux_args* x, int64_t R, int W, int H, GsrAuxBlend* a)
 {
+	if (!x) return nullptr;
 	gsr_aux_layout l;
 	gsr_aux_layout_of(R, W, H, &l);
-	char* b = (char*)x.scratch;
-	GsrAuxBlend a;
-	a.out_depth = x.out_depth; a.out_alpha = x.out_alpha;
-	a.ckpt_depth = (float*)(b + l.ckpt_depth);
-	a.final_D = (float*)(b + l.final_D);
-	a.dL_ddepth = x.dL_ddepth; a.dL_dalpha = x.dL_dalpha;
+	char* b = (char*)x->scratch;
+	a->out_depth = x->out_depth; a->out_alpha = x->out_alpha;
+	a->ckpt_depth = (float*)(b + l.ckpt_depth);
+	a->final_D = (float*)(b + l.final_D);
+	a->dL_ddepth = x->dL_ddepth; a->dL_dalpha = x->dL_dalpha;
 	return a;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// The one validity check of the option arguments (include/gsr_aux.h, include/gsr_aa.h), called once by every *_aux / *_aa entry
+// point.  antialiasing: 0 or 1 (the *_aux calls pass 0).  aux: NULL only where `optional` (the *_aa calls); its mode is always
+// checked, and beyond that what the calling stage needs of it.  live: the call has work to launch, so what it needs must be there.
+enum GsrAuxNeeds {
+	GSR_AUX_NEEDS_MODE,      // stage 1: reads nothing else
+	GSR_AUX_NEEDS_SCRATCH,   // the backward: an aligned scratch (the blend reads it; the per-Gaussian pass takes the same arguments)
+	GSR_AUX_NEEDS_OUTPUTS    // the forward blend: the two maps and the scratch
+};
+static int gsr_option_check(const char* who, int antialiasing, const gsr_aux_args* aux, bool optional, GsrAuxNeeds needs, bool live)
+{
+	if (antialiasing != 0 && antialiasing != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: antialiasing must be 0 or 1, got %d", who, antialiasing);
+	if (!aux) return optional ? GSR_OK : gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: aux is NULL", who);
+	if (aux->mode != GSR_AUX_DEPTH && aux->mode != GSR_AUX_INVDEPTH) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the mode of aux is unknown", who);
+	if (needs == GSR_AUX_NEEDS_MODE) return GSR_OK;
+	if (!aligned16(aux->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	if (live && (!aux->scratch || (needs == GSR_AUX_NEEDS_OUTPUTS && (!aux->out_depth || !aux->out_alpha))))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %sscratch is NULL", who, needs == GSR_AUX_NEEDS_OUTPUTS ? "out_depth, out_alpha or " : "");
+	return GSR_OK;
 }
 
 GsrGeometry gsr_geometry_view(void* blob, int P)
@@ -374,8 +394,6 @@ extern "C" uint32_t gsr_get_higher_msb(uint32_t n)
 	return msb;
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 // ---- per-thread helper resources -----------------------------------------------------------------
 // One helper stream (+ fork / join events) and one pinned landing buffer (+ its event) per host thread and device, created
 // on first use by gsr_forward_preprocess*.  They are the only things the library keeps between calls; a thread that is
@@ -410,6 +428,26 @@ extern "C" int gsr_thread_release(void)
 	}
 	if (rc) { (void)hipGetLastError(); return gsr_fail(rc, "gsr_thread_release: a HIP resource could not be freed"); }
 	return GSR_OK;
+}
+
+// A helper stream of this thread, created on first use: a non-blocking stream and its events (e1 may be NULL: none).  false: they
+// cannot be had, nothing is kept, and the caller runs that work in line.
+static bool gsr_helper_stream(hipStream_t* stream, hipEvent_t* e0, hipEvent_t* e1)
+{
+	if (*stream) return true;
+	hipStream_t st = nullptr;
+	hipEvent_t a = nullptr, b = nullptr;
+	if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&a, hipEventDisableTiming) == hipSuccess &&
+	    (!e1 || hipEventCreateWithFlags(&b, hipEventDisableTiming) == hipSuccess)) {
+		*stream = st; *e0 = a;
+		if (e1) *e1 = b;
+		return true;
+	}
+	(void)hipGetLastError();
+	if (st) (void)hipStreamDestroy(st);
+	if (a) (void)hipEventDestroy(a);
+	if (b) (void)hipEventDestroy(b);
+	return false;
 }
 
 // Makes `stream` wait for the helper stream's join event when the scope ends, unless now() already did.
@@ -449,45 +487,36 @@ struct GsrLastStage1 { const void* geometry = nullptr; bool col_pairs = false; }
 static thread_local GsrLastStage1 g_last_stage1;
 
 // ---- forward, stage 1 --------------------------------------------------------------------------
-static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int height, const float* means3D,
-                                       const float* shs, const float* shs_rest, int leaf, const float* colors_precomp,
-                                       const float* opacities, const float* scales, float scale_modifier,
-                                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                                       const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
-                                       int prefiltered, int* radii, void* geometry, int64_t* num_rendered_host,
-                                       void* stream, int debug, int aux = 0, int aa = 0)
+// `in`: the caller's inputs (gsr_preprocess_inputs / gsr_preprocess_leaves); what stage 1 derives itself (focal lengths, trim, the
+// geometry view) is filled in here.  aux: 0 or a GSR_AUX_* mode; aa: the screen-space filter.  Both stay outside the struct, which
+// is the kernels' argument.
+static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geometry, int64_t* num_rendered_host, void* stream, int debug,
+                                       int aux, int aa)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
+	GsrPreprocessArgs a = in;
+	const int P = a.P, width = a.W, height = a.H;
 	if (!num_rendered_host) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered_host is NULL");
 	*num_rendered_host = 0;
 	if (P < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "bad P / image size");
 	if (P == 0) return GSR_OK;  // rasterize_points.cu:94: nothing is launched for an empty scene
-	if (!means3D || !opacities || !viewmatrix || !projmatrix || !geometry)  // radii is optional (rasterizer.h:52)
+	if (!a.means3D || !a.opacities || !a.viewmatrix || !a.projmatrix || !geometry)  // radii is optional (rasterizer.h:52)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess: required pointer is NULL");
-	if (!colors_precomp && !shs)  // rasterizer_impl.cu:281-284
+	if (!a.colors_precomp && !a.shs)  // rasterizer_impl.cu:281-284
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "For non-RGB, provide precomputed Gaussian colors!");
-	if (!colors_precomp && (M <= 0 || (D + 1) * (D + 1) > M || D < 0 || D > 3 || !cam_pos))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", D, (D + 1) * (D + 1), M);
-	if (!cov3D_precomp && (!scales || !rotations))
+	if (!a.colors_precomp && (a.M <= 0 || (a.D + 1) * (a.D + 1) > a.M || a.D < 0 || a.D > 3 || !a.cam_pos))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "SH degree %d needs %d coefficients, M = %d", a.D, (a.D + 1) * (a.D + 1), a.M);
+	if (!a.cov3D_precomp && (!a.scales || !a.rotations))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "provide scales+rotations or cov3D_precomp");
 	if (width > 65535 * GSR_TILE_X || height > 65535 * GSR_TILE_Y)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image too large for 16-bit tile coordinates");
 	if (!aligned16(geometry)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "geometry buffer must be 16-byte aligned");
 
-	if (leaf && (M > 1 && !shs_rest)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: features_rest is NULL");
-	if (leaf && M > 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: at most 16 SH coefficients (degree 3), M = %d", M);
-	GsrPreprocessArgs a = {};
-	a.leaf = leaf; a.shs_rest = shs_rest;
-	a.P = P; a.D = D; a.M = M; a.W = width; a.H = height;
-	a.means3D = means3D; a.shs = shs; a.colors_precomp = colors_precomp; a.opacities = opacities;
-	a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
-	a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.cam_pos = cam_pos;
-	a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-	a.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:251-252
-	a.focal_x = width / (2.0f * tan_fovx);
-	a.prefiltered = prefiltered;
-	a.radii = radii;
+	if (a.leaf && (a.M > 1 && !a.shs_rest)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: features_rest is NULL");
+	if (a.leaf && a.M > 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: at most 16 SH coefficients (degree 3), M = %d", a.M);
+	a.focal_y = height / (2.0f * a.tan_fovy);  // rasterizer_impl.cu:251-252
+	a.focal_x = width / (2.0f * a.tan_fovx);
 	a.g = gsr_geometry_view(geometry, P);
 
 	int rc;
@@ -510,24 +539,11 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 #else
 	const bool bucket = gsr_bucket_sort_applies(P) && !(debug & GSR_DEBUG_RADIX_DEPTH);
 #endif
-	bool beside = color && !(debug & (GSR_DEBUG_SYNC | GSR_DEBUG_SERIAL)) && !gsr_prof_records_all(s);
-	if (beside && !td.aux_stream) {
-		hipStream_t st = nullptr;
-		hipEvent_t f = nullptr, j = nullptr;
-		// (Measured and not kept, round 3: a lowest-priority helper stream changes nothing -- the depth sort's first histogram
-		// and scatter still take 15 + 25 us beside the colour kernel instead of 6 + 13 alone; a helper stream confined to every
-		// other CU with hipExtStreamCreateWithCUMask made the step 0.16 ms slower.)
-		if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess &&
-		    hipEventCreateWithFlags(&j, hipEventDisableTiming) == hipSuccess) {
-			td.aux_stream = st; td.aux_fork = f; td.aux_join = j;
-		} else {
-			(void)hipGetLastError();
-			if (st) (void)hipStreamDestroy(st);
-			if (f) (void)hipEventDestroy(f);
-			if (j) (void)hipEventDestroy(j);
-			beside = false;  // no helper stream: the colour kernel runs in line
-		}
-	}
+	// (Measured and not kept, round 3: a lowest-priority helper stream changes nothing -- the depth sort's first histogram
+	// and scatter still take 15 + 25 us beside the colour kernel instead of 6 + 13 alone; a helper stream confined to every
+	// other CU with hipExtStreamCreateWithCUMask made the step 0.16 ms slower.)
+	const bool beside = color && !(debug & (GSR_DEBUG_SYNC | GSR_DEBUG_SERIAL)) && !gsr_prof_records_all(s) &&
+	                    gsr_helper_stream(&td.aux_stream, &td.aux_fork, &td.aux_join);   // no helper stream: the colour kernel runs in line
 	// From the fork on, EVERY return -- the error returns too -- first makes the caller's stream wait for the colour kernel:
 	// the caller is free to release or reuse `geometry` on `stream` the moment this call returns (include/gsr.h, stream
 	// contract), and the helper stream may still be writing rgb / clamp bits / sh_ddir into it.
@@ -546,22 +562,11 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 	}
 	// The count's read-back (a 6 us blit) goes to a stream of its own behind the geometry kernel, so that the depth sort's first
 	// launch follows that kernel directly; the stream waits for an event that the geometry kernel's own dispatch packet signals
-	// (hipExtLaunchKernelGGL) -- a hipEventRecord behind the kernel is a barrier packet and cost the sort's first launch ~8 us.
+	// (gsr_launch) -- a hipEventRecord behind the kernel is a barrier packet and cost the sort's first launch ~8 us.
 	// The host waits for the copy before this call returns, so nothing of it outlives the call.  In line with GSR_DEBUG_SYNC /
 	// GSR_DEBUG_SERIAL, when every stage is being timed, or when the stream cannot be had.
-	bool copy_beside = !(debug & (GSR_DEBUG_SYNC | GSR_DEBUG_SERIAL)) && !gsr_prof_records_all(s);
-	if (copy_beside && !td.copy_stream) {
-		hipStream_t st = nullptr;
-		hipEvent_t f = nullptr;
-		if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&f, hipEventDisableTiming) == hipSuccess) {
-			td.copy_stream = st; td.copy_fork = f;
-		} else {
-			(void)hipGetLastError();
-			if (st) (void)hipStreamDestroy(st);
-			if (f) (void)hipEventDestroy(f);
-			copy_beside = false;
-		}
-	}
+	const bool copy_beside = !(debug & (GSR_DEBUG_SYNC | GSR_DEBUG_SERIAL)) && !gsr_prof_records_all(s) &&
+	                         gsr_helper_stream(&td.copy_stream, &td.copy_fork, nullptr);
 	{
 		GsrProfScope p(s, "preprocess");
 		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux, aa);
@@ -647,6 +652,35 @@ static int gsr_forward_preprocess_impl(int P, int D, int M, int width, int heigh
 	return gsr_stage_done(s, debug, "depth_sort");
 }
 
+// the inputs of the calls that take activated tensors, and of the calls that take the optimiser's leaves (activated inside the kernels)
+static GsrPreprocessArgs gsr_preprocess_inputs(int P, int D, int M, int width, int height, const float* means3D, const float* shs,
+                                               const float* colors_precomp, const float* opacities, const float* scales,
+                                               float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                               const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
+                                               float tan_fovy, int prefiltered, int* radii)
+{
+	GsrPreprocessArgs a = {};
+	a.P = P; a.D = D; a.M = M; a.W = width; a.H = height;
+	a.means3D = means3D; a.shs = shs; a.colors_precomp = colors_precomp; a.opacities = opacities;
+	a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations; a.cov3D_precomp = cov3D_precomp;
+	a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.cam_pos = cam_pos;
+	a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
+	a.prefiltered = prefiltered;
+	a.radii = radii;
+	return a;
+}
+static GsrPreprocessArgs gsr_preprocess_leaves(int P, int D, int M, int width, int height, const float* xyz, const float* features_dc,
+                                               const float* features_rest, const float* opacity_logits, const float* log_scales,
+                                               float scale_modifier, const float* raw_rotations, const float* viewmatrix,
+                                               const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                                               int prefiltered, int* radii)
+{
+	GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, xyz, features_dc, nullptr, opacity_logits, log_scales, scale_modifier,
+	                                            raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	a.leaf = 1; a.shs_rest = features_rest;
+	return a;
+}
+
 extern "C" int gsr_forward_preprocess(int P, int D, int M, int width, int height, const float* means3D,
                                       const float* shs, const float* colors_precomp, const float* opacities,
                                       const float* scales, float scale_modifier, const float* rotations,
@@ -654,9 +688,9 @@ extern "C" int gsr_forward_preprocess(int P, int D, int M, int width, int height
                                       const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                                       int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	return gsr_forward_preprocess_impl(P, D, M, width, height, means3D, shs, nullptr, 0, colors_precomp, opacities, scales,
-	                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-	                                   tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug);
+	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, 0, 0);
 }
 
 extern "C" int gsr_forward_preprocess_leaf(int P, int D, int M, int width, int height, const float* xyz,
@@ -667,9 +701,9 @@ extern "C" int gsr_forward_preprocess_leaf(int P, int D, int M, int width, int h
                                            int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                            int debug)
 {
-	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
-	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
-	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug);
+	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
+	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, 0, 0);
 }
 
 extern "C" int gsr_forward_preprocess_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* means3D,
@@ -679,11 +713,11 @@ extern "C" int gsr_forward_preprocess_aux(const gsr_aux_args* aux, int P, int D,
                                           const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                                           int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	g_err[0] = 0;
-	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess_aux: aux is NULL or its mode is unknown");
-	return gsr_forward_preprocess_impl(P, D, M, width, height, means3D, shs, nullptr, 0, colors_precomp, opacities, scales,
-	                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-	                                   tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux->mode);
+	int rc;
+	if ((rc = gsr_option_check("gsr_forward_preprocess_aux", 0, aux, false, GSR_AUX_NEEDS_MODE, false))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux->mode, 0);
 }
 
 extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* xyz,
@@ -694,21 +728,14 @@ extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, i
                                                int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                                int debug)
 {
-	g_err[0] = 0;
-	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess_leaf_aux: aux is NULL or its mode is unknown");
-	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
-	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
-	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux->mode);
+	int rc;
+	if ((rc = gsr_option_check("gsr_forward_preprocess_leaf_aux", 0, aux, false, GSR_AUX_NEEDS_MODE, false))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
+	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux->mode, 0);
 }
 
 // the anti-aliased path (include/gsr_aa.h): aux NULL or a known mode; antialiasing 0 or 1
-static int gsr_aa_check(int antialiasing, const gsr_aux_args* aux, const char* who)
-{
-	if (antialiasing != 0 && antialiasing != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: antialiasing must be 0 or 1, got %d", who, antialiasing);
-	if (aux && !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the mode of aux is unknown", who);
-	return GSR_OK;
-}
-
 extern "C" int gsr_forward_preprocess_aa(int antialiasing, const gsr_aux_args* aux, int P, int D, int M, int width, int height,
                                          const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,
                                          const float* scales, float scale_modifier, const float* rotations,
@@ -716,13 +743,11 @@ extern "C" int gsr_forward_preprocess_aa(int antialiasing, const gsr_aux_args* a
                                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                                          int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	g_err[0] = 0;
 	int rc;
-	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_forward_preprocess_aa"))) return rc;
-	return gsr_forward_preprocess_impl(P, D, M, width, height, means3D, shs, nullptr, 0, colors_precomp, opacities, scales,
-	                                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx,
-	                                   tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0,
-	                                   antialiasing);
+	if ((rc = gsr_option_check("gsr_forward_preprocess_aa", antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing);
 }
 
 extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_args* aux, int P, int D, int M, int width, int height,
@@ -733,13 +758,11 @@ extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_ar
                                               int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                               int debug)
 {
-	g_err[0] = 0;
 	int rc;
-	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_forward_preprocess_leaf_aa"))) return rc;
-	return gsr_forward_preprocess_impl(P, D, M, width, height, xyz, features_dc, features_rest, 1, nullptr, opacity_logits,
-	                                   log_scales, scale_modifier, raw_rotations, nullptr, viewmatrix, projmatrix, cam_pos,
-	                                   tan_fovx, tan_fovy, prefiltered, radii, geometry, num_rendered_host, stream, debug,
-	                                   aux ? aux->mode : 0, antialiasing);
+	if ((rc = gsr_option_check("gsr_forward_preprocess_leaf_aa", antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
+	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing);
 }
 
 // ---- forward, stage 2 --------------------------------------------------------------------------
@@ -822,12 +845,9 @@ static int gsr_forward_render_impl(int P, int64_t R, int width, int height, cons
 	if ((rc = gsr_stage_done(s, debug, "tile_order"))) return rc;
 	{
 		GsrProfScope p(s, "render_forward");
-		if (aux) {
-			const GsrAuxBlend x = gsr_aux_view(*aux, R, width, height);
-			gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s, &x);
-		} else {
-				gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s);
-		}
+		GsrAuxBlend x;
+		gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s,
+		                          gsr_aux_view(aux, R, width, height, &x));
 	}
 	return gsr_stage_done(s, debug, "render_forward");
 }
@@ -843,11 +863,8 @@ extern "C" int gsr_forward_render_aux(const gsr_aux_args* aux, int P, int64_t R,
                                       const int* radii, void* geometry, void* binning, void* image, float* out_color,
                                       void* stream, int debug)
 {
-	g_err[0] = 0;
-	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: aux is NULL or its mode is unknown");
-	if (P > 0 && (!aux->out_depth || !aux->out_alpha || !aux->scratch))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: out_depth, out_alpha and scratch are required");
-	if (!aligned16(aux->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render_aux: scratch must be 16-byte aligned");
+	int rc;
+	if ((rc = gsr_option_check("gsr_forward_render_aux", 0, aux, false, GSR_AUX_NEEDS_OUTPUTS, P > 0))) return rc;
 	return gsr_forward_render_impl(P, R, width, height, background, radii, geometry, binning, image, out_color, stream, debug, aux);
 }
 
@@ -910,40 +927,25 @@ static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_
 		hipEvent_t t0 = nullptr, t1 = nullptr;
 		const bool own = gsr_prof_kernel_events(s, "render_backward", &t0, &t1);
 		GsrProfScope p(s, own ? nullptr : "render_backward");
-		if (aux) {
-			const GsrAuxBlend x = gsr_aux_view(*aux, a.num_rendered, a.width, a.height);
-			gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
-			                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1, &x);
-		} else {
-			gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
-			                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1);
-		}
+		GsrAuxBlend x;
+		gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
+		                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1,
+		                           gsr_aux_view(aux, a.num_rendered, a.width, a.height, &x));
 	}
 	return gsr_stage_done(s, a.debug, "render_backward");
 }
 
 extern "C" int gsr_backward_blend(const gsr_backward_args* args) { return gsr_backward_blend_impl(args, nullptr); }
 
-static int gsr_aux_check(const gsr_aux_args* aux, const char* who)
-{
-	if (!aux || !gsr_aux_mode_ok(aux->mode)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: aux is NULL or its mode is unknown", who);
-	if (!aligned16(aux->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
-	return GSR_OK;
-}
-
 extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_aux_args* aux)
 {
-	g_err[0] = 0;
 	int rc;
-	if ((rc = gsr_aux_check(aux, "gsr_backward_blend_aux"))) return rc;
-	if (args && args->P > 0 && args->num_rendered > 0 && !aux->scratch)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend_aux: scratch is NULL");
+	if ((rc = gsr_option_check("gsr_backward_blend_aux", 0, aux, false, GSR_AUX_NEEDS_SCRATCH, args && args->P > 0 && args->num_rendered > 0))) return rc;
 	return gsr_backward_blend_impl(args, aux);
 }
 
-// aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h); NULL: the default ones
-static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux,
-                                       const float* aa_opacities = nullptr)
+// aux: 0 or a GSR_AUX_* mode; aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h), NULL: the default ones
+static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
@@ -972,38 +974,29 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		if (aa_opacities) {
-			GsrGaussianBackwardArgsAA x;
-			static_cast<GsrGaussianBackwardArgs&>(x) = a;
-			x.opacities = aa_opacities;
-			gsr_launch_gaussian_backward_aa(x, s, aux);
-		} else {
-			gsr_launch_gaussian_backward(a, s, aux);
-		}
+		gsr_launch_gaussian_backward(a, aa_opacities, s, aux);
 	}
 	return gsr_stage_done(s, b.debug, "gaussian_backward");
 }
 
 extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
 {
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, 0);
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, 0, nullptr);
 }
 
 extern "C" int gsr_backward_gaussians_aux(const gsr_backward_args* args, const gsr_aux_args* aux, int first, int count, int out_row0)
 {
-	g_err[0] = 0;
 	int rc;
-	if ((rc = gsr_aux_check(aux, "gsr_backward_gaussians_aux"))) return rc;
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux->mode);
+	// (the per-Gaussian pass reads the mode alone; the scratch's alignment is checked as the blend's call does)
+	if ((rc = gsr_option_check("gsr_backward_gaussians_aux", 0, aux, false, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux->mode, nullptr);
 }
 
 extern "C" int gsr_backward_gaussians_aa(const gsr_backward_args* args, int antialiasing, const float* opacities, const gsr_aux_args* aux,
                                          int first, int count, int out_row0)
 {
-	g_err[0] = 0;
 	int rc;
-	if ((rc = gsr_aa_check(antialiasing, aux, "gsr_backward_gaussians_aa"))) return rc;
-	if (aux && (rc = gsr_aux_check(aux, "gsr_backward_gaussians_aa"))) return rc;
+	if ((rc = gsr_option_check("gsr_backward_gaussians_aa", antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
 	if (antialiasing && args && args->P > 0 && count > 0 && !opacities)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians_aa: the opacity input is NULL");
 	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr);

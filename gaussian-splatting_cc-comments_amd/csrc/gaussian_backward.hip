@@ -537,47 +537,28 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 	}
 }
 
-template <int AUX, bool AA, typename Args>
-static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int sh_via_lds, int skip_dsh)
+// one instantiation per (LEAF, depth-and-alpha mode, AA): the AA ones are those that receive the struct with the opacity input
+template <typename Args>
+static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux)
 {
-	if (a.leaf) hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, AUX, AA>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
-	else hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, AUX, AA>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
-}
-
-// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
-static void gsr_gaussian_backward_modes(const GsrGaussianBackwardArgs& a, int& sh_via_lds, int& skip_dsh)
-{
-	skip_dsh = (a.shs && !a.dL_dsh) ? 1 : 0;  // view-parallel mode (include/gsr.h)
-	sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
-	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
-}
-
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux)
-{
+	constexpr bool AA = std::is_same<Args, GsrGaussianBackwardArgsAA>::value;
 	// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
 	const int skip_dsh = (a.shs && !a.dL_dsh) ? 1 : 0;  // view-parallel mode (include/gsr.h)
 	int sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
-	if (aux) {
-		if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH, false>(a, s, sh_via_lds, skip_dsh);
-		else gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH, false>(a, s, sh_via_lds, skip_dsh);
-		return;
-	}
-	if (a.leaf) {
-		if (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0)) sh_via_lds = 0;
-		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<true, 0, false>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
-	} else {
-		hipLaunchKernelGGL((gsr_gaussian_backward_kernel<false, 0, false>), dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s, a, sh_via_lds, skip_dsh);
-	}
+	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
+	gsr_variant(a.leaf, aux, AA, [&](auto LEAF, auto AUX, auto) {
+		gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA>, dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s,
+		           nullptr, nullptr, a, sh_via_lds, skip_dsh);
+	});
 }
 
-void gsr_launch_gaussian_backward_aa(const GsrGaussianBackwardArgsAA& a, hipStream_t s, int aux)
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux)
 {
-	int sh_via_lds = 0, skip_dsh = 0;
-	gsr_gaussian_backward_modes(a, sh_via_lds, skip_dsh);
-	if (aux == GSR_AUX_INVDEPTH) gsr_launch_gaussian_backward_t<GSR_AUX_INVDEPTH, true>(a, s, sh_via_lds, skip_dsh);
-	else if (aux) gsr_launch_gaussian_backward_t<GSR_AUX_DEPTH, true>(a, s, sh_via_lds, skip_dsh);
-	else gsr_launch_gaussian_backward_t<0, true>(a, s, sh_via_lds, skip_dsh);
+	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux);
+	GsrGaussianBackwardArgsAA x;
+	static_cast<GsrGaussianBackwardArgs&>(x) = a;
+	x.opacities = aa_opacities;
+	gsr_launch_gaussian_backward_t(x, s, aux);
 }
 
 // ---- view-parallel SH gradient (no reference counterpart) ------------------------------

@@ -1,8 +1,11 @@
 // gsr_internal.h -- host-side glue shared by the translation units of libgsr_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_aux.h"
@@ -110,6 +113,39 @@ struct GsrProfScope {
 };
 
 // ---- kernel launchers ------------------------------------------------------------------------
+// The one launch call of every kernel that may carry events.  start / stop: optional events that the kernel's own dispatch packet
+// signals (hipExtLaunchKernelGGL) -- its timestamps, or "this kernel has finished" for another stream to wait on.  A hipEventRecord
+// in front of or behind the kernel would be a barrier packet of its own and costs the stream's next launch 6-8 us.  Without an event
+// it is the plain launch.  The arguments are converted to the kernel's own parameter types here (the Ext call packs them as given).
+template <typename T> struct GsrSame { typedef T type; };
+template <typename... P>
+static inline void gsr_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t start, hipEvent_t stop,
+                              typename GsrSame<P>::type... args)
+{
+	if (start || stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, s, start, stop, 0, args...);
+	else hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+}
+
+// The one place where a call's run-time variant becomes template arguments: f(LEAF, AUX, AA) is called with the three as
+// std::integral_constant values (LEAF() etc. are constant expressions).  aux: 0 or a GSR_AUX_* mode; a kernel without one of the
+// three variants ignores that argument (the colour kernel has no AA form, the blend kernels only "maps or not").  The order of the
+// branches is the order in which a file's instantiations appear in its device code (`make audit` output is compared across commits).
+template <typename F>
+static inline void gsr_variant(bool leaf, int aux, bool aa, F&& f)
+{
+	auto with_leaf = [&](auto AUX, auto AA) {
+		if (leaf) f(std::true_type{}, AUX, AA);
+		else f(std::false_type{}, AUX, AA);
+	};
+	auto with_aux = [&](auto AA) {
+		if (aux == GSR_AUX_INVDEPTH) with_leaf(std::integral_constant<int, GSR_AUX_INVDEPTH>{}, AA);
+		else if (aux) with_leaf(std::integral_constant<int, GSR_AUX_DEPTH>{}, AA);
+		else with_leaf(std::integral_constant<int, 0>{}, AA);
+	};
+	if (aa) with_aux(std::true_type{});
+	else with_aux(std::false_type{});
+}
+
 struct GsrPreprocessArgs {
 	int P, D, M, W, H;
 	const float* means3D;
@@ -137,10 +173,11 @@ struct GsrPreprocessArgs {
 // preprocess.hip
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the kernels then also store the depth value v in the splat record's last word
 // aa: the anti-aliased path (include/gsr_aa.h): the record's opacity is opacity * rho (gsr_aa.h); the colour kernel has no such variant
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done = nullptr, int aux = 0, int aa = 0);
-void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done = nullptr);
+// done: NULL, or an event signalled when the kernel has finished (gsr_launch)
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa);
+void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done);
 bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a);
-void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu = 0, int aux = 0);
+void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu, int aux);
 void gsr_launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
 
 // binning.hip
@@ -189,13 +226,13 @@ int gsr_tile_key_bytes(int ntiles, size_t num_rendered);
 // render_forward.hip
 void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float4* checkpoints,
                                const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s,
-                               const GsrAuxBlend* aux = nullptr);   // ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries; aux: the depth-and-alpha variant
+                               const GsrAuxBlend* aux);   // ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries; aux: NULL, or the depth-and-alpha variant
 
 // render_backward.hip
 void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
                                 const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start = nullptr, hipEvent_t t_stop = nullptr,
-                                const GsrAuxBlend* aux = nullptr);   // t_*: taken by the kernel's own dispatch packet; aux: the depth-and-alpha variant
+                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop,
+                                const GsrAuxBlend* aux);   // t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
 
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
@@ -243,9 +280,9 @@ struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
 	const float* opacities;
 };
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the slots' tenth word (dL/dv) is summed and chained into dL/dmean3D
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, int aux = 0);
-// the anti-aliased kernels (same aux modes): dL/dopacity = dL/dopacity_record * rho, and dL/drho into dL/dcov3D and dL/dmean3D
-void gsr_launch_gaussian_backward_aa(const GsrGaussianBackwardArgsAA& a, hipStream_t s, int aux = 0);
+// aa_opacities: NULL, or the anti-aliased kernels with this opacity input: dL/dopacity = dL/dopacity_record * rho, and dL/drho into
+// dL/dcov3D and dL/dmean3D
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,
                                    int64_t view_stride, float* dL_dsh, hipStream_t s);
 

@@ -6,7 +6,6 @@
 // kernel also accumulates the instance count (num_rendered) -- one atomic add per workgroup into 64
 // partial counters -- so no scan over P follows.
 #include "gsr_internal.h"
-#include <hip/hip_ext.h>
 #include "gsr_rect_trim.h"
 #include "gsr_aa.h"
 
@@ -288,9 +287,8 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_color_ker
 }
 
 // The status words (instance count and depth range as 64-way partial sums / maxima, the prefiltered flag) start at zero.  A kernel
-// of ours instead of hipMemsetAsync (which is a kernel launch too) because its dispatch packet can signal an event
-// (hipExtLaunchKernelGGL): `done` = the fork event of the helper stream -- a hipEventRecord in front of the first kernel is a
-// barrier packet of its own, ~6 us of every forward call.
+// of ours instead of hipMemsetAsync (which is a kernel launch too) because its dispatch packet can signal an event (gsr_launch):
+// `done` = the fork event of the helper stream, ~6 us of every forward call less than a hipEventRecord in front of the first kernel.
 __global__ void gsr_zero_status_kernel(uint32_t* __restrict__ status)
 {
 	if (threadIdx.x < GSR_STATUS_WORDS) status[threadIdx.x] = 0u;
@@ -298,21 +296,10 @@ __global__ void gsr_zero_status_kernel(uint32_t* __restrict__ status)
 void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done)
 {
 	static_assert(GSR_STATUS_WORDS <= 256, "one workgroup zeroes the status words");
-	if (done) hipExtLaunchKernelGGL(gsr_zero_status_kernel, dim3(1), dim3(256), 0, s, nullptr, done, 0, status);
-	else hipLaunchKernelGGL(gsr_zero_status_kernel, dim3(1), dim3(256), 0, s, status);
+	gsr_launch(gsr_zero_status_kernel, dim3(1), dim3(256), 0, s, nullptr, done, status);
 }
 
-// done: optional event signalled by the kernel's own dispatch packet when it has finished (hipExtLaunchKernelGGL): a separate
-// hipEventRecord behind the kernel is a barrier packet of its own and costs the stream's next launch ~8 us
-// the depth-and-alpha and anti-aliased variants: one instantiation per (LEAF, mode, AA)
-template <int AUX, bool AA>
-static void gsr_launch_preprocess_aux(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int nb, uint32_t* clear, size_t clear_words,
-                                      uint32_t* clear2, size_t clear2_words)
-{
-	if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, AUX, AA>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-	else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, AUX, AA>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-}
-
+// one instantiation per (LEAF, depth-and-alpha mode, AA); done: the event the count's read-back waits for (api.hip)
 void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
@@ -320,24 +307,10 @@ void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t
 	const size_t clear_words = gsr_radix_clear_words((size_t)a.P);
 	uint32_t* clear2 = (uint32_t*)a.g.col_table;
 	const size_t clear2_words = gsr_tilebin_col_clear_words((size_t)a.P);
-	if (aa) {
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		else if (aux) gsr_launch_preprocess_aux<GSR_AUX_DEPTH, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		else gsr_launch_preprocess_aux<0, true>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		return;
-	}
-	if (aux) {
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_aux<GSR_AUX_INVDEPTH, false>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		else gsr_launch_preprocess_aux<GSR_AUX_DEPTH, false>(a, s, done, nb, clear, clear_words, clear2, clear2_words);
-		return;
-	}
-	if (done) {
-		if (a.leaf) hipExtLaunchKernelGGL((gsr_preprocess_kernel<true, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-		else hipExtLaunchKernelGGL((gsr_preprocess_kernel<false, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done, 0, a, clear, clear_words, clear2, clear2_words);
-		return;
-	}
-	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_kernel<true, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
-	else hipLaunchKernelGGL((gsr_preprocess_kernel<false, 0, false>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, a, clear, clear_words, clear2, clear2_words);
+	gsr_variant(a.leaf, aux, aa, [&](auto LEAF, auto AUX, auto AA) {
+		gsr_launch(gsr_preprocess_kernel<LEAF(), AUX(), AA()>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done,
+		           a, clear, clear_words, clear2, clear2_words);
+	});
 }
 
 // the colour kernel exists only for SH colours
@@ -345,33 +318,17 @@ bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a) { return a.shs && !a
 
 // wgs_per_cu: 0 = as many workgroups per CU as fit; else the kernel is held to that many by (unused) dynamic LDS on top of its own
 // staging area (26 KB) -- while it runs beside the depth sort on the helper stream (api.hip)
-template <int AUX>
-static void gsr_launch_preprocess_color_aux(const GsrPreprocessArgs& a, hipStream_t s, int nb, size_t throttle, int sh_via_lds)
-{
-	if (a.leaf) hipLaunchKernelGGL((gsr_preprocess_color_kernel<true, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
-	else hipLaunchKernelGGL((gsr_preprocess_color_kernel<false, AUX>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
-}
-
 void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu, int aux)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
-	// LDS-transposed SH path: the flagship layout (16 coefficients), 16-byte aligned tensor
-	int sh_via_lds = (a.M == 16 && ((uintptr_t)a.shs & 15u) == 0) ? 1 : 0;
+	// LDS-transposed SH path: the flagship layout (16 coefficients), 16-byte aligned tensors
+	const int sh_via_lds = (a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && !(a.leaf && ((uintptr_t)a.shs_rest & 15u) != 0)) ? 1 : 0;
 	const size_t own = (size_t)(GSR_PREPROCESS_BLOCK / 64) * 32 * GSR_SH_ROW4 * sizeof(float4);
 	const size_t share = wgs_per_cu > 0 ? (size_t)160 * 1024 / (size_t)wgs_per_cu : 0;
 	const size_t throttle = share > own + 1024 ? share - own - 1024 : 0;   // (1 KB of slack for allocation granularity)
-	if (a.leaf && ((uintptr_t)a.shs_rest & 15u) != 0) sh_via_lds = 0;
-	if (aux) {
-		if (aux == GSR_AUX_INVDEPTH) gsr_launch_preprocess_color_aux<GSR_AUX_INVDEPTH>(a, s, nb, throttle, sh_via_lds);
-		else gsr_launch_preprocess_color_aux<GSR_AUX_DEPTH>(a, s, nb, throttle, sh_via_lds);
-		return;
-	}
-	if (a.leaf) {
-		if (((uintptr_t)a.shs_rest & 15u) != 0) sh_via_lds = 0;
-		hipLaunchKernelGGL((gsr_preprocess_color_kernel<true, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
-	} else {
-		hipLaunchKernelGGL((gsr_preprocess_color_kernel<false, 0>), dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, a, sh_via_lds);
-	}
+	gsr_variant(a.leaf, aux, false, [&](auto LEAF, auto AUX, auto) {   // (no AA form: the filter changes nothing about the colour)
+		gsr_launch(gsr_preprocess_color_kernel<LEAF(), AUX()>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), throttle, s, nullptr, nullptr, a, sh_via_lds);
+	});
 }
 
 // rasterizer_impl.cu:56-69 checkFrustum: only the view-space z test of in_frustum survives

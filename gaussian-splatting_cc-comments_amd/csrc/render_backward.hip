@@ -20,7 +20,6 @@
 // from the same roundings as in the forward kernel (gsr_pair_power; the forward's pre-halved conic terms give the same
 // bits), so the products the forward formed are the ones undone here.
 #include "render_common.h"
-#include <hip/hip_ext.h>
 
 #define GSR_BWD_NV 9
 #define GSR_BWD_FLUSH 4   // reduced instances finished together (default variant): 4 x (8 values + 8 groups of the ninth) = 64 lanes
@@ -423,19 +422,9 @@ void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* poin
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (int)gsr_tile_order_max_segments(ntiles);   // whole tiles + the extra entries of heavy tiles' depth segments
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
-	if (aux) {
-		hipExtLaunchKernelGGL(gsr_render_backward_wave_kernel<true>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, 0, W, H, gx, nslots,
-		                      img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		                      img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, *aux);
-		return;
-	}
-	if (t_start || t_stop) {
-		hipExtLaunchKernelGGL(gsr_render_backward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, 0, W, H, gx, nslots,
-		                      img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		                      img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, GsrAuxBlend{});
-		return;
-	}
-	hipLaunchKernelGGL(gsr_render_backward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
-	                   img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-	                   img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, GsrAuxBlend{});
+	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, false, [&](auto, auto AUX, auto) {   // (one kernel for both modes: it reads v from the record)
+		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, W, H, gx, nslots,
+		           img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
+		           img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
+	});
 }

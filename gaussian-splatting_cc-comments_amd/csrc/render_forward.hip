@@ -215,13 +215,9 @@ void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (ordered ? 3 * (int)gsr_tile_order_max_split(ntiles) : 0);
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
-	if (aux) {
-		hipLaunchKernelGGL(gsr_render_forward_wave_kernel<true>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
-		                   img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		                   ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, *aux);
-		return;
-	}
-	hipLaunchKernelGGL(gsr_render_forward_wave_kernel<false>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, W, H, gx, nslots,
-	                   img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-	                   ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, GsrAuxBlend{});
+	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, false, [&](auto, auto AUX, auto) {   // (one kernel for both modes: it reads v from the record)
+		gsr_launch(gsr_render_forward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, nullptr, nullptr, W, H, gx, nslots,
+		           img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
+		           ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
+	});
 }

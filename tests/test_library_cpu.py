@@ -134,6 +134,67 @@ def test_8f_entry_points_validate_before_any_device_work():
     assert rc == -1 and b"NULL" in L.gsr_last_error()
 
 
+def test_aux_and_aa_entry_points_validate_before_any_device_work():
+    """include/gsr_aux.h / gsr_aa.h: what every *_aux / *_aa entry point rejects about its gsr_aux_args (and the filter's opacity
+    input) before any HIP call, and that an empty scene is GSR_OK with nothing launched.  Where the remaining arguments would be
+    rejected as well, P == 0 or the message's prefix tells the option's own check apart from the stage's."""
+    from diff_gaussian_rasterization import _C
+    L = _C.lib()
+    OK, BAD = 0, -1
+    err = L.gsr_last_error
+    f1 = ctypes.c_float(1)
+    R = ctypes.c_int64(-1)
+    buf = ctypes.create_string_buffer(64 + 16)   # never dereferenced: the calls below return before any device work
+    aligned = (ctypes.addressof(buf) + 15) & ~15
+
+    def aux_args(mode=1, scratch=aligned, out=aligned):
+        return _C.AuxArgs(mode, out, out, None, None, scratch)
+
+    def pre(P=0, width=8):       # the arguments of gsr_forward_preprocess; gsr_forward_preprocess_leaf has one pointer fewer
+        return [P, 0, 1, width, 8] + [None] * 5 + [f1] + [None] * 5 + [f1, f1, 0, None, None, ctypes.byref(R), None, 0]
+
+    def pre_leaf(P=0):
+        return [P, 0, 1, 8, 8] + [None] * 5 + [f1] + [None] * 4 + [f1, f1, 0, None, None, ctypes.byref(R), None, 0]
+
+    def render(P=0):
+        return [P, 0, 8, 8] + [None] * 7 + [0]
+
+    def bwd(P=0):
+        a = _C.BackwardArgs()
+        a.P, a.M, a.width, a.height, a.tan_fovx, a.tan_fovy = P, 1, 8, 8, 1.0, 1.0
+        if P:   # pointers that pass the stage's own checks; none is dereferenced before the range check
+            for n in ("background", "means3D", "viewmatrix", "projmatrix", "geometry", "image", "dL_dpix", "dL_dmean2D", "dL_dopacity",
+                      "dL_dmean3D", "dL_dscale", "dL_drot", "scales", "rotations", "colors_precomp", "dL_dcolor"):
+                setattr(a, n, aligned)
+        return a
+
+    # aux == NULL and an unknown mode, every *_aux entry point (P == 0: only the option's check can object)
+    calls = ((L.gsr_forward_preprocess_aux, lambda x: [x] + pre()), (L.gsr_forward_preprocess_leaf_aux, lambda x: [x] + pre_leaf()),
+             (L.gsr_forward_render_aux, lambda x: [x] + render()), (L.gsr_backward_blend_aux, lambda x: [ctypes.byref(bwd()), x]),
+             (L.gsr_backward_gaussians_aux, lambda x: [ctypes.byref(bwd()), x, 0, 0, 0]))
+    for fn, args in calls:
+        assert fn(*args(None)) == BAD and err().startswith(fn.__name__.encode()), fn.__name__
+        assert fn(*args(ctypes.byref(aux_args(mode=3)))) == BAD and err().startswith(fn.__name__.encode()), fn.__name__
+        assert fn(*args(ctypes.byref(aux_args()))) == OK and err() == b"", fn.__name__    # P == 0: nothing is launched
+    assert R.value == 0   # (what stage 1 reports for an empty scene)
+    # the blend needs the outputs and the scratch, 16-byte aligned; the backward calls an aligned scratch
+    assert L.gsr_forward_render_aux(ctypes.byref(aux_args(out=None)), *render(P=1)) == BAD and err().startswith(b"gsr_forward_render_aux")
+    assert L.gsr_forward_render_aux(ctypes.byref(aux_args(scratch=aligned + 4)), *render()) == BAD and err().startswith(b"gsr_forward_render_aux")
+    assert L.gsr_backward_blend_aux(ctypes.byref(bwd()), ctypes.byref(aux_args(scratch=aligned + 4))) == BAD
+    assert err().startswith(b"gsr_backward_blend_aux")
+    assert L.gsr_backward_gaussians_aux(ctypes.byref(bwd()), ctypes.byref(aux_args(scratch=aligned + 4)), 0, 0, 0) == BAD
+    assert err().startswith(b"gsr_backward_gaussians_aux")
+    # the filter's per-Gaussian backward: the opacity input, and the range's first Gaussian a multiple of 64
+    assert L.gsr_backward_gaussians_aa(ctypes.byref(bwd(P=128)), 1, None, None, 0, 64, 0) == BAD and err().startswith(b"gsr_backward_gaussians_aa")
+    assert L.gsr_backward_gaussians_aa(ctypes.byref(bwd(P=128)), 1, aligned, None, 32, 64, 0) == BAD and err().startswith(b"gsr_backward_gaussians")
+    assert L.gsr_backward_gaussians_aa(ctypes.byref(bwd(P=128)), 1, aligned, None, 64, 0, 0) == OK     # an empty range: nothing is launched
+    assert L.gsr_backward_gaussians_aa(ctypes.byref(bwd(P=128)), 0, None, None, 32, 64, 0) == BAD
+    # with the option off the call is its default: the same verdict on the same invalid image size
+    rc = L.gsr_forward_preprocess(*pre(P=1, width=0))
+    assert rc == BAD and b"bad" in err()
+    assert L.gsr_forward_preprocess_aa(0, None, *pre(P=1, width=0)) == rc and b"bad" in err()
+
+
 def test_8f_python_surfaces_refuse_cpu_tensors():
     import fused_loss
     import fused_params
