@@ -12,6 +12,7 @@
 
 #include "gsr_internal.h"
 #include "../../include/gsr_aa.h"
+#include "../../include/gsr_contrib.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1050,6 +1051,46 @@ extern "C" int gsr_backward_leaf(int P, int D, int M, int64_t R, int width, int 
 	a.dL_dsh = dL_dfeatures_dc; a.dL_dsh_rest = dL_dfeatures_rest; a.dL_dscale = dL_dlog_scales; a.dL_drot = dL_draw_rotations;
 	a.stream = stream; a.debug = debug;
 	return gsr_backward_whole(a);
+}
+
+// ---- blend-weight statistics (include/gsr_contrib.h) --------------------------------------------
+extern "C" size_t gsr_contrib_scratch_bytes(int P, int64_t R)
+{
+	(void)P;
+	if (R < 0) return 0;
+	return gsr_contrib_valid_offset(R) + gsr_align_up((size_t)R);   // the records, then one validity byte per slot
+}
+
+extern "C" int gsr_contributions(int P, int64_t R, int width, int height, const void* geometry, const void* binning, const void* image,
+                                 const float* pixel_weight, float* weight_sum, float* weight_max, int32_t* pixel_count, void* scratch,
+                                 void* stream, int debug)
+{
+	g_err[0] = 0;
+	hipStream_t s = (hipStream_t)stream;
+	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: bad sizes");
+	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
+	if (!weight_sum && !weight_max && !pixel_count) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: all three outputs are NULL");
+	if (!geometry || !image || (R > 0 && (!binning || !scratch)))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: required pointer is NULL");
+	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(scratch))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "state buffers and scratch must be 16-byte aligned");
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered exceeds 32-bit offsets");
+	if (R == 0) return GSR_OK;   // nothing blended: every Gaussian is left untouched
+	GsrGeometry g = gsr_geometry_view((void*)geometry, P);
+	GsrImage im = gsr_image_view((void*)image, width, height);
+	GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
+	int rc;
+	{
+		GsrProfScope p(s, "contrib_tiles");   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
+		if ((rc = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_contrib_valid_offset(R), 0, (size_t)R, s), "hipMemsetAsync(contrib validity)"))) return rc;
+		gsr_launch_contrib_tiles(width, height, im, b.point_list, g.splat, g.slot_base, pixel_weight, scratch, R, !(debug & GSR_DEBUG_NO_CULL), s);
+	}
+	if ((rc = gsr_stage_done(s, debug, "contrib_tiles"))) return rc;
+	{
+		GsrProfScope p(s, "contrib_gaussians");
+		gsr_launch_contrib_gaussians(P, g, scratch, R, weight_sum, weight_max, pixel_count, s);
+	}
+	return gsr_stage_done(s, debug, "contrib_gaussians");
 }
 
 extern "C" size_t gsr_loss_scratch_bytes(int C, int H, int W)

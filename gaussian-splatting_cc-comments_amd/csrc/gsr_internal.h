@@ -234,6 +234,14 @@ void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* poin
                                 uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop,
                                 const GsrAuxBlend* aux);   // t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
 
+// contrib.hip: blend-weight statistics (include/gsr_contrib.h).  scratch: R 16-byte records, then (at gsr_contrib_valid_offset) R validity
+// bytes, which gsr_contributions clears on the stream before the tile pass
+size_t gsr_contrib_valid_offset(int64_t R);
+void gsr_launch_contrib_tiles(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
+                              const float* pixel_weight, void* scratch, int64_t R, bool cull, hipStream_t s);
+void gsr_launch_contrib_gaussians(int P, GsrGeometry g, const void* scratch, int64_t R, float* weight_sum, float* weight_max, int32_t* pixel_count,
+                                  hipStream_t s);
+
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
 	int P, D, M, W, H;

@@ -161,6 +161,11 @@ def lib():
                            ("gsr_backward_gaussians_aa", [pb, _i, _vp, pa, _i, _i, _i])):
         getattr(L, name).restype = _i
         getattr(L, name).argtypes = argtypes
+    # include/gsr_contrib.h: per-Gaussian blend-weight statistics
+    L.gsr_contrib_scratch_bytes.restype = _sz
+    L.gsr_contrib_scratch_bytes.argtypes = [_i, _i64]
+    L.gsr_contributions.restype = _i
+    L.gsr_contributions.argtypes = [_i, _i64, _i, _i] + [_vp] * 8 + [_vp, _i]
     _lib = L
     return L
 
@@ -458,6 +463,60 @@ def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, r
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), True, False, None, stats, antialiasing, opacities)
+
+
+# ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------
+def contrib_stat_tensors(stats, P):
+    """Checks stats = (weight_sum f32, weight_max f32, pixel_count i32), [P] each, any of them None -> their device.  No kernel and no
+    library is touched: CPU tensors, wrong dtypes and wrong shapes are refused first."""
+    if not isinstance(stats, (tuple, list)) or len(stats) != 3 or all(t is None for t in stats):
+        raise RuntimeError("contrib_stats must be (weight_sum, weight_max, pixel_count) with at least one tensor")
+    dev = None
+    for name, t, dt in zip(("weight_sum", "weight_max", "pixel_count"), stats, (torch.float32, torch.float32, torch.int32)):
+        if t is None:
+            continue
+        tn = str(dt).replace("torch.", "")
+        if t.dtype != dt:
+            raise RuntimeError(f"{name} must be {tn} (got {t.dtype})")
+        if tuple(t.shape) != (P,) or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous {tn} tensor with P = {P} elements (got shape {tuple(t.shape)})")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} must be a HIP (cuda) tensor (got {t.device}); the HIP rasterizer has no CPU path")
+        dev = t.device if dev is None else dev
+        if t.device != dev:
+            raise RuntimeError(f"{name} must be on {dev} (got {t.device})")
+    return dev
+
+
+def contrib_pixel_weight(pixel_weight, W, H, device):
+    """The per-pixel weight map m of the weight sums: (H, W) or (1, H, W) float32 on `device`, or None (= 1) -> contiguous or None."""
+    if pixel_weight is None:
+        return None
+    if tuple(pixel_weight.shape) not in ((H, W), (1, H, W)):
+        raise RuntimeError(f"pixel_weight must have shape ({H}, {W}) or (1, {H}, {W}), got {tuple(pixel_weight.shape)}")
+    if pixel_weight.dtype != torch.float32:
+        raise RuntimeError(f"pixel_weight must be float32 (got {pixel_weight.dtype})")
+    return _dev_f32(pixel_weight, device, "pixel_weight")
+
+
+def gaussian_contributions(geomBuffer, binningBuffer, imgBuffer, num_rendered, P, W, H, stats, pixel_weight=None, debug=0):
+    """Per-Gaussian blend-weight statistics of the view whose forward left the three state buffers (of any variant), updated in place:
+    weight_sum += sum_p m(p) w(p), weight_max = max(itself, max_p w(p)), pixel_count += pixels blended into, with w = alpha * T of the
+    forward and m = pixel_weight ((H, W) or (1, H, W); None = 1).  Gaussians that blended nowhere keep their values.  No gradients, no
+    atomics; nothing of the state is written, so the backward of the same forward may still follow."""
+    P, R, W, H = int(P), int(num_rendered), int(W), int(H)
+    dev = contrib_stat_tensors(stats, P)
+    m = contrib_pixel_weight(pixel_weight, W, H, dev)
+    for name, t in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imgBuffer", imgBuffer)):
+        if t.numel() != 0 and t.device != dev:
+            raise RuntimeError(f"{name} must be on {dev} (got {t.device}); the HIP rasterizer has no CPU path")
+    L = lib()
+    with torch.cuda.device(dev):
+        scratch = None
+        if P > 0 and R > 0:
+            scratch = torch.empty((L.gsr_contrib_scratch_bytes(P, R),), dtype=torch.uint8, device=dev)
+        _check(L.gsr_contributions(P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(m), *(_ptr(t) for t in stats),
+                                   _ptr(scratch), _stream(dev), _dbg(debug)))
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------

@@ -21,19 +21,22 @@ def cpu_deep_copy_tuple(input_tuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None, antialiasing=False):
-    """reference __init__.py:22-45 (+ the optional densification-statistics tensors and the screen-space filter, see
-    GaussianRasterizer)"""
+                        raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None):
+    """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter and the blend-weight
+    statistics, see GaussianRasterizer)"""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None)
+                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
+                                     contrib_stats, contrib_pixel_weight)
 
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                    raster_settings, depth_alpha, densify_stats=None, antialiasing=False):
+                                    raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
+                                    contrib_pixel_weight=None):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
     _C.aux_mode(depth_alpha)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha)
+                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
+                                     contrib_stats, contrib_pixel_weight)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -44,7 +47,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None):
+                raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
+                contrib_pixel_weight=None):
+        if contrib_stats is not None:   # refused before anything runs
+            _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
         args = (
             raster_settings.bg,
@@ -83,6 +89,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise ex
         else:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args, **kw)
+
+        if contrib_stats is not None:
+            # the blend-weight statistics of this view (include/gsr_contrib.h), from the state the render just left: once per forward,
+            # gradients enabled or not, never in backward
+            _C.gaussian_contributions(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
+                                      raster_settings.image_width, raster_settings.image_height, contrib_stats, contrib_pixel_weight,
+                                      raster_settings.debug)
 
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
@@ -166,6 +179,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
             None,
+            None,
+            None,
         )
 
 
@@ -199,9 +214,16 @@ class GaussianRasterizer(nn.Module):
     antialiasing (extension, default False): upstream's `antialiasing=True`, the screen-space filter of Mip-Splatting.  The projected
     covariance keeps its 0.3 px^2 dilation, and the opacity is scaled by rho = sqrt(max(2.5e-5, det(Sigma) / det(Sigma + 0.3 I))), so a
     sub-pixel Gaussian keeps the footprint integral of its undilated self; gradients include d rho (include/gsr_aa.h).  Combines with
-    depth_alpha.  A bool; anything else raises TypeError."""
+    depth_alpha.  A bool; anything else raises TypeError.
 
-    def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False):
+    contrib_stats (extension, optional): (weight_sum, weight_max, pixel_count) -- float32, float32 and int32 [P] tensors, any of them
+    None -- that forward() updates in place right after the render, with or without gradients enabled, from the blend weights
+    w = alpha * T of this view: weight_sum += sum over pixels of m w, weight_max = max(itself, max w), pixel_count += pixels blended
+    into; Gaussians that blended nowhere keep their values, so a sweep over views accumulates (include/gsr_contrib.h).
+    contrib_pixel_weight: the map m, (H, W) or (1, H, W) float32, default 1.  The returned tuple is unchanged, and the backward is too."""
+
+    def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
+                 contrib_pixel_weight=None):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
@@ -209,6 +231,8 @@ class GaussianRasterizer(nn.Module):
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
         self.depth_alpha = depth_alpha
+        self.contrib_stats = contrib_stats
+        self.contrib_pixel_weight = contrib_pixel_weight
 
     def markVisible(self, positions):
         # Mark visible points (based on frustum culling for camera) with a boolean
@@ -242,6 +266,7 @@ class GaussianRasterizer(nn.Module):
         if self.depth_alpha is not None:
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
-                                                   self.antialiasing)
+                                                   self.antialiasing, self.contrib_stats, self.contrib_pixel_weight)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing)
+                                   cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
+                                   self.contrib_pixel_weight)

@@ -82,10 +82,15 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                depth_alpha=None, antialiasing=False):
+                depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None):
+        if contrib_stats is not None:   # refused before anything runs
+            _C.contrib_stat_tensors(contrib_stats, int(xyz.size(0)))
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps = _leaf_forward(
             None if depth_alpha is None else _C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation,
             raster_settings, antialiasing)
+        if contrib_stats is not None:   # the blend-weight statistics of this view (GaussianRasterizer): once per forward, never in backward
+            _C.gaussian_contributions(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width, raster_settings.image_height,
+                                      contrib_stats, contrib_pixel_weight, raster_settings.debug)
         ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
         ctx.antialiasing = antialiasing
         # after the state: the aux state of the maps, and the opacity logits that the anti-aliased backward reads (the records hold
@@ -123,21 +128,22 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                     hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
                     x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None)
-        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None
+        return d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None
 
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                             depth_alpha=None, antialiasing=False):
+                             depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
     -> (color (3,H,W), radii (P,) int32); with depth_alpha = "depth" / "invdepth" -> (color, radii, depth, alpha), the maps of
     GaussianRasterizer(raster_settings, depth_alpha=...).  antialiasing: the screen-space filter of
-    GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always."""
+    GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always.
+    contrib_stats / contrib_pixel_weight: the blend-weight statistics of GaussianRasterizer, updated by the forward."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
     return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats,
-                                         depth_alpha, _C.aa_flag(antialiasing))
+                                         depth_alpha, _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight)
 
 
 class FusedAdam(torch.optim.Optimizer):
