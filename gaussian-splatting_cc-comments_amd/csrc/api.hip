@@ -946,7 +946,9 @@ extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_a
 }
 
 // aux: 0 or a GSR_AUX_* mode; aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h), NULL: the default ones
-static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities)
+// cam: NULL, or the camera gradients (include/gsr_cam.h; checked by the caller): the twin kernels, then the fold of their rows
+static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities,
+                                       const gsr_cam_args* cam = nullptr)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
@@ -956,8 +958,15 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	if (first < 0 || count < 0 || (int64_t)first + count > b.P || (first & 63) || (out_row0 != 0 && out_row0 != first))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: bad range [%d, %d + %d) of %d Gaussians (first must be a multiple "
 		                "of 64, out_row0 must be 0 or first)", first, first, count, b.P);
-	if (count == 0) return GSR_OK;
 	hipStream_t s = (hipStream_t)b.stream;
+	if (cam && count == 0) {   // no Gaussian: the fold of no rows writes the 35 zeros
+		{
+			GsrProfScope p(s, "camera_grad");
+			gsr_launch_camera_grad_fold((const float*)cam->scratch, 0, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
+		}
+		return gsr_stage_done(s, b.debug, "camera_grad");
+	}
+	if (count == 0) return GSR_OK;
 	GsrGaussianBackwardArgs a = {};
 	a.leaf = b.leaf; a.shs_rest = b.shs_rest; a.dL_dsh_rest = b.dL_dsh_rest;
 	a.P = b.P; a.D = b.D; a.M = b.M; a.W = b.width; a.H = b.height;
@@ -975,9 +984,15 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, aa_opacities, s, aux);
+		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam ? (float*)cam->scratch : nullptr);
 	}
-	return gsr_stage_done(s, b.debug, "gaussian_backward");
+	if (!cam) return gsr_stage_done(s, b.debug, "gaussian_backward");
+	if ((rc = gsr_stage_done(s, b.debug, "gaussian_backward"))) return rc;
+	{
+		GsrProfScope p(s, "camera_grad");
+		gsr_launch_camera_grad_fold((const float*)cam->scratch, (int)gsr_cam_rows(count), cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
+	}
+	return gsr_stage_done(s, b.debug, "camera_grad");
 }
 
 extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
@@ -1001,6 +1016,29 @@ extern "C" int gsr_backward_gaussians_aa(const gsr_backward_args* args, int anti
 	if (antialiasing && args && args->P > 0 && count > 0 && !opacities)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians_aa: the opacity input is NULL");
 	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr);
+}
+
+// ---- camera gradients (include/gsr_cam.h) ----
+extern "C" size_t gsr_cam_bytes(int P) { return (gsr_cam_rows(P) > 0 ? gsr_cam_rows(P) : 1) * 32 * sizeof(float); }
+
+extern "C" int gsr_backward_gaussians_cam(const gsr_backward_args* args, int antialiasing, const float* opacities, const gsr_aux_args* aux,
+                                          const gsr_cam_args* cam, int first, int count, int out_row0)
+{
+	if (!cam) return gsr_backward_gaussians_aa(args, antialiasing, opacities, aux, first, count, out_row0);
+	const char* who = "gsr_backward_gaussians_cam";
+	int rc;
+	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	if (!cam->dL_dviewmatrix || !cam->dL_dprojmatrix || !cam->dL_dcampos)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dviewmatrix, dL_dprojmatrix or dL_dcampos is NULL", who);
+	if (!cam->scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam is NULL", who);
+	if (!aligned16(cam->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam must be 16-byte aligned", who);
+	if (first != 0 || count != args->P)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera gradients need the whole scene in one call (first 0, count %d; got %d, %d): "
+		                "the part-by-part pipeline of view-parallel mode has no camera form", who, args->P, first, count);
+	if (args->P > 0 && args->shs && !args->cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
+	if (antialiasing && args->P > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, cam);
 }
 
 static int gsr_backward_whole(const gsr_backward_args& a)

@@ -7,6 +7,7 @@
 // rasterize_points.cu:168-178: every output element is written exactly once.
 #include "gsr_internal.h"
 #include "gsr_aa.h"
+#include "gsr_depth_key.h"   // gsr_sync()
 #include <type_traits>
 
 __device__ __forceinline__ GsrVec3 gsr_dnormvdv(GsrVec3 v, GsrVec3 dv)  // auxiliary.h:109-120
@@ -53,9 +54,11 @@ __device__ __forceinline__ void gsr_sh_basis(int deg, float x, float y, float z,
 // ddir9: d(colour channel)/d(unit direction) as the forward kernel left it (gsr_sh_dcolor_ddir): the SH row itself is
 // not needed here.  write_dsh: writes dL_dsh rows [0, (D+1)^2) and zeros the rest up to M; otherwise only the
 // view-direction term of dL_dmean is produced (view-parallel mode, see gsr_sh_grad_from_views).
+template <bool DM = false>
 __device__ __forceinline__ void gsr_sh_backward(int deg, int M, GsrVec3 pos, const float* campos, const float* ddir9,
                                                 uint8_t clamp_bits, const float* dL_dcolor, float* dL_dmean,
-                                                float* dL_dsh, bool write_dsh, float* dL_dRGB_out, float* basis_out = nullptr)
+                                                float* dL_dsh, bool write_dsh, float* dL_dRGB_out, float* basis_out = nullptr,
+                                                float* dm_out = nullptr)   // DM: dm_out receives dL/d(mean - campos) itself (camera gradients)
 {
 	GsrVec3 dir_orig = {pos.x - campos[0], pos.y - campos[1], pos.z - campos[2]};
 	float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
@@ -83,6 +86,7 @@ __device__ __forceinline__ void gsr_sh_backward(int deg, int M, GsrVec3 pos, con
 	GsrVec3 ddir = {dd0, dd1, dd2};
 	GsrVec3 dm = gsr_dnormvdv(dir_orig, ddir);
 	dL_dmean[0] += dm.x; dL_dmean[1] += dm.y; dL_dmean[2] += dm.z;
+	if constexpr (DM) { dm_out[0] = dm.x; dm_out[1] = dm.y; dm_out[2] = dm.z; }
 }
 
 // backward.cu:281-345
@@ -187,10 +191,27 @@ __device__ __forceinline__ void gsr_add_slot(const GsrGradSlot* __restrict__ slo
 // AA: the anti-aliased path (include/gsr_aa.h): the record holds opacity * rho, so the opacity input comes from a.opacities
 // (GsrGaussianBackwardArgsAA); dL/dopacity = dL/dopacity_record * rho, and dL/drho = dL/dopacity_record * opacity joins dL/da, db, dc
 // (the undilated 2D covariance, gsr_aa.h) before they reach dL/dcov3D and the dL/dT chain.
+// CAM: the camera gradients (include/gsr_cam.h).  Every visible Gaussian's terms of dL/dviewmatrix, dL/dprojmatrix and dL/dcampos are
+// the other halves of product rules whose first halves go into dL/dmean3D.  The sums are whole-wave DPP (gsr_wave_sum_to_lane63), so
+// they cannot sit inside the branch of the visible lanes: the branch is closed behind the projection block, the view and projection
+// rows are summed from their 15 factors (zeros in the culled and out-of-range lanes), the branch is reopened for the SH and covariance
+// backward, and dL/dcampos follows it.  Lane 63 stores the wave's row of GSR_CAM_ROW floats, four at a time as its groups finish:
+//   [4 i + k] = sum dL/dvm[4 k + i] (k < 3), [4 i + 3] = sum dL/dvm[12 + i]     i < 3: rows of the view matrix
+//   [12 + 4 j + k] = sum dL/dproj[4 k + r_j], [12 + 4 j + 3] = sum dL/dproj[12 + r_j]   r_j = 0, 1, 3
+//   [24 + k] = sum dL/dcampos[k], [27] = 0; [28, 32) is padding that nobody reads
+// gsr_camera_grad_fold_kernel adds the rows.  The arguments get the row pointer behind them in a struct of its own, so the other
+// instantiations keep their argument layout and their instruction stream.
+#define GSR_CAM_ROW 32
+template <typename Base>
+struct GsrGaussianBackwardCam : Base {
+	float* cam_partials;   // [waves of the launch][GSR_CAM_ROW]
+};
 #define GSR_GB_THREADS 64
-template <bool LEAF, int AUX, bool AA>
+template <bool LEAF, int AUX, bool AA, bool CAM>
 __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
-	typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type a, int sh_via_lds, int skip_dsh)
+	typename std::conditional<CAM, GsrGaussianBackwardCam<typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type>,
+	                          typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type>::type a,
+	int sh_via_lds, int skip_dsh)
 {
 	// staging of the dL/dsh output block: rows of 13 float4; the packed layout goes out in two halves of 32 rows
 	// (6.6 KB per wave), the split leaf tensors as one linear 12 KB block
@@ -325,6 +346,10 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 	float basis_keep[16];             // SH basis at the view direction (entries >= (D+1)^2 zero), visible Gaussians
 #pragma unroll
 	for (int k = 0; k < 16; k++) basis_keep[k] = 0.f;
+	// CAM: the factors of the camera terms, zero unless the Gaussian is visible: dL/dt (with the depth value's dL/dz), dL/dW row by
+	// row, the three row factors of dL/dprojmatrix, and dL/d(mean - campos)
+	float cam_dt[3] = {0.f, 0.f, 0.f}, cam_dW[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+	float cam_p[3] = {0.f, 0.f, 0.f}, cam_dm[3] = {0.f, 0.f, 0.f};
 
 	if (visible) {
 		// ---- computeCov2DCUDA, backward.cu:144-277 ----
@@ -418,42 +443,54 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 			dmean3D[1] += dz * vm[6];
 			dmean3D[2] += dz * vm[10];
 		}
-
-		if (a.shs) {
-			if (sh_via_lds) {
-				// dL_dsh = basis x dL/dRGB: kept as its two factors until the block store below
-				gsr_sh_backward(a.D, M, mean, a.cam_pos, ddir9, clamp_bits, dcolor, dmean3D, nullptr, false, dRGB, basis_keep);
-				if (!skip_dsh && LEAF) {
-					const int used_sh = (a.D + 1) * (a.D + 1);
-					float o[48];
-#pragma unroll
-					for (int e = 0; e < 48; e++) o[e] = (e / 3 < used_sh) ? basis_keep[e / 3] * dRGB[e % 3] : 0.f;
-					gsr_sh_lin_row_put(reinterpret_cast<float*>(s_sh[wave]), lane, o);
-				}
-			} else if (LEAF) {
-				const int used = (a.D + 1) * (a.D + 1);
-				float basis[16];
-				gsr_sh_backward(a.D, used, mean, a.cam_pos, ddir9, clamp_bits, dcolor, dmean3D, nullptr, false, dRGB, basis);
-#pragma unroll
-				for (int e = 0; e < 48; e++) dsh_local[e] = (e / 3 < used) ? basis[e / 3] * dRGB[e % 3] : 0.f;
-			} else {
-				gsr_sh_backward(a.D, M, mean, a.cam_pos, ddir9, clamp_bits, dcolor, dmean3D, dsh_global, !skip_dsh, dRGB);
+		if constexpr (CAM) {
+			// the other half of the product rules above: t = V mean, T = W J (J's entries as gsr_cov2d forms them), p_hom = P mean
+			const float J00 = h_x / t.z, J11 = h_y / t.z;
+			const float J02 = -(h_x * t.x) / (t.z * t.z), J12 = -(h_y * t.y) / (t.z * t.z);
+			cam_dt[0] = dL_dtx; cam_dt[1] = dL_dty; cam_dt[2] = dL_dtz;
+			if (AUX) {
+				const float dv = acc[NACC - 1];
+				cam_dt[2] += AUX == GSR_AUX_INVDEPTH ? -dv / (t.z * t.z) : dv;
 			}
+			cam_dW[0] = J00 * dL_dT00; cam_dW[1] = J00 * dL_dT01; cam_dW[2] = J00 * dL_dT02;
+			cam_dW[3] = J11 * dL_dT10; cam_dW[4] = J11 * dL_dT11; cam_dW[5] = J11 * dL_dT12;
+			cam_dW[6] = J02 * dL_dT00 + J12 * dL_dT10; cam_dW[7] = J02 * dL_dT01 + J12 * dL_dT11; cam_dW[8] = J02 * dL_dT02 + J12 * dL_dT12;
+			cam_p[0] = gx2 * m_w; cam_p[1] = gy2 * m_w; cam_p[2] = -(mul1 * gx2 + mul2 * gy2);
 		}
-		if (a.scales)
-			gsr_cov3d_backward(sc, a.scale_modifier, q, dcov, dscale, drot);
-		if (LEAF) {
-			// exp backward: grad * result;  sigmoid backward: grad * ((1 - y) * y)
-			dscale[0] *= sc[0]; dscale[1] *= sc[1]; dscale[2] *= sc[2];
-			const float o = leaf_opacity;
-			dop = dop * ((1.0f - o) * o);
-			// F.normalize backward: y = x / d, d = clamp_min(||x||, 1e-12)
-			float gd = 0.f;
+
+		if constexpr (!CAM) {
+#include "gaussian_backward_tail.inc"
+		}
+	}
+
+	if constexpr (CAM) {
+		// ---- the wave's row of camera partials: whole-wave sums in the DPP tree's fixed order; culled lanes add exact zeros ----
+		float4* row = reinterpret_cast<float4*>(a.cam_partials) + (size_t)(blockIdx.x * (GSR_GB_THREADS / 64) + wave) * (GSR_CAM_ROW / 4);
+		const float mx = visible ? mean.x : 0.f, my = visible ? mean.y : 0.f, mz = visible ? mean.z : 0.f;  // (a culled mean may be anything)
 #pragma unroll
-			for (int k = 0; k < 4; k++) gd += -drot[k] * q_raw[k] / (q_den * q_den);
-			const float r = (q_den > 1e-12f) ? gd / q_den : 0.f;
+		for (int i = 0; i < 3; i++) {   // row i of the view matrix: dL/dvm[4 k + i] = dL/dt_i mean_k + dL/dW[i][k], dL/dvm[12 + i] = dL/dt_i
+			const float v0 = gsr_wave_sum_to_lane63(cam_dt[i] * mx + cam_dW[3 * i]);
+			const float v1 = gsr_wave_sum_to_lane63(cam_dt[i] * my + cam_dW[3 * i + 1]);
+			const float v2 = gsr_wave_sum_to_lane63(cam_dt[i] * mz + cam_dW[3 * i + 2]);
+			const float v3 = gsr_wave_sum_to_lane63(cam_dt[i]);
+			if (lane == 63) row[i] = make_float4(v0, v1, v2, v3);
+		}
 #pragma unroll
-			for (int k = 0; k < 4; k++) drot[k] = drot[k] / q_den + q_raw[k] * r;
+		for (int j = 0; j < 3; j++) {   // rows 0, 1 and 3 of the projection matrix
+			const float v0 = gsr_wave_sum_to_lane63(cam_p[j] * mx);
+			const float v1 = gsr_wave_sum_to_lane63(cam_p[j] * my);
+			const float v2 = gsr_wave_sum_to_lane63(cam_p[j] * mz);
+			const float v3 = gsr_wave_sum_to_lane63(cam_p[j]);
+			if (lane == 63) row[3 + j] = make_float4(v0, v1, v2, v3);
+		}
+		if (visible) {   // (reopened: SH, covariance and leaf backward of the visible lanes)
+#include "gaussian_backward_tail.inc"
+		}
+		{
+			const float v0 = gsr_wave_sum_to_lane63(-cam_dm[0]);
+			const float v1 = gsr_wave_sum_to_lane63(-cam_dm[1]);
+			const float v2 = gsr_wave_sum_to_lane63(-cam_dm[2]);
+			if (lane == 63) row[6] = make_float4(v0, v1, v2, 0.f);
 		}
 	}
 
@@ -539,26 +576,98 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 
 // one instantiation per (LEAF, depth-and-alpha mode, AA): the AA ones are those that receive the struct with the opacity input
 template <typename Args>
-static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux)
+static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux, float* cam_partials)
 {
 	constexpr bool AA = std::is_same<Args, GsrGaussianBackwardArgsAA>::value;
 	// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
 	const int skip_dsh = (a.shs && !a.dL_dsh) ? 1 : 0;  // view-parallel mode (include/gsr.h)
 	int sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
 	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
+	const dim3 grid((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS);
 	gsr_variant(a.leaf, aux, AA, [&](auto LEAF, auto AUX, auto) {
-		gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA>, dim3((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS), dim3(GSR_GB_THREADS), 0, s,
+		if (cam_partials) {   // the camera-gradient twin (include/gsr_cam.h): the same arguments with the row pointer behind them
+			GsrGaussianBackwardCam<Args> c;
+			static_cast<Args&>(c) = a;
+			c.cam_partials = cam_partials;
+			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
+			return;
+		}
+		gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, false>, grid, dim3(GSR_GB_THREADS), 0, s,
 		           nullptr, nullptr, a, sh_via_lds, skip_dsh);
 	});
 }
 
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux)
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials)
 {
-	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux);
+	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux, cam_partials);
 	GsrGaussianBackwardArgsAA x;
 	static_cast<GsrGaussianBackwardArgs&>(x) = a;
 	x.opacities = aa_opacities;
-	gsr_launch_gaussian_backward_t(x, s, aux);
+	gsr_launch_gaussian_backward_t(x, s, aux, cam_partials);
+}
+
+// ---- fold of the camera partials (include/gsr_cam.h) ---------------------------------------------------------------------------
+// One workgroup per float4 column of the rows (seven: the 27 terms and one zero), so a workgroup's sum depends on no other workgroup
+// and on nothing that is scheduled: no atomics, no counters, one launch.  The order is a tree whose shape follows from the number of
+// rows alone: thread t takes the rows t, t + 1024, ..., four at a time as (r0 + r1) + (r2 + r3) added to its running sum, then a
+// ragged tail one by one; the 64 sums of a wave go through the DPP tree of gsr_wave_sum_to_lane63; thread 0 adds the sixteen wave sums
+// as a balanced tree and writes the column's four outputs -- and, in the first workgroup of each matrix, that matrix's four exact zeros.
+#define GSR_CAM_FOLD_THREADS 1024
+#define GSR_CAM_FOLD_GROUPS 7
+__device__ __forceinline__ float4 gsr_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+__global__ void __launch_bounds__(GSR_CAM_FOLD_THREADS) gsr_camera_grad_fold_kernel(const float4* __restrict__ partials, int nrows,
+                                                                                  float* __restrict__ dL_dviewmatrix,
+                                                                                  float* __restrict__ dL_dprojmatrix,
+                                                                                  float* __restrict__ dL_dcampos)
+{
+	__shared__ float4 s_wave[GSR_CAM_FOLD_THREADS / 64];
+	const int col = blockIdx.x;   // float4 column of the rows
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const float4* p = partials + col;
+	float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+	int r = threadIdx.x;
+	for (; r + 3 * GSR_CAM_FOLD_THREADS < nrows; r += 4 * GSR_CAM_FOLD_THREADS) {
+		const float4 r0 = p[(size_t)r * (GSR_CAM_ROW / 4)];
+		const float4 r1 = p[(size_t)(r + GSR_CAM_FOLD_THREADS) * (GSR_CAM_ROW / 4)];
+		const float4 r2 = p[(size_t)(r + 2 * GSR_CAM_FOLD_THREADS) * (GSR_CAM_ROW / 4)];
+		const float4 r3 = p[(size_t)(r + 3 * GSR_CAM_FOLD_THREADS) * (GSR_CAM_ROW / 4)];
+		acc = gsr_add4(acc, gsr_add4(gsr_add4(r0, r1), gsr_add4(r2, r3)));
+	}
+	for (; r < nrows; r += GSR_CAM_FOLD_THREADS) acc = gsr_add4(acc, p[(size_t)r * (GSR_CAM_ROW / 4)]);
+	acc.x = gsr_wave_sum_to_lane63(acc.x);
+	acc.y = gsr_wave_sum_to_lane63(acc.y);
+	acc.z = gsr_wave_sum_to_lane63(acc.z);
+	acc.w = gsr_wave_sum_to_lane63(acc.w);
+	if (lane == 63) s_wave[wave] = acc;
+	gsr_sync();
+	if (threadIdx.x != 0) return;
+	float4 t[GSR_CAM_FOLD_THREADS / 64];
+#pragma unroll
+	for (int i = 0; i < GSR_CAM_FOLD_THREADS / 64; i++) t[i] = s_wave[i];
+#pragma unroll
+	for (int n = GSR_CAM_FOLD_THREADS / 128; n > 0; n >>= 1)
+#pragma unroll
+		for (int i = 0; i < n; i++) t[i] = gsr_add4(t[2 * i], t[2 * i + 1]);
+	const float4 v = t[0];
+	if (col < 3) {          // row `col` of the view matrix
+		dL_dviewmatrix[col] = v.x; dL_dviewmatrix[4 + col] = v.y; dL_dviewmatrix[8 + col] = v.z; dL_dviewmatrix[12 + col] = v.w;
+		if (col == 0) { dL_dviewmatrix[3] = 0.f; dL_dviewmatrix[7] = 0.f; dL_dviewmatrix[11] = 0.f; dL_dviewmatrix[15] = 0.f; }
+	} else if (col < 6) {   // rows 0, 1 and 3 of the projection matrix
+		const int rr = col == 5 ? 3 : col - 3;
+		dL_dprojmatrix[rr] = v.x; dL_dprojmatrix[4 + rr] = v.y; dL_dprojmatrix[8 + rr] = v.z; dL_dprojmatrix[12 + rr] = v.w;
+		if (col == 3) { dL_dprojmatrix[2] = 0.f; dL_dprojmatrix[6] = 0.f; dL_dprojmatrix[10] = 0.f; dL_dprojmatrix[14] = 0.f; }
+	} else {
+		dL_dcampos[0] = v.x; dL_dcampos[1] = v.y; dL_dcampos[2] = v.z;
+	}
+}
+
+size_t gsr_cam_rows(int P) { return ((size_t)(P > 0 ? P : 0) + 63) / 64; }
+
+void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s)
+{
+	gsr_launch(gsr_camera_grad_fold_kernel, dim3(GSR_CAM_FOLD_GROUPS), dim3(GSR_CAM_FOLD_THREADS), 0, s, nullptr, nullptr,
+	           reinterpret_cast<const float4*>(partials), nrows, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos);
 }
 
 // ---- view-parallel SH gradient (no reference counterpart) ------------------------------

@@ -9,6 +9,7 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_aux.h"
+#include "../../include/gsr_cam.h"
 #include "gsr_device.h"
 
 #define GSR_PREPROCESS_BLOCK 256  // Gaussians per workgroup of the binning kernels (granularity of their scans)
@@ -290,7 +291,11 @@ struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the slots' tenth word (dL/dv) is summed and chained into dL/dmean3D
 // aa_opacities: NULL, or the anti-aliased kernels with this opacity input: dL/dopacity = dL/dopacity_record * rho, and dL/drho into
 // dL/dcov3D and dL/dmean3D
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux);
+// cam_partials: NULL, or the camera-gradient kernels (include/gsr_cam.h), which also store one row of 32 floats per wave of 64
+// Gaussians there (gsr_cam_rows(count) rows; first must be 0); gsr_launch_camera_grad_fold adds the rows into the 35 outputs
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials = nullptr);
+size_t gsr_cam_rows(int P);
+void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,
                                    int64_t view_stride, float* dL_dsh, hipStream_t s);
 

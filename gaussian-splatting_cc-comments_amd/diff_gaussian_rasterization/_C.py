@@ -64,6 +64,11 @@ class AuxArgs(ctypes.Structure):
     _fields_ = [("mode", _i), ("out_depth", _vp), ("out_alpha", _vp), ("dL_ddepth", _vp), ("dL_dalpha", _vp), ("scratch", _vp)]
 
 
+class CamArgs(ctypes.Structure):
+    """include/gsr_cam.h gsr_cam_args"""
+    _fields_ = [("dL_dviewmatrix", _vp), ("dL_dprojmatrix", _vp), ("dL_dcampos", _vp), ("scratch", _vp)]
+
+
 class AuxLayout(ctypes.Structure):
     _fields_ = [(n, _sz) for n in ("ckpt_depth", "final_D", "total")]
 
@@ -161,6 +166,11 @@ def lib():
                            ("gsr_backward_gaussians_aa", [pb, _i, _vp, pa, _i, _i, _i])):
         getattr(L, name).restype = _i
         getattr(L, name).argtypes = argtypes
+    # include/gsr_cam.h: camera gradients
+    L.gsr_cam_bytes.restype = _sz
+    L.gsr_cam_bytes.argtypes = [_i]
+    L.gsr_backward_gaussians_cam.restype = _i
+    L.gsr_backward_gaussians_cam.argtypes = [pb, _i, _vp, pa, ctypes.POINTER(CamArgs), _i, _i, _i]
     # include/gsr_contrib.h: per-Gaussian blend-weight statistics
     L.gsr_contrib_scratch_bytes.restype = _sz
     L.gsr_contrib_scratch_bytes.argtypes = [_i, _i64]
@@ -214,17 +224,41 @@ def aa_flag(antialiasing):
     return antialiasing
 
 
+def camera_flag(camera_grads):
+    """The `camera_grads` keyword -> bool; anything but a bool raises TypeError, like `antialiasing`."""
+    if not isinstance(camera_grads, bool):
+        raise TypeError(f"camera_grads must be True or False, got {camera_grads!r}")
+    return camera_grads
+
+
+def camera_backward_args(P, device):
+    """CamArgs of a backward with camera gradients (include/gsr_cam.h) -> (struct, (dL_dviewmatrix (4,4), dL_dprojmatrix (4,4),
+    dL_dcampos (3,))): the three outputs, which the fold kernel writes in full, and the scratch of P Gaussians, all from torch's
+    allocator; the struct keeps them alive until the calls that use it have been enqueued."""
+    f32 = dict(dtype=torch.float32, device=device)
+    outs = (torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32))
+    scratch = torch.empty((lib().gsr_cam_bytes(int(P)),), dtype=torch.uint8, device=device)
+    c = CamArgs()
+    c.dL_dviewmatrix, c.dL_dprojmatrix, c.dL_dcampos = (t.data_ptr() for t in outs)
+    c.scratch = scratch.data_ptr()
+    c._keep = outs + (scratch,)
+    return c, outs
+
+
 # ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
-def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None):
+def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None):
     """-> (function of L, the arguments that precede the default entry point's own).  stage: "preprocess" | "render" (the two forward
     calls) | "blend" | "gaussians" (the two backward stages: their leading arguments follow the gsr_backward_args pointer); leaf: the
     inputs are the optimiser's leaves (fused_params.py); x: the AuxArgs of a call with depth and alpha maps, or None; aa: the
     screen-space filter, whose per-Gaussian backward reads the forward's opacity input at address `opacities`.  The *_aa entry
-    points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice."""
+    points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice.
+    cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None."""
     xr = None if x is None else ctypes.byref(x)
     if stage == "preprocess":
         name = "gsr_forward_preprocess_leaf" if leaf else "gsr_forward_preprocess"
         name, lead = (name + "_aa", (1, xr)) if aa else (name + "_aux", (xr,)) if x is not None else (name, ())
+    elif stage == "gaussians" and cam is not None:
+        name, lead = "gsr_backward_gaussians_cam", (int(aa), opacities if aa else None, xr, ctypes.byref(cam))
     elif stage == "gaussians":
         name, lead = ("gsr_backward_gaussians_aa", (1, opacities, xr)) if aa else \
             ("gsr_backward_gaussians_aux", (xr,)) if x is not None else ("gsr_backward_gaussians", ())
@@ -345,12 +379,15 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
     return x
 
 
-def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None):
+def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
     logits in leaf mode) when the screen-space filter was on, else None; before_part(k) / after_part(k): called around part k's pass
-    (view_parallel.py sets the part's output pointers and starts its collectives there)."""
+    (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_backward_args()) when
+    the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`."""
+    if cam is not None and parts is not None:
+        raise NotImplementedError("camera gradients need the whole scene in one per-Gaussian pass: not with `parts`")
     L = lib()
     ra = ctypes.byref(a)
     blend, lead = _entry(L, "blend", x=x)
@@ -358,7 +395,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
-    gaussians, lead = _entry(L, "gaussians", x=x, aa=aa, opacities=opacities)
+    gaussians, lead = _entry(L, "gaussians", x=x, aa=aa, opacities=opacities, cam=cam)
     for k, (first, count) in enumerate(((0, a.P),) if parts is None else parts):
         if before_part is not None:
             before_part(k)
@@ -368,7 +405,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     release_scratch(scratch, device)
 
 
-def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities):
+def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -376,6 +413,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
     aa = aa_flag(antialiasing)
     if aa and opacities is None:
         raise RuntimeError(f"{who}: antialiasing=True needs the forward's opacities")
+    cam, cam_grads = None, ()
     L = lib()
     dev = means3D.device
     P = int(means3D.size(0))
@@ -404,7 +442,9 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                     (cov3D_precomp, "cov3D_precomp"), (viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"),
                     (dL_dout_color, "dL_dout_color"), (sh, "shs"), (campos, "campos")))
             scratch = backward_scratch(P, R, dev)
-            if stats is None and not aa and aux is None:   # nothing but the reference's backward: one call for both stages
+            if camera_flag(camera_grads):
+                cam, cam_grads = camera_backward_args(P, dev)
+            if stats is None and not aa and aux is None and cam is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
                                       _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                       _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -424,16 +464,18 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh,
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
-                run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None)
+                run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam)
+        elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
+            cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
         debug_out["dL_dconic"] = dL_dconic
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+    return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations) + tuple(cam_grads)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
-                                 debug_out=None, stats=None, antialiasing=False, opacities=None):
+                                 debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -445,24 +487,27 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
       debug_out dict that receives the internal "dL_dconic" tensor (tests)
       stats     (xyz_gradient_accum, denom, max_radii2D) float32 [P] tensors updated in place for the Gaussians
                 visible in this view (train.py:157-159, gaussian_model.py:599-602); any of them may be None
-      antialiasing  the backward of an antialiasing=True forward; `opacities` is then its opacity input (include/gsr_aa.h)"""
+      antialiasing  the backward of an antialiasing=True forward; `opacities` is then its opacity input (include/gsr_aa.h)
+      camera_grads  True: three more results behind the eight, dL_dviewmatrix (4,4), dL_dprojmatrix (4,4) and dL_dcampos (3,) of the
+                    camera tensors as the kernels read them (include/gsr_cam.h)"""
     return _backward_plain("rasterize_gaussians_backward", None,
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities)
+                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads)
 
 
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
-                                             dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None):
+                                             dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
+                                             camera_grads=False):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
-    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities: as there."""
+    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads: as there."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities)
+                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------

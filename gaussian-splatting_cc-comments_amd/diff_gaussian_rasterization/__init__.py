@@ -21,34 +21,52 @@ def cpu_deep_copy_tuple(input_tuple):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None):
-    """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter and the blend-weight
-    statistics, see GaussianRasterizer)"""
+                        raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
+                        camera_grads=False):
+    """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
+    statistics and the camera gradients, see GaussianRasterizer)"""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                                     contrib_stats, contrib_pixel_weight)
+                                     contrib_stats, contrib_pixel_weight, *camera_inputs(raster_settings, camera_grads))
+
+
+def camera_inputs(raster_settings, camera_grads):
+    """camera_grads=True: the three camera tensors of the settings, which the autograd Functions then take as three more inputs behind
+    their own; False: none.  Anything but a bool raises TypeError."""
+    if not _C.camera_flag(camera_grads):
+        return ()
+    return (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
+
+
+def camera_grad_results(needs, grads, inputs):
+    """The three camera gradients of a backward, each shaped like its input, None where the input does not require one."""
+    return tuple(g.reshape(t.shape) if n else None for n, g, t in zip(needs, grads, inputs))
 
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
-                                    contrib_pixel_weight=None):
+                                    contrib_pixel_weight=None, camera_grads=False):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
     _C.aux_mode(depth_alpha)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                                     contrib_stats, contrib_pixel_weight)
+                                     contrib_stats, contrib_pixel_weight, *camera_inputs(raster_settings, camera_grads))
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     """The reference's Function, plus (depth_alpha = "depth" / "invdepth") two differentiable per-pixel outputs from the same blend pass
     (include/gsr_aux.h): depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term)
     and alpha A = 1 - T_final.  Colour and radii are bit-identical with and without the maps.  When neither map's gradient reaches the
-    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True)."""
+    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True).
+
+    Camera gradients (include/gsr_cam.h): with the settings' viewmatrix, projmatrix and campos as three more inputs behind the others,
+    the backward returns their gradients too -- the camera-gradient kernels run when at least one of the three requires a gradient,
+    the default ones otherwise.  The kernels read the tensors of the settings; the inputs only tie them into the graph."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None):
+                contrib_pixel_weight=None, *camera):
         if contrib_stats is not None:   # refused before anything runs
             _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
@@ -102,6 +120,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
+        ctx.camera = len(camera) == 3
         # after the reference's ten: the aux state of the maps, and the opacity input that the anti-aliased backward reads (the records
         # hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
@@ -121,6 +140,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
                                          dtype=torch.float32, device=means3D.device)
         kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
+        cam_needs = tuple(ctx.needs_input_grad[14:17]) if ctx.camera else ()
+        if any(cam_needs):
+            kw["camera_grads"] = True
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
@@ -150,7 +172,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
             grads = _C.rasterize_gaussians_backward_depth_alpha(ctx.depth_alpha, *args[:-1], extra[0], hw(grad_depth), hw(grad_alpha),
                                                                 raster_settings.debug, stats=ctx.densify_stats, **kw)
-        elif raster_settings.debug and ctx.depth_alpha is None:  # reference __init__.py:141-148
+        elif raster_settings.debug and ctx.depth_alpha is None and not any(cam_needs):  # reference __init__.py:141-148
             cpu_args = cpu_deep_copy_tuple(args)
             try:
                 grads = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
@@ -163,7 +185,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             # the default backward kernels, at the default cost.)
             grads = _C.rasterize_gaussians_backward(*args, lean=not raster_settings.debug, stats=ctx.densify_stats, **kw)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = grads
+         grad_rotations) = grads[:8]
+        cam_grads = ()
+        if ctx.camera:
+            cam_grads = camera_grad_results(cam_needs, grads[8:], (raster_settings.viewmatrix, raster_settings.projmatrix,
+                                                                   raster_settings.campos)) if any(cam_needs) else (None, None, None)
 
         # gradient order: reference __init__.py:154-164
         return (
@@ -181,6 +207,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
             None,
+            *cam_grads,
         )
 
 
@@ -220,14 +247,22 @@ class GaussianRasterizer(nn.Module):
     None -- that forward() updates in place right after the render, with or without gradients enabled, from the blend weights
     w = alpha * T of this view: weight_sum += sum over pixels of m w, weight_max = max(itself, max w), pixel_count += pixels blended
     into; Gaussians that blended nowhere keep their values, so a sweep over views accumulates (include/gsr_contrib.h).
-    contrib_pixel_weight: the map m, (H, W) or (1, H, W) float32, default 1.  The returned tuple is unchanged, and the backward is too."""
+    contrib_pixel_weight: the map m, (H, W) or (1, H, W) float32, default 1.  The returned tuple is unchanged, and the backward is too.
+
+    camera_grads (extension, default False): with True the settings' viewmatrix, projmatrix and campos take part in autograd as three
+    independent inputs, exactly as the kernels read them: a caller who builds full_proj_transform and camera_center from the pose in
+    torch gets the total derivative.  The gradients are those of the function the backward differentiates for the Gaussians (clamped
+    t.x / t.y constant inside the EWA Jacobian; culling, radii, tile membership and depth order carry none; tanfovx / tanfovy are
+    constants).  When none of the three requires a gradient the default kernels run and nothing is allocated.  A bool; anything else
+    raises TypeError."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
-                 contrib_pixel_weight=None):
+                 contrib_pixel_weight=None, camera_grads=False):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
         self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
+        self.camera_grads = _C.camera_flag(camera_grads)   # the same
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
         self.depth_alpha = depth_alpha
@@ -266,7 +301,7 @@ class GaussianRasterizer(nn.Module):
         if self.depth_alpha is not None:
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
-                                                   self.antialiasing, self.contrib_stats, self.contrib_pixel_weight)
+                                                   self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
-                                   self.contrib_pixel_weight)
+                                   self.contrib_pixel_weight, self.camera_grads)

@@ -54,14 +54,18 @@ def _result(image, screenspace_points, radii, aux=None):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
-           depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None):
+           depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
     antialiasing: the screen-space filter with opacity compensation (see GaussianRasterizer); None = getattr(pipe, "antialiasing",
     False).
     contrib_stats / contrib_pixel_weight (extension): see GaussianRasterizer -- the per-Gaussian blend-weight statistics of this view
-    (weight sum, weight max, hit count), updated by the forward on both paths."""
+    (weight sum, weight max, hit count), updated by the forward on both paths.
+    camera_grads: the camera's world_view_transform, full_proj_transform and camera_center take part in autograd (see
+    GaussianRasterizer): pose refinement; None = getattr(pipe, "camera_grads", False)."""
+    if camera_grads is None:
+        camera_grads = getattr(pipe, "camera_grads", False)
     if antialiasing is None:
         antialiasing = getattr(pipe, "antialiasing", False)
     xyz = pc.get_xyz
@@ -72,8 +76,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     except Exception:
         pass
     settings = _settings_for(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
-    # the blend-weight statistics travel only when asked for, as two more keywords of either path
-    contrib = {} if contrib_stats is None else dict(contrib_stats=contrib_stats, contrib_pixel_weight=contrib_pixel_weight)
+    # the optional extensions travel only when asked for, as more keywords of either path: the blend-weight statistics ...
+    extras = {} if contrib_stats is None else dict(contrib_stats=contrib_stats, contrib_pixel_weight=contrib_pixel_weight)
+    if camera_grads is not False:   # the camera gradients travel the same way (a non-bool reaches the check that refuses it)
+        extras["camera_grads"] = camera_grads
 
     python_cov = bool(pipe.compute_cov3D_python)
     python_sh = bool(pipe.convert_SHs_python)
@@ -81,7 +87,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         from fused_params import rasterize_leaf_gaussians
         out = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                        pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha,
-                                       antialiasing=antialiasing, **contrib)
+                                       antialiasing=antialiasing, **extras)
         return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)
 
     inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
@@ -98,5 +104,5 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         inputs["shs"] = pc.get_features
 
     out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha,
-                             antialiasing=antialiasing, **contrib)(**inputs)
+                             antialiasing=antialiasing, **extras)(**inputs)
     return _result(out[0], screenspace_points, out[1], out[2:] if depth_alpha is not None else None)

@@ -239,12 +239,15 @@ class _RasterizeViewParallel(torch.autograd.Function):
 
 
 def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
-                            antialiasing=False):
+                            antialiasing=False, camera_grads=False):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
     DensificationStats.kernel_tensors()).  antialiasing: the screen-space filter of GaussianRasterizer(..., antialiasing=True)."""
     from diff_gaussian_rasterization import _C
+    if _C.camera_flag(camera_grads):
+        raise NotImplementedError("rasterize_view_parallel: camera gradients need the whole scene in one per-Gaussian pass; the "
+                                  "part-by-part pipeline of view-parallel mode has no camera form (include/gsr_cam.h)")
     return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
                                         _C.aa_flag(antialiasing))
 
