@@ -906,7 +906,8 @@ static uint8_t* gsr_slot_valid_of(const gsr_backward_args& a)
 	return (uint8_t*)gsr_binning_view(a.binning, a.P, a.num_rendered, a.width, a.height).tile_keys_alt;
 }
 
-static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_args* aux)
+// absgrad: the ABS variant of the blend kernel (include/gsr_absgrad.h)
+static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_args* aux, bool absgrad = false)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend: args is NULL");
@@ -931,7 +932,7 @@ static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_
 		GsrAuxBlend x;
 		gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
 		                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1,
-		                           gsr_aux_view(aux, a.num_rendered, a.width, a.height, &x));
+		                           gsr_aux_view(aux, a.num_rendered, a.width, a.height, &x), absgrad);
 	}
 	return gsr_stage_done(s, a.debug, "render_backward");
 }
@@ -1089,6 +1090,39 @@ extern "C" int gsr_backward_leaf(int P, int D, int M, int64_t R, int width, int 
 	a.dL_dsh = dL_dfeatures_dc; a.dL_dsh_rest = dL_dfeatures_rest; a.dL_dscale = dL_dlog_scales; a.dL_drot = dL_draw_rotations;
 	a.stream = stream; a.debug = debug;
 	return gsr_backward_whole(a);
+}
+
+// ---- absolute screen-space gradients (include/gsr_absgrad.h) -------------------------------------
+extern "C" int gsr_backward_blend_abs(const gsr_backward_args* args, const gsr_aux_args* aux, int absgrad)
+{
+	if (absgrad != 0 && absgrad != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend_abs: absgrad must be 0 or 1, got %d", absgrad);
+	int rc;
+	if ((rc = gsr_option_check("gsr_backward_blend_abs", 0, aux, true, GSR_AUX_NEEDS_SCRATCH, args && args->P > 0 && args->num_rendered > 0))) return rc;
+	return gsr_backward_blend_impl(args, aux, absgrad != 0);
+}
+
+extern "C" int gsr_absgrad_fold(const gsr_backward_args* args, const gsr_absgrad_args* abs, int first, int count)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_absgrad_fold";
+	if (!args || !abs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args or abs is NULL", who);
+	const gsr_backward_args& a = *args;
+	if (a.P < 0 || a.num_rendered < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (first < 0 || count < 0 || (int64_t)first + count > a.P)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad range [%d, %d + %d) of %d Gaussians", who, first, first, count, a.P);
+	if (!abs->abs_dL_dmean2D && !abs->stat_abs_gradient_accum)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: abs_dL_dmean2D and stat_abs_gradient_accum are both NULL", who);
+	if (count == 0) return GSR_OK;
+	if (!a.geometry || (a.num_rendered > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(a.geometry) || !aligned16(a.binning) || !aligned16(a.scratch))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
+	hipStream_t s = (hipStream_t)a.stream;
+	{
+		GsrProfScope p(s, "absgrad_fold");
+		gsr_launch_absgrad_fold(first, count, gsr_geometry_view(a.geometry, a.P), a.radii, (const GsrGradSlot*)a.scratch, gsr_slot_valid_of(a),
+		                        abs->abs_dL_dmean2D, abs->stat_abs_gradient_accum, s);
+	}
+	return gsr_stage_done(s, a.debug, "absgrad_fold");
 }
 
 // ---- blend-weight statistics (include/gsr_contrib.h) --------------------------------------------

@@ -129,11 +129,7 @@ __device__ __forceinline__ void gsr_cov3d_backward(const float* scale, float mod
 // GSR_SLOT_COOP slots are added by the owning lane; longer runs (a big splat can own > 1000) are
 // added by the whole wave, lanes striding over the run, then reduced with DPP -- so the wave's
 // time no longer follows its single most-loaded lane.  The order is fixed: bitwise reproducible.
-#ifndef GSR_SLOT_COOP
-#define GSR_SLOT_COOP 30   // swept on MI355X at C3: 12 / 18 / 24 / 36 -> 0.172 / 0.164 / 0.166 / 0.171 ms with the slots in depth order (round 2);
-                           // in index order (round 4) a lane's records lie next to its neighbours': 18 / 30 / 58 -> 0.130 / 0.120 / 0.118 ms at C3,
-                           // 0.745 / 0.626 / 0.628 at C5
-#endif
+// (GSR_SLOT_COOP: gsr_internal.h, shared with absgrad.hip)
 #define GSR_NACC 9
 #ifndef GSR_SLOT_ROUND
 #define GSR_SLOT_ROUND 6   // slot records requested per round of the per-lane sum

@@ -10,6 +10,7 @@
 #include "../../include/gsr.h"
 #include "../../include/gsr_aux.h"
 #include "../../include/gsr_cam.h"
+#include "../../include/gsr_absgrad.h"
 #include "gsr_device.h"
 
 #define GSR_PREPROCESS_BLOCK 256  // Gaussians per workgroup of the binning kernels (granularity of their scans)
@@ -25,6 +26,14 @@
 #define GSR_STATUS_NEGMIN (4 + GSR_COUNT_PARTS)
 #define GSR_STATUS_MAX (4 + 2 * GSR_COUNT_PARTS)
 #define GSR_STATUS_WORDS (4 + 3 * GSR_COUNT_PARTS)
+
+// A Gaussian's run of per-tile gradient slots is added by its own lane up to this length and by the whole wave beyond it, in
+// gaussian_backward.hip (gsr_add_slot) and in absgrad.hip alike.
+#ifndef GSR_SLOT_COOP
+#define GSR_SLOT_COOP 30   // swept on MI355X at C3: 12 / 18 / 24 / 36 -> 0.172 / 0.164 / 0.166 / 0.171 ms with the slots in depth order (round 2);
+                           // in index order (round 4) a lane's records lie next to its neighbours': 18 / 30 / 58 -> 0.130 / 0.120 / 0.118 ms at C3,
+                           // 0.745 / 0.626 / 0.628 at C5 (the per-Gaussian backward)
+#endif
 
 static inline size_t gsr_align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 static inline int gsr_grid_x(int W) { return (W + GSR_TILE_X - 1) / GSR_TILE_X; }
@@ -233,7 +242,13 @@ void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point
 void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
                                 const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
                                 uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop,
-                                const GsrAuxBlend* aux);   // t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
+                                const GsrAuxBlend* aux, bool absgrad = false);   // t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
+                                                                                 // absgrad: the ABS variant, which also fills the slots' words 10 and 11 (include/gsr_absgrad.h)
+
+// absgrad.hip: per-Gaussian fold of the slots' words 10 and 11 (include/gsr_absgrad.h) for the Gaussians [first, first + count).
+// radii: NULL = visibility from tiles_touched; slots / slot_valid: NULL when nothing was rendered (every Gaussian then gets zeros)
+void gsr_launch_absgrad_fold(int first, int count, GsrGeometry g, const int* radii, const GsrGradSlot* slots, const uint8_t* slot_valid,
+                             float* abs_dL_dmean2D, float* stat_abs_gradient_accum, hipStream_t s);
 
 // contrib.hip: blend-weight statistics (include/gsr_contrib.h).  scratch: R 16-byte records, then (at gsr_contrib_valid_offset) R validity
 // bytes, which gsr_contributions clears on the stream before the tile pass

@@ -40,8 +40,16 @@ __device__ __forceinline__ float gsr_add_halves(v2f a)
 // its accum_rec (restarted from ckpt_depth / final_D by the depth segments), (v - accum_rec_D) dL/dD in dL/dalpha -- dL/dA enters
 // through the background term (A = 1 - T_final: -T_final (bg . dL/dpix - dL/dA)), and dL/dv = sum alpha T dL/dD is a tenth reduced
 // partial, written to the slot's pad0.  Same slots, same order, no atomics.
-template <bool AUX>
-__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) gsr_render_backward_wave_kernel(
+// ABS (absolute screen-space gradients, include/gsr_absgrad.h): beside the signed moments sum f dx, sum f dy every evaluated pair adds
+// the moduli of its two per-pixel terms of dL/dmean2D, |f (a dx + b dy)| and |f (c dy + b dx)| -- taken per pixel, before any sum --
+// into two more partials; both are reduced over the wave like the AUX variant's tenth value and written, scaled by 0.5 W / 0.5 H, to
+// the slot's pad1 / pad2 (gsr_absgrad_fold_kernel, absgrad.hip, adds them per Gaussian).  The ABS instantiations finish every instance
+// on its own, as the AUX ones do; the other nine (ten) words are computed by the same operations as without ABS.
+// Waves per SIMD: four (at most 128 VGPRs) for every instantiation but <AUX, ABS>.  The AUX variant alone fills the 128 (left
+// to itself the compiler takes 130), and the two accumulators, the halved b and the terms' temporaries of ABS on top spill 10
+// registers to scratch at that limit: that instantiation takes 144 VGPRs and runs three waves per SIMD, without scratch.
+template <bool AUX, bool ABS>
+__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu((AUX && ABS) ? 3 : 4, 4))) gsr_render_backward_wave_kernel(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
 	const GsrSplat* __restrict__ splat, const float4* __restrict__ checkpoints, const float* __restrict__ final_C, const uint32_t* __restrict__ slot_base, const float* __restrict__ bg,
 	const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,
@@ -64,7 +72,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	// and the 64 lanes' v[8] (at 64 + lane); up to GSR_BWD_FLUSH instances wait here and are finished together (gsr_flush below).
 	// 2 KB more per wave: 9.5 KB x 16 waves still fits one CU's 160 KB at 4 waves per SIMD.  The AUX variant keeps the
 	// per-instance finish (its tenth value would leave fewer lanes per flush and its LDS would not fit 16 waves).
-	__shared__ __attribute__((aligned(16))) float s_pend[GSR_WAVES_PER_WG][AUX ? 4 : GSR_BWD_FLUSH * 128];
+	__shared__ __attribute__((aligned(16))) float s_pend[GSR_WAVES_PER_WG][(AUX || ABS) ? 4 : GSR_BWD_FLUSH * 128];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const int slot_id = blockIdx.x * GSR_WAVES_PER_WG + wave;
 	if (slot_id >= nslots) return;  // wave-uniform; no barriers below
@@ -244,6 +252,15 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			if (AUX) { const float4 R5 = rec[5][j]; V = v2f{R5.x, R5.y}; }
 			const v2f dx = X - pfx2;
 			const v2f ax2 = (CA * dx) * dx, bdx = CB * dx;  // this file is compiled with -ffp-contract=off
+			// ABS: a dx + b dy = -2 ((-0.5 a) dx + (-0.5 b) dy): with b halved like a and c, a per-pixel term is one product and one
+			// FMA on f dx, f dy; the factor 2 (exact) joins 0.5 W / 0.5 H at the store
+			v2f CBh = {0.f, 0.f};
+			// Two scalar partials, not the two more v2f partials the feature was first specified with: |.| is a source modifier of the
+			// scalar add but not of the packed one, so a v2f partial would pay a separate pair of ANDs per term, and two v2f are
+			// four registers where this instantiation has none to spare.  The order of summation is as fixed as for acc[]: a pair's
+			// two moduli are added to each other first, then to the lane's sum over its pixels.
+			float absx = 0.f, absy = 0.f;
+			if constexpr (ABS) CBh = -0.5f * CB;
 			// per-lane partial sums over its pixels (one float2 = two pixels, added at the end).  The
 			// geometric terms are kept as raw moments of f = G * dL/dG (sum f dx, f dy, f dx^2, f dx dy,
 			// f dy^2); the conic and the 0.5*W / 0.5*H / -0.5 factors of backward.cu:574-594 are applied
@@ -326,6 +343,11 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				acc[2] = __builtin_elementwise_fma(fdx, dx, acc[2]);
 				acc[3] = __builtin_elementwise_fma(fdx, dy, acc[3]);
 				acc[4] = __builtin_elementwise_fma(fdy, dy, acc[4]);
+				if constexpr (ABS) {   // a pixel without a hit has f = 0: it adds exact zeros here as above
+					const v2f tx = __builtin_elementwise_fma(CA, fdx, CBh * fdy), ty = __builtin_elementwise_fma(CC, fdy, CBh * fdx);
+					absx += __builtin_fabsf(tx.x) + __builtin_fabsf(tx.y);
+					absy += __builtin_fabsf(ty.x) + __builtin_fabsf(ty.y);
+				}
 			}
 			if (any) {  // wave-uniform
 				GSR_TILE_STAT(st_reductions++;)
@@ -341,11 +363,16 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				float col[8];
 #pragma unroll
 				for (int k = 0; k < 8; k++) col[k] = red_r[red_step * k];
-				if constexpr (AUX) {
+				if constexpr (AUX || ABS) {
 					// the ninth value's DPP chain runs while the LDS round trip is under way
 					__builtin_amdgcn_sched_barrier(0);
 					const float t9 = gsr_wave_sum_to_lane63(v[8]);  // lane 63 holds the total of v[8]
-					const float t10 = gsr_wave_sum_to_lane63(gsr_add_halves(acc[9]));   // ... and of dL/dv
+					float t10 = 0.f, tax = 0.f, tay = 0.f;
+					if constexpr (AUX) t10 = gsr_wave_sum_to_lane63(gsr_add_halves(acc[9]));   // ... and of dL/dv
+					if constexpr (ABS) {   // ... and of the two sums of moduli
+						tax = gsr_wave_sum_to_lane63(absx);
+						tay = gsr_wave_sum_to_lane63(absy);
+					}
 					__builtin_amdgcn_sched_barrier(0);
 					const float tcol = ((col[0] + col[1]) + (col[2] + col[3])) + ((col[4] + col[5]) + (col[6] + col[7]));
 					const float t8 = gsr_sum8(tcol);                // group c holds the total of v[c]
@@ -358,8 +385,12 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 					const float r = out_index < 2 ? r01 : out_scale * t8;   // dL/dconic .x .y .w (x -0.5); opacity and colour as they are
 					if ((lane & 7) == 0) out[out_index] = r;
 					if (lane == 63) {
-						out[8] = t9;
-						out[9] = t10;
+						if constexpr (ABS) {   // words 8..11 as one 16-byte store (pad0 is 0 without AUX)
+							reinterpret_cast<float4*>(out)[2] = make_float4(t9, t10, (2.0f * ddelx_dx) * tax, (2.0f * ddely_dy) * tay);
+						} else {
+							out[8] = t9;
+							out[9] = t10;
+						}
 						slot_valid[slot] = 1;
 					}
 				} else {
@@ -372,7 +403,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 					npend++;
 				}
 			}
-			if (!AUX && (npend == GSR_BWD_FLUSH || (npend != 0 && j == cnt - 1))) {  // wave-uniform; rec is restaged only after the batch
+			if (!(AUX || ABS) && (npend == GSR_BWD_FLUSH || (npend != 0 && j == cnt - 1))) {  // wave-uniform; rec is restaged only after the batch
 				// gsr_flush: finish up to four reduced instances in one instruction stream over the 64 lanes.  A wave's LDS
 				// operations execute in program order, so the reads below see every s_pend store above, and the next instance's
 				// stores come after them; the wave barriers only keep the compiler from moving LDS accesses across.
@@ -416,14 +447,16 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 
 void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
                                 const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const GsrAuxBlend* aux)
+                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const GsrAuxBlend* aux, bool absgrad)
 {
 	const int gx = gsr_grid_x(W), gy = gsr_grid_y(H);
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (int)gsr_tile_order_max_segments(ntiles);   // whole tiles + the extra entries of heavy tiles' depth segments
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
-	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, false, [&](auto, auto AUX, auto) {   // (one kernel for both modes: it reads v from the record)
-		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, W, H, gx, nslots,
+	// (one kernel for both modes of the maps: it reads v from the record; the blend has no anti-aliased form, so the third slot of
+	// gsr_variant carries ABS here)
+	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, absgrad, [&](auto, auto AUX, auto ABS) {
+		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0, ABS()>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, W, H, gx, nslots,
 		           img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
 		           img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
 	});

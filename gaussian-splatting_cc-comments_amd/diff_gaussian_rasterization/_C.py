@@ -69,6 +69,11 @@ class CamArgs(ctypes.Structure):
     _fields_ = [("dL_dviewmatrix", _vp), ("dL_dprojmatrix", _vp), ("dL_dcampos", _vp), ("scratch", _vp)]
 
 
+class AbsgradArgs(ctypes.Structure):
+    """include/gsr_absgrad.h gsr_absgrad_args"""
+    _fields_ = [("abs_dL_dmean2D", _vp), ("stat_abs_gradient_accum", _vp)]
+
+
 class AuxLayout(ctypes.Structure):
     _fields_ = [(n, _sz) for n in ("ckpt_depth", "final_D", "total")]
 
@@ -171,6 +176,11 @@ def lib():
     L.gsr_cam_bytes.argtypes = [_i]
     L.gsr_backward_gaussians_cam.restype = _i
     L.gsr_backward_gaussians_cam.argtypes = [pb, _i, _vp, pa, ctypes.POINTER(CamArgs), _i, _i, _i]
+    # include/gsr_absgrad.h: absolute screen-space gradients
+    L.gsr_backward_blend_abs.restype = _i
+    L.gsr_backward_blend_abs.argtypes = [pb, pa, _i]
+    L.gsr_absgrad_fold.restype = _i
+    L.gsr_absgrad_fold.argtypes = [pb, ctypes.POINTER(AbsgradArgs), _i, _i]
     # include/gsr_contrib.h: per-Gaussian blend-weight statistics
     L.gsr_contrib_scratch_bytes.restype = _sz
     L.gsr_contrib_scratch_bytes.argtypes = [_i, _i64]
@@ -231,6 +241,36 @@ def camera_flag(camera_grads):
     return camera_grads
 
 
+def absgrad_tensors(absgrad, P, device=None):
+    """Checks the `absgrad` keyword: (abs_mean2D float32 [P, 2] or None, abs_gradient_accum float32 [P] or None), contiguous tensors
+    on `device` (None: any HIP device, the same for both) -> AbsgradArgs.  Anything but a 2-tuple raises TypeError; a wrong dtype,
+    shape or device, a non-contiguous tensor and two Nones raise ValueError.  No kernel and no library is touched."""
+    if not isinstance(absgrad, (tuple, list)) or len(absgrad) != 2:
+        raise TypeError(f"absgrad must be a 2-tuple (abs_mean2D, abs_gradient_accum), got {absgrad!r}")
+    if any(t is not None and not isinstance(t, torch.Tensor) for t in absgrad):
+        raise TypeError("absgrad must hold tensors or None")
+    if all(t is None for t in absgrad):
+        raise ValueError("absgrad must hold at least one tensor: (abs_mean2D, abs_gradient_accum) are both None")
+    c = AbsgradArgs()
+    for field, name, t, shape in zip(("abs_dL_dmean2D", "stat_abs_gradient_accum"), ("abs_mean2D", "abs_gradient_accum"), absgrad,
+                                     ((int(P), 2), (int(P),))):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32 (got {t.dtype})")
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} (got shape {tuple(t.shape)}, "
+                             f"{'' if t.is_contiguous() else 'not '}contiguous)")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a HIP (cuda) tensor (got {t.device}); the HIP rasterizer has no CPU path")
+        device = t.device if device is None else device
+        if t.device != device:
+            raise ValueError(f"{name} must be on {device} (got {t.device})")
+        setattr(c, field, _ptr(t))
+    c._keep = tuple(absgrad)
+    return c
+
+
 def camera_backward_args(P, device):
     """CamArgs of a backward with camera gradients (include/gsr_cam.h) -> (struct, (dL_dviewmatrix (4,4), dL_dprojmatrix (4,4),
     dL_dcampos (3,))): the three outputs, which the fold kernel writes in full, and the scratch of P Gaussians, all from torch's
@@ -246,13 +286,14 @@ def camera_backward_args(P, device):
 
 
 # ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
-def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None):
+def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, absgrad=False):
     """-> (function of L, the arguments that precede the default entry point's own).  stage: "preprocess" | "render" (the two forward
     calls) | "blend" | "gaussians" (the two backward stages: their leading arguments follow the gsr_backward_args pointer); leaf: the
     inputs are the optimiser's leaves (fused_params.py); x: the AuxArgs of a call with depth and alpha maps, or None; aa: the
     screen-space filter, whose per-Gaussian backward reads the forward's opacity input at address `opacities`.  The *_aa entry
     points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice.
-    cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None."""
+    cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None.
+    absgrad: the blend that also leaves the sums of per-pixel moduli in the slots (include/gsr_absgrad.h)."""
     xr = None if x is None else ctypes.byref(x)
     if stage == "preprocess":
         name = "gsr_forward_preprocess_leaf" if leaf else "gsr_forward_preprocess"
@@ -262,6 +303,8 @@ def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None):
     elif stage == "gaussians":
         name, lead = ("gsr_backward_gaussians_aa", (1, opacities, xr)) if aa else \
             ("gsr_backward_gaussians_aux", (xr,)) if x is not None else ("gsr_backward_gaussians", ())
+    elif stage == "blend" and absgrad:
+        name, lead = "gsr_backward_blend_abs", (xr, 1)
     else:
         name = {"render": "gsr_forward_render", "blend": "gsr_backward_blend"}[stage]
         name, lead = (name + "_aux", (xr,)) if x is not None else (name, ())
@@ -379,19 +422,25 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
     return x
 
 
-def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None):
+def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
     logits in leaf mode) when the screen-space filter was on, else None; before_part(k) / after_part(k): called around part k's pass
     (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_backward_args()) when
-    the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`."""
+    the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`.
+    absgrad: AbsgradArgs (absgrad_tensors()) when the blend shall keep the per-pixel moduli of dL/dmean2D and a fold pass behind it
+    shall overwrite abs_mean2D and add into abs_gradient_accum (include/gsr_absgrad.h); not with `parts` either."""
     if cam is not None and parts is not None:
         raise NotImplementedError("camera gradients need the whole scene in one per-Gaussian pass: not with `parts`")
+    if absgrad is not None and parts is not None:
+        raise NotImplementedError("absolute gradients have no part-by-part form")
     L = lib()
     ra = ctypes.byref(a)
-    blend, lead = _entry(L, "blend", x=x)
+    blend, lead = _entry(L, "blend", x=x, absgrad=absgrad is not None)
     _check(blend(ra, *lead))
+    if absgrad is not None:   # right behind the blend, while the slots are still in cache
+        _check(L.gsr_absgrad_fold(ra, ctypes.byref(absgrad), 0, a.P))
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
@@ -405,7 +454,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     release_scratch(scratch, device)
 
 
-def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False):
+def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -444,7 +493,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
             scratch = backward_scratch(P, R, dev)
             if camera_flag(camera_grads):
                 cam, cam_grads = camera_backward_args(P, dev)
-            if stats is None and not aa and aux is None and cam is None:   # nothing but the reference's backward: one call for both stages
+            ab = None if absgrad is None else absgrad_tensors(absgrad, P, dev)
+            if stats is None and not aa and aux is None and cam is None and ab is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
                                       _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                       _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -464,7 +514,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dcolor=dL_dcolors, dL_dmean3D=dL_dmeans3D, dL_dcov3D=dL_dcov3D, dL_dsh=dL_dsh,
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
-                run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam)
+                run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
+                             absgrad=ab)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
@@ -475,7 +526,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
-                                 debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False):
+                                 debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False, absgrad=None):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -489,25 +540,28 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 visible in this view (train.py:157-159, gaussian_model.py:599-602); any of them may be None
       antialiasing  the backward of an antialiasing=True forward; `opacities` is then its opacity input (include/gsr_aa.h)
       camera_grads  True: three more results behind the eight, dL_dviewmatrix (4,4), dL_dprojmatrix (4,4) and dL_dcampos (3,) of the
-                    camera tensors as the kernels read them (include/gsr_cam.h)"""
+                    camera tensors as the kernels read them (include/gsr_cam.h)
+      absgrad   (abs_mean2D [P, 2], abs_gradient_accum [P]) float32 tensors, either None: the first is overwritten with the sums over
+                the pixels of |dL_p/dmean2D| per component, the second gets their norm added for the visible Gaussians
+                (include/gsr_absgrad.h)"""
     return _backward_plain("rasterize_gaussians_backward", None,
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads)
+                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads, absgrad)
 
 
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
-                                             camera_grads=False):
+                                             camera_grads=False, absgrad=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
-    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads: as there."""
+    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad: as there."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads)
+                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------

@@ -22,12 +22,12 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
-                        camera_grads=False):
+                        camera_grads=False, absgrad=None):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
-    statistics and the camera gradients, see GaussianRasterizer)"""
+    statistics, the camera gradients and the absolute gradients, see GaussianRasterizer)"""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                                     contrib_stats, contrib_pixel_weight, *camera_inputs(raster_settings, camera_grads))
+                                     contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
 
 
 def camera_inputs(raster_settings, camera_grads):
@@ -45,12 +45,12 @@ def camera_grad_results(needs, grads, inputs):
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
-                                    contrib_pixel_weight=None, camera_grads=False):
+                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
     _C.aux_mode(depth_alpha)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                                     contrib_stats, contrib_pixel_weight, *camera_inputs(raster_settings, camera_grads))
+                                     contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -61,14 +61,19 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     Camera gradients (include/gsr_cam.h): with the settings' viewmatrix, projmatrix and campos as three more inputs behind the others,
     the backward returns their gradients too -- the camera-gradient kernels run when at least one of the three requires a gradient,
-    the default ones otherwise.  The kernels read the tensors of the settings; the inputs only tie them into the graph."""
+    the default ones otherwise.  The kernels read the tensors of the settings; the inputs only tie them into the graph.
+
+    Absolute gradients (include/gsr_absgrad.h): absgrad = (abs_mean2D, abs_gradient_accum) is checked before anything runs and only
+    the backward writes the tensors; a non-tensor input, so the saved tensors stay as they are and the gradient tuple grows by a None."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None, *camera):
+                contrib_pixel_weight=None, absgrad=None, *camera):
         if contrib_stats is not None:   # refused before anything runs
             _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
+        if absgrad is not None:         # the same, the render's device included (a CPU means3D is refused by the forward itself)
+            _C.absgrad_tensors(absgrad, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
         args = (
             raster_settings.bg,
@@ -121,6 +126,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
         ctx.camera = len(camera) == 3
+        ctx.absgrad = absgrad
         # after the reference's ten: the aux state of the maps, and the opacity input that the anti-aliased backward reads (the records
         # hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
@@ -140,9 +146,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
                                          dtype=torch.float32, device=means3D.device)
         kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
-        cam_needs = tuple(ctx.needs_input_grad[14:17]) if ctx.camera else ()
+        cam_needs = tuple(ctx.needs_input_grad[15:18]) if ctx.camera else ()
         if any(cam_needs):
             kw["camera_grads"] = True
+        if ctx.absgrad is not None:
+            kw["absgrad"] = ctx.absgrad
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
@@ -207,6 +215,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
             None,
+            None,
             *cam_grads,
         )
 
@@ -254,10 +263,18 @@ class GaussianRasterizer(nn.Module):
     torch gets the total derivative.  The gradients are those of the function the backward differentiates for the Gaussians (clamped
     t.x / t.y constant inside the EWA Jacobian; culling, radii, tile membership and depth order carry none; tanfovx / tanfovy are
     constants).  When none of the three requires a gradient the default kernels run and nothing is allocated.  A bool; anything else
-    raises TypeError."""
+    raises TypeError.
+
+    absgrad (extension, optional): (abs_mean2D, abs_gradient_accum) -- contiguous float32 tensors [P, 2] and [P] on the render's
+    device, either of them None -- the absolute screen-space gradients of AbsGS / gsplat's `absgrad` (include/gsr_absgrad.h).  The
+    backward overwrites abs_mean2D[g] with (0.5 W sum_p |dL_p/dmean2D.x|, 0.5 H sum_p |dL_p/dmean2D.y|), the moduli taken per pixel
+    before any sum -- the units of means2D.grad, exact zeros for Gaussians that blended nowhere -- and adds their norm into
+    abs_gradient_accum for the visible Gaussians (radii > 0), the counterpart of densify_stats' xyz_gradient_accum, which stays signed.
+    Under no_grad, or when no backward runs, nothing is touched.  Anything but a 2-tuple raises TypeError; wrong tensors ValueError,
+    before anything runs.  With None, the default, the default kernels run and every output has the same bits as without the keyword."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
-                 contrib_pixel_weight=None, camera_grads=False):
+                 contrib_pixel_weight=None, camera_grads=False, absgrad=None):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
@@ -268,6 +285,7 @@ class GaussianRasterizer(nn.Module):
         self.depth_alpha = depth_alpha
         self.contrib_stats = contrib_stats
         self.contrib_pixel_weight = contrib_pixel_weight
+        self.absgrad = absgrad
 
     def markVisible(self, positions):
         # Mark visible points (based on frustum culling for camera) with a boolean
@@ -301,7 +319,8 @@ class GaussianRasterizer(nn.Module):
         if self.depth_alpha is not None:
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
-                                                   self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads)
+                                                   self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
+                                                   self.absgrad)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
-                                   self.contrib_pixel_weight, self.camera_grads)
+                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad)

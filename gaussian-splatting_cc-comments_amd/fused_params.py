@@ -82,9 +82,11 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, *camera):
+                depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, absgrad=None, *camera):
         if contrib_stats is not None:   # refused before anything runs
             _C.contrib_stat_tensors(contrib_stats, int(xyz.size(0)))
+        if absgrad is not None:         # the same; only the backward writes the tensors (GaussianRasterizer, absgrad)
+            _C.absgrad_tensors(absgrad, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps = _leaf_forward(
             None if depth_alpha is None else _C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation,
             raster_settings, antialiasing)
@@ -93,6 +95,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                                       contrib_stats, contrib_pixel_weight, raster_settings.debug)
         ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
         ctx.antialiasing = antialiasing
+        ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
         # after the state: the aux state of the maps, and the opacity logits that the anti-aliased backward reads (the records hold
         # sigmoid(logit) * rho), each saved on its path only
@@ -111,7 +114,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
         P = int(xyz.size(0))
         f32 = dict(dtype=torch.float32, device=dev)
-        cam_needs = tuple(ctx.needs_input_grad[13:16]) if ctx.camera else ()
+        cam_needs = tuple(ctx.needs_input_grad[14:17]) if ctx.camera else ()
         cam, cam_grads = None, (None, None, None) if ctx.camera else ()
         with torch.cuda.device(dev):
             alloc = torch.zeros if P == 0 else torch.empty
@@ -132,16 +135,18 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                     x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
                 if any(cam_needs):
                     cam, outs = _C.camera_backward_args(P, dev)
-                _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam)
+                _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
+                                absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev))
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
                 cam_grads = camera_grad_results(cam_needs, outs, (st.viewmatrix, st.projmatrix, st.campos))
-        return (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, *cam_grads)
+        return (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, None, *cam_grads)
 
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                             depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False):
+                             depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
+                             absgrad=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -149,11 +154,12 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     GaussianRasterizer(raster_settings, depth_alpha=...).  antialiasing: the screen-space filter of
     GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always.
     contrib_stats / contrib_pixel_weight: the blend-weight statistics of GaussianRasterizer, updated by the forward.
-    camera_grads: the settings' viewmatrix, projmatrix and campos take part in autograd, as in GaussianRasterizer."""
+    camera_grads: the settings' viewmatrix, projmatrix and campos take part in autograd, as in GaussianRasterizer.
+    absgrad: (abs_mean2D, abs_gradient_accum), the absolute screen-space gradients of GaussianRasterizer, written by the backward."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
     return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats,
-                                         depth_alpha, _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight,
+                                         depth_alpha, _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad,
                                          *camera_inputs(raster_settings, camera_grads))
 
 

@@ -54,7 +54,8 @@ def _result(image, screenspace_points, radii, aux=None):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
-           depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None):
+           depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
+           absgrad=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -63,7 +64,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     contrib_stats / contrib_pixel_weight (extension): see GaussianRasterizer -- the per-Gaussian blend-weight statistics of this view
     (weight sum, weight max, hit count), updated by the forward on both paths.
     camera_grads: the camera's world_view_transform, full_proj_transform and camera_center take part in autograd (see
-    GaussianRasterizer): pose refinement; None = getattr(pipe, "camera_grads", False)."""
+    GaussianRasterizer): pose refinement; None = getattr(pipe, "camera_grads", False).
+    absgrad (extension): (abs_mean2D, abs_gradient_accum), see GaussianRasterizer -- the absolute screen-space gradients, written by the
+    backward on both paths; None = off."""
     if camera_grads is None:
         camera_grads = getattr(pipe, "camera_grads", False)
     if antialiasing is None:
@@ -80,6 +83,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     extras = {} if contrib_stats is None else dict(contrib_stats=contrib_stats, contrib_pixel_weight=contrib_pixel_weight)
     if camera_grads is not False:   # the camera gradients travel the same way (a non-bool reaches the check that refuses it)
         extras["camera_grads"] = camera_grads
+    if absgrad is not None:
+        extras["absgrad"] = absgrad
 
     python_cov = bool(pipe.compute_cov3D_python)
     python_sh = bool(pipe.convert_SHs_python)

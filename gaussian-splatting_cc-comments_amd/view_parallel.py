@@ -239,7 +239,7 @@ class _RasterizeViewParallel(torch.autograd.Function):
 
 
 def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
-                            antialiasing=False, camera_grads=False):
+                            antialiasing=False, camera_grads=False, absgrad=None):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
@@ -248,6 +248,9 @@ def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations,
     if _C.camera_flag(camera_grads):
         raise NotImplementedError("rasterize_view_parallel: camera gradients need the whole scene in one per-Gaussian pass; the "
                                   "part-by-part pipeline of view-parallel mode has no camera form (include/gsr_cam.h)")
+    if absgrad is not None:
+        raise NotImplementedError("rasterize_view_parallel: absolute gradients (absgrad) have no view-parallel form: the statistic "
+                                  "is not folded over ranks (include/gsr_absgrad.h)")
     return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
                                         _C.aa_flag(antialiasing))
 
