@@ -13,6 +13,7 @@
 #include "gsr_internal.h"
 #include "../../include/gsr_aa.h"
 #include "../../include/gsr_contrib.h"
+#include "../../include/gsr_features.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1163,6 +1164,89 @@ extern "C" int gsr_contributions(int P, int64_t R, int width, int height, const 
 		gsr_launch_contrib_gaussians(P, g, scratch, R, weight_sum, weight_max, pixel_count, s);
 	}
 	return gsr_stage_done(s, debug, "contrib_gaussians");
+}
+
+// ---- blended feature channels (include/gsr_features.h) ---------------------------------------------
+#define GSR_FEATURES_MAX_K (4 * 65535)   // one grid row of the tile passes per chunk of four channels
+
+extern "C" size_t gsr_features_scratch_bytes(int P, int64_t R, int K)
+{
+	(void)P;
+	if (R <= 0 || K < 1 || K > GSR_FEATURES_MAX_K) return 0;
+	return gsr_features_valid_offset(R, K) + gsr_align_up((size_t)R);   // the records of every chunk, then one validity byte per slot
+}
+
+extern "C" int gsr_features_forward(int P, int64_t R, int width, int height, int K, const void* geometry, const void* binning, const void* image,
+                                    const float* features, float* out, void* stream, int debug)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_features_forward";
+	hipStream_t s = (hipStream_t)stream;
+	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (K < 1 || K > GSR_FEATURES_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must be in [1, %d], got %d", who, GSR_FEATURES_MAX_K, K);
+	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
+	if (!features || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: features or out is NULL", who);
+	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	int rc;
+	{
+		GsrProfScope p(s, "features_forward");
+		if (R == 0) {   // nothing blended: the map is zeros
+			if ((rc = gsr_check_hip(hipMemsetAsync(out, 0, (size_t)K * height * width * sizeof(float), s), "hipMemsetAsync(feature map)"))) return rc;
+		} else {
+			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
+			GsrImage im = gsr_image_view((void*)image, width, height);
+			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
+			gsr_launch_features_forward(width, height, K, im, b.point_list, g.splat, features, out, !(debug & GSR_DEBUG_NO_CULL), s);
+		}
+	}
+	return gsr_stage_done(s, debug, "features_forward");
+}
+
+extern "C" int gsr_features_backward(const gsr_backward_args* args, int K, const float* features, const float* dL_dout, float* dL_dfeatures,
+                                     void* scratch, int into_slots)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_features_backward";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	const gsr_backward_args& a = *args;
+	const int64_t R = a.num_rendered;
+	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (K < 1 || K > GSR_FEATURES_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must be in [1, %d], got %d", who, GSR_FEATURES_MAX_K, K);
+	if (into_slots != 0 && into_slots != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: into_slots must be 0 or 1, got %d", who, into_slots);
+	if (a.P == 0) return GSR_OK;
+	if (!features || !dL_dout || !dL_dfeatures) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: features, dL_dout or dL_dfeatures is NULL", who);
+	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !scratch || (into_slots && !a.scratch))))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(scratch) || (into_slots && !aligned16(a.scratch)))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	hipStream_t s = (hipStream_t)a.stream;
+	int rc;
+	if (R == 0) {   // nothing blended: every gradient is zero
+		{
+			GsrProfScope p(s, "features_backward_fold");
+			if ((rc = gsr_check_hip(hipMemsetAsync(dL_dfeatures, 0, (size_t)a.P * K * sizeof(float), s), "hipMemsetAsync(dL_dfeatures)"))) return rc;
+		}
+		return gsr_stage_done(s, a.debug, "features_backward_fold");
+	}
+	GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
+	GsrImage im = gsr_image_view(a.image, a.width, a.height);
+	GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
+	{
+		GsrProfScope p(s, "features_backward_tiles");   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
+		if ((rc = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_features_valid_offset(R, K), 0, (size_t)R, s), "hipMemsetAsync(features validity)"))) return rc;
+		gsr_launch_features_backward_tiles(a.width, a.height, K, R, im, b.point_list, g.splat, g.slot_base, features, dL_dout, scratch,
+		                                   into_slots ? (GsrGradSlot*)a.scratch : nullptr, !(a.debug & GSR_DEBUG_NO_CULL), s);
+	}
+	if ((rc = gsr_stage_done(s, a.debug, "features_backward_tiles"))) return rc;
+	{
+		GsrProfScope p(s, "features_backward_fold");
+		gsr_launch_features_fold(a.P, K, R, g, scratch, dL_dfeatures, s);
+	}
+	return gsr_stage_done(s, a.debug, "features_backward_fold");
 }
 
 extern "C" size_t gsr_loss_scratch_bytes(int C, int H, int W)

@@ -258,6 +258,18 @@ void gsr_launch_contrib_tiles(int W, int H, GsrImage img, const uint32_t* point_
 void gsr_launch_contrib_gaussians(int P, GsrGeometry g, const void* scratch, int64_t R, float* weight_sum, float* weight_max, int32_t* pixel_count,
                                   hipStream_t s);
 
+// features.hip: K blended feature channels and their gradients (include/gsr_features.h).  scratch: gsr_features_chunks(K) x R 16-byte
+// records, then (at gsr_features_valid_offset) R validity bytes, which gsr_features_backward clears on the stream before the tile pass.
+// slots: NULL (into_slots = 0), or the gradient slots whose words 0..5 the tile pass adds into
+int gsr_features_chunks(int K);
+size_t gsr_features_valid_offset(int64_t R, int K);
+void gsr_launch_features_forward(int W, int H, int K, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float* features,
+                                 float* out, bool cull, hipStream_t s);
+void gsr_launch_features_backward_tiles(int W, int H, int K, int64_t R, GsrImage img, const uint32_t* point_list, const GsrSplat* splat,
+                                        const uint32_t* slot_base, const float* features, const float* dL_dout, void* scratch,
+                                        GsrGradSlot* slots, bool cull, hipStream_t s);
+void gsr_launch_features_fold(int P, int K, int64_t R, GsrGeometry g, const void* scratch, float* dL_dfeatures, hipStream_t s);
+
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
 	int P, D, M, W, H;

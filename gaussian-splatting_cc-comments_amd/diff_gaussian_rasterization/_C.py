@@ -186,6 +186,13 @@ def lib():
     L.gsr_contrib_scratch_bytes.argtypes = [_i, _i64]
     L.gsr_contributions.restype = _i
     L.gsr_contributions.argtypes = [_i, _i64, _i, _i] + [_vp] * 8 + [_vp, _i]
+    # include/gsr_features.h: K blended feature channels and their gradients
+    L.gsr_features_scratch_bytes.restype = _sz
+    L.gsr_features_scratch_bytes.argtypes = [_i, _i64, _i]
+    L.gsr_features_forward.restype = _i
+    L.gsr_features_forward.argtypes = [_i, _i64, _i, _i, _i] + [_vp] * 5 + [_vp, _i]
+    L.gsr_features_backward.restype = _i
+    L.gsr_features_backward.argtypes = [pb, _i, _vp, _vp, _vp, _vp, _i]
     _lib = L
     return L
 
@@ -422,7 +429,8 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
     return x
 
 
-def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None):
+def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None,
+                 features=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
@@ -430,7 +438,11 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_backward_args()) when
     the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`.
     absgrad: AbsgradArgs (absgrad_tensors()) when the blend shall keep the per-pixel moduli of dL/dmean2D and a fold pass behind it
-    shall overwrite abs_mean2D and add into abs_gradient_accum (include/gsr_absgrad.h); not with `parts` either."""
+    shall overwrite abs_mean2D and add into abs_gradient_accum (include/gsr_absgrad.h); not with `parts` either.
+    features: FeatureBackward (include/gsr_features.h) when a feature map took part in the loss: its pass runs between the blend (and
+    the absgrad fold) and the per-Gaussian parts, adds the map's share of dL/dmean2D, dL/dconic and dL/dopacity into the slots and
+    leaves dL/dfeatures in features.grad.  The slots are complete before the first part runs, so x, opacities, cam, absgrad and parts
+    work unchanged."""
     if cam is not None and parts is not None:
         raise NotImplementedError("camera gradients need the whole scene in one per-Gaussian pass: not with `parts`")
     if absgrad is not None and parts is not None:
@@ -441,6 +453,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     _check(blend(ra, *lead))
     if absgrad is not None:   # right behind the blend, while the slots are still in cache
         _check(L.gsr_absgrad_fold(ra, ctypes.byref(absgrad), 0, a.P))
+    if features is not None:
+        features.run(a, device, into_slots=True)
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
@@ -454,7 +468,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     release_scratch(scratch, device)
 
 
-def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None):
+def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None,
+                    features=None):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -494,7 +509,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
             if camera_flag(camera_grads):
                 cam, cam_grads = camera_backward_args(P, dev)
             ab = None if absgrad is None else absgrad_tensors(absgrad, P, dev)
-            if stats is None and not aa and aux is None and cam is None and ab is None:   # nothing but the reference's backward: one call for both stages
+            if stats is None and not aa and aux is None and cam is None and ab is None and features is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
                                       _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                       _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -515,7 +530,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
                 run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
-                             absgrad=ab)
+                             absgrad=ab, features=features)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
@@ -526,7 +541,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
-                                 debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False, absgrad=None):
+                                 debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False, absgrad=None,
+                                 features=None):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -543,25 +559,29 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                     camera tensors as the kernels read them (include/gsr_cam.h)
       absgrad   (abs_mean2D [P, 2], abs_gradient_accum [P]) float32 tensors, either None: the first is overwritten with the sums over
                 the pixels of |dL_p/dmean2D| per component, the second gets their norm added for the visible Gaussians
-                (include/gsr_absgrad.h)"""
+                (include/gsr_absgrad.h)
+      features  FeatureBackward(features, dL_dfeature_map): the feature map of features_forward() took part in the loss; its share
+                of the geometry gradients is in the eight results, dL/dfeatures is left in features.grad (include/gsr_features.h)"""
     return _backward_plain("rasterize_gaussians_backward", None,
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads, absgrad)
+                            imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads, absgrad,
+                           features)
 
 
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
-                                             camera_grads=False, absgrad=None):
+                                             camera_grads=False, absgrad=None, features=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
-    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad: as there."""
+    precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad /
+    features: as there."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad)
+                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------
@@ -616,6 +636,87 @@ def gaussian_contributions(geomBuffer, binningBuffer, imgBuffer, num_rendered, P
             scratch = torch.empty((L.gsr_contrib_scratch_bytes(P, R),), dtype=torch.uint8, device=dev)
         _check(L.gsr_contributions(P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(m), *(_ptr(t) for t in stats),
                                    _ptr(scratch), _stream(dev), _dbg(debug)))
+
+
+# ---- K blended feature channels (include/gsr_features.h) ---------------------------------------------------------------------------
+def feature_tensor(features, P, device=None):
+    """Checks the `features` keyword: a float32 (P, K) HIP tensor, K >= 1 -> K.  No kernel and no library is touched: anything but a
+    tensor raises TypeError; a CPU tensor, a wrong dtype, a wrong shape or a wrong device RuntimeError; a (P, M, K) tensor of SH
+    coefficients NotImplementedError (view-dependent features are evaluated by the caller)."""
+    if not isinstance(features, torch.Tensor):
+        raise TypeError(f"features must be a float32 (P, K) tensor or None, got {type(features).__name__}")
+    if features.dim() == 3:
+        raise NotImplementedError("SH-evaluated features are not supported: evaluate them per view and pass the (P, K) result")
+    if features.dtype != torch.float32:
+        raise RuntimeError(f"features must be float32 (got {features.dtype})")
+    if features.dim() != 2 or int(features.size(0)) != int(P) or int(features.size(1)) < 1:
+        raise RuntimeError(f"features must have shape (P, K) with P = {int(P)} and K >= 1 (got {tuple(features.shape)})")
+    if not features.is_cuda:
+        raise RuntimeError(f"features must be a HIP (cuda) tensor (got {features.device}); the HIP rasterizer has no CPU path")
+    if device is not None and features.device != device:
+        raise RuntimeError(f"features must be on {device} (got {features.device})")
+    return int(features.size(1))
+
+
+def features_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, P, W, H, features, debug=0):
+    """feature_map (K, H, W) = sum_i features[i] alpha_i T_i of the view whose forward (of any variant) left the three state buffers:
+    the colour pass's own weights bit for bit, no background term, zeros where nothing blends.  Nothing of the state is written."""
+    P, R, W, H = int(P), int(num_rendered), int(W), int(H)
+    K = feature_tensor(features, P)
+    dev = features.device
+    features = features.contiguous()
+    with torch.cuda.device(dev):
+        out = (torch.zeros if P == 0 else torch.empty)((K, H, W), dtype=torch.float32, device=dev)
+        if P > 0:
+            _check(lib().gsr_features_forward(P, R, W, H, K, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(features),
+                                              _ptr(out), _stream(dev), _dbg(debug)))
+    return out
+
+
+class FeatureBackward:
+    """The feature map's part of one backward: features (P, K) and dL_dfeature_map (K, H, W).  run() leaves dL/dfeatures (P, K) in
+    .grad -- every element written, zeros for Gaussians without a hit."""
+
+    def __init__(self, features, dL_dmap):
+        self.K = feature_tensor(features, features.size(0))
+        dev = features.device
+        self.features = features.contiguous()
+        self.dL_dmap = _dev_f32(dL_dmap, dev, "dL_dfeature_map")
+        if self.dL_dmap.dim() != 3 or int(self.dL_dmap.size(0)) != self.K:
+            raise RuntimeError(f"dL_dfeature_map must have shape ({self.K}, H, W), got {tuple(self.dL_dmap.shape)}")
+        self.grad = None
+
+    def run(self, a, device, into_slots):
+        """a: the BackwardArgs of the colour backward (into_slots: its blend has run, its per-Gaussian pass has not), or one that
+        holds the sizes, the three state buffers, stream and debug alone (not into_slots: a.scratch is not touched)."""
+        L = lib()
+        P, R = int(a.P), int(a.num_rendered)
+        if tuple(self.dL_dmap.shape[1:]) != (int(a.height), int(a.width)):
+            raise RuntimeError(f"dL_dfeature_map must have shape ({self.K}, {a.height}, {a.width}), got {tuple(self.dL_dmap.shape)}")
+        self.grad = (torch.zeros if P == 0 else torch.empty)((P, self.K), dtype=torch.float32, device=device)
+        if P == 0:
+            return self.grad
+        scratch = None
+        if R > 0:
+            scratch = torch.empty((L.gsr_features_scratch_bytes(P, R, self.K),), dtype=torch.uint8, device=device)
+        _check(L.gsr_features_backward(ctypes.byref(a), self.K, _ptr(self.features), _ptr(self.dL_dmap), _ptr(self.grad), _ptr(scratch),
+                                       1 if into_slots else 0))
+        if scratch is not None:
+            release_scratch(scratch, device)
+        return self.grad
+
+
+def features_backward_only(geomBuffer, binningBuffer, imgBuffer, num_rendered, P, W, H, features, dL_dmap, debug=0):
+    """dL/dfeatures (P, K) alone, for features on a frozen scene: no colour backward, no gradient slots, no geometry gradient."""
+    fb = FeatureBackward(features, dL_dmap)
+    dev = features.device
+    a = BackwardArgs()
+    a.P, a.num_rendered, a.width, a.height = int(P), int(num_rendered), int(W), int(H)
+    a.geometry, a.binning, a.image = _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer)
+    a.debug = _dbg(debug)
+    with torch.cuda.device(dev):
+        a.stream = _stream(dev)
+        return fb.run(a, dev, into_slots=False)
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------

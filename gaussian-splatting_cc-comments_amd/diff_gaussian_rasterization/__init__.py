@@ -22,12 +22,20 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
-                        camera_grads=False, absgrad=None):
+                        camera_grads=False, absgrad=None, features=None):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
-    statistics, the camera gradients and the absolute gradients, see GaussianRasterizer)"""
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                                     contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+    statistics, the camera gradients, the absolute gradients and the feature channels, see GaussianRasterizer)"""
+    return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                  cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+
+
+def _apply(features, *inputs):
+    """features=None: the Function of every release so far, on its own inputs; a tensor: the Function that takes it in front of them
+    and returns the feature map behind the other outputs."""
+    if features is None:
+        return _RasterizeGaussians.apply(*inputs)
+    return _RasterizeGaussiansFeatures.apply(features, *inputs)
 
 
 def camera_inputs(raster_settings, camera_grads):
@@ -45,12 +53,12 @@ def camera_grad_results(needs, grads, inputs):
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
-                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None):
-    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W))"""
+                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None):
+    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, feature_map])"""
     _C.aux_mode(depth_alpha)
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                                     contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+    return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                  cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -64,13 +72,18 @@ class _RasterizeGaussians(torch.autograd.Function):
     the default ones otherwise.  The kernels read the tensors of the settings; the inputs only tie them into the graph.
 
     Absolute gradients (include/gsr_absgrad.h): absgrad = (abs_mean2D, abs_gradient_accum) is checked before anything runs and only
-    the backward writes the tensors; a non-tensor input, so the saved tensors stay as they are and the gradient tuple grows by a None."""
+    the backward writes the tensors; a non-tensor input, so the saved tensors stay as they are and the gradient tuple grows by a None.
+
+    Feature channels (include/gsr_features.h): _RasterizeGaussiansFeatures below takes `features` (P, K) in front of these inputs
+    and runs this forward and backward with it; through apply() of this class nothing of them is reached."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None, absgrad=None, *camera):
-        if contrib_stats is not None:   # refused before anything runs
+                contrib_pixel_weight=None, absgrad=None, *camera, _features=None):
+        if _features is not None:       # refused before anything runs
+            _C.feature_tensor(_features, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
+        if contrib_stats is not None:   # the same
             _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
         if absgrad is not None:         # the same, the render's device included (a CPU means3D is refused by the forward itself)
             _C.absgrad_tensors(absgrad, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
@@ -120,8 +133,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                                       raster_settings.image_width, raster_settings.image_height, contrib_stats, contrib_pixel_weight,
                                       raster_settings.debug)
 
+        fmap = ()
+        if _features is not None:
+            # the feature map, from the state the render just left and the weights it blended the colours with
+            fmap = (_C.features_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
+                                        raster_settings.image_width, raster_settings.image_height, _features, raster_settings.debug),)
+
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
+        ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
         ctx.num_rendered = num_rendered
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
@@ -130,25 +150,45 @@ class _RasterizeGaussians(torch.autograd.Function):
         # after the reference's ten: the aux state of the maps, and the opacity input that the anti-aliased backward reads (the records
         # hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *maps[2:], *((opacities,) if antialiasing else ()))
+                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:],
+                              *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
         ctx.set_materialize_grads(False)
-        return (color, radii, *maps[:2])
+        return (color, radii, *maps[:2], *fmap)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
+        return _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, None)[1]
+
+    @staticmethod
+    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map):
+        """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         num_rendered = ctx.num_rendered
         raster_settings = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, *extra) = ctx.saved_tensors
+        off = 1 if ctx.features else 0
+        n_in = 15 + (3 if ctx.camera else 0)
+        fb = None
+        if ctx.features:
+            features, extra = extra[0], extra[1:]
+            if grad_features_map is not None and ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:]):
+                # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
+                return (_C.features_backward_only(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
+                                                  raster_settings.image_width, raster_settings.image_height, features,
+                                                  grad_features_map, raster_settings.debug), (None,) * n_in)
+            if grad_features_map is not None:   # (no gradient reached the map: the feature pass is skipped)
+                fb = _C.FeatureBackward(features, grad_features_map)
         if grad_out_color is None:  # the image took no part in the loss: the zero gradient autograd would have materialised
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
                                          dtype=torch.float32, device=means3D.device)
         kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
-        cam_needs = tuple(ctx.needs_input_grad[15:18]) if ctx.camera else ()
+        cam_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera else ()
         if any(cam_needs):
             kw["camera_grads"] = True
+        if fb is not None:
+            kw["features"] = fb
         if ctx.absgrad is not None:
             kw["absgrad"] = ctx.absgrad
 
@@ -200,7 +240,10 @@ class _RasterizeGaussians(torch.autograd.Function):
                                                                    raster_settings.campos)) if any(cam_needs) else (None, None, None)
 
         # gradient order: reference __init__.py:154-164
-        return (
+        grad_features = None
+        if fb is not None:   # (no Gaussian: nothing ran)
+            grad_features = fb.grad if fb.grad is not None else torch.zeros_like(fb.features)
+        return grad_features, (
             grad_means3D,
             grad_means2D,
             grad_sh if (sh.numel() != 0 and grad_sh is not None) else None,
@@ -218,6 +261,23 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             *cam_grads,
         )
+
+
+class _RasterizeGaussiansFeatures(torch.autograd.Function):
+    """_RasterizeGaussians with `features` (P, K) in front of its inputs -> (color, radii[, depth, alpha], feature_map (K, H, W)):
+    feature_map = sum_i features[i] alpha_i T_i with the colour pass's own weights, differentiable w.r.t. features and, through the
+    gradient slots of the colour backward, w.r.t. every geometry input (include/gsr_features.h).  Colour, radii and maps have the
+    bits of _RasterizeGaussians."""
+
+    @staticmethod
+    def forward(ctx, features, *inputs):
+        return _RasterizeGaussians.forward(ctx, *inputs, _features=features)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, *grads):
+        grad_depth, grad_alpha = grads[:2] if len(grads) == 3 else (None, None)
+        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grads[-1])
+        return (grad_features, *rest)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -271,7 +331,19 @@ class GaussianRasterizer(nn.Module):
     before any sum -- the units of means2D.grad, exact zeros for Gaussians that blended nowhere -- and adds their norm into
     abs_gradient_accum for the visible Gaussians (radii > 0), the counterpart of densify_stats' xyz_gradient_accum, which stays signed.
     Under no_grad, or when no backward runs, nothing is touched.  Anything but a 2-tuple raises TypeError; wrong tensors ValueError,
-    before anything runs.  With None, the default, the default kernels run and every output has the same bits as without the keyword."""
+    before anything runs.  With None, the default, the default kernels run and every output has the same bits as without the keyword.
+
+    features (extension, a keyword of forward(); default None): a float32 (P, K) HIP tensor of per-Gaussian feature channels, any
+    K >= 1 -- semantic or language features, normals, logits.  forward() then returns one more element, LAST in the tuple:
+    (color, radii[, depth, alpha], feature_map), feature_map (K, H, W) = sum_i features[i] alpha_i T_i with the weights the colour
+    pass blended with, bit for bit; no background term (add (1 - A) bg_k from the alpha map if wanted), zeros where nothing blends.
+    One more walk over the tile lists per four channels instead of a whole rasterizer call per three (include/gsr_features.h).
+    The map is differentiable w.r.t. features and w.r.t. every geometry input: means2D.grad and densify_stats see the total
+    gradient, colour plus features; absgrad stays the colour's moduli alone; contrib_stats is unaffected.  If the map receives no
+    gradient its backward pass is skipped; if `features` is the only input that requires a gradient, only dL/dfeatures is computed
+    (no colour backward).  A CPU tensor, a wrong dtype or a wrong shape raise before anything runs.  Out of scope, each raising
+    NotImplementedError: view_parallel.rasterize_view_parallel and ViewsInFlight with features, and SH-evaluated features (a
+    (P, M, K) coefficient tensor).  With None every call form, saved tensor and output is what it was without the keyword."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
                  contrib_pixel_weight=None, camera_grads=False, absgrad=None):
@@ -295,8 +367,10 @@ class GaussianRasterizer(nn.Module):
         return visible
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, features=None):
         raster_settings = self.raster_settings
+        if features is not None:   # refused before anything runs
+            _C.feature_tensor(features, int(means3D.size(0)))
 
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -320,7 +394,7 @@ class GaussianRasterizer(nn.Module):
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
                                                    self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
-                                                   self.absgrad)
+                                                   self.absgrad, features)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
-                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad)
+                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad, features)

@@ -82,8 +82,11 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
-                depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, absgrad=None, *camera):
-        if contrib_stats is not None:   # refused before anything runs
+                depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, absgrad=None, *camera,
+                _features=None):
+        if _features is not None:       # refused before anything runs
+            _C.feature_tensor(_features, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
+        if contrib_stats is not None:   # the same
             _C.contrib_stat_tensors(contrib_stats, int(xyz.size(0)))
         if absgrad is not None:         # the same; only the backward writes the tensors (GaussianRasterizer, absgrad)
             _C.absgrad_tensors(absgrad, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
@@ -94,27 +97,47 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             _C.gaussian_contributions(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width, raster_settings.image_height,
                                       contrib_stats, contrib_pixel_weight, raster_settings.debug)
         ctx.raster_settings, ctx.num_rendered, ctx.M, ctx.stats, ctx.depth_alpha = raster_settings, R, M, stats, depth_alpha
+        fmap = ()
+        if _features is not None:   # the feature map of GaussianRasterizer (features=), from the state the render just left
+            fmap = (_C.features_forward(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width,
+                                        raster_settings.image_height, _features, raster_settings.debug),)
+        ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
         ctx.antialiasing = antialiasing
         ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
         # after the state: the aux state of the maps, and the opacity logits that the anti-aliased backward reads (the records hold
         # sigmoid(logit) * rho), each saved on its path only
-        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *maps[2:],
-                              *((opacity,) if antialiasing else ()))
+        ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
+                              *(() if _features is None else (_features,)), *maps[2:], *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
-        return (color, radii, *maps[:2])
+        return (color, radii, *maps[:2], *fmap)
 
     @staticmethod
     def backward(ctx, grad_color, _, grad_depth=None, grad_alpha=None):
+        return _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha, None)[1]
+
+    @staticmethod
+    def backward_with(ctx, grad_color, grad_depth, grad_alpha, grad_features_map):
+        """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
         xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *extra = ctx.saved_tensors
         dev = xyz.device
+        off = 1 if ctx.features else 0
+        fb = None
+        if ctx.features:
+            features, extra = extra[0], extra[1:]
+            if grad_features_map is not None and ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:]):
+                # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
+                return (_C.features_backward_only(geom, binning, img, R, int(xyz.size(0)), st.image_width, st.image_height, features,
+                                                  grad_features_map, st.debug), (None,) * (14 + (3 if ctx.camera else 0)))
+            if grad_features_map is not None:   # (no gradient reached the map: the feature pass is skipped)
+                fb = _C.FeatureBackward(features, grad_features_map)
         if grad_color is None:
             grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=dev)
         P = int(xyz.size(0))
         f32 = dict(dtype=torch.float32, device=dev)
-        cam_needs = tuple(ctx.needs_input_grad[14:17]) if ctx.camera else ()
+        cam_needs = tuple(ctx.needs_input_grad[14 + off:17 + off]) if ctx.camera else ()
         cam, cam_grads = None, (None, None, None) if ctx.camera else ()
         with torch.cuda.device(dev):
             alloc = torch.zeros if P == 0 else torch.empty
@@ -136,17 +159,36 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                 if any(cam_needs):
                     cam, outs = _C.camera_backward_args(P, dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
-                                absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev))
+                                absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb)
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
                 cam_grads = camera_grad_results(cam_needs, outs, (st.viewmatrix, st.projmatrix, st.campos))
-        return (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, None, *cam_grads)
+        grad_features = None
+        if fb is not None:   # (no Gaussian: nothing ran)
+            grad_features = fb.grad if fb.grad is not None else torch.zeros_like(fb.features)
+        return grad_features, (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, None,
+                               *cam_grads)
+
+
+class _RasterizeLeafGaussiansFeatures(torch.autograd.Function):
+    """_RasterizeLeafGaussians with `features` (P, K) in front of its inputs -> (color, radii[, depth, alpha], feature_map (K, H, W)),
+    the counterpart of diff_gaussian_rasterization._RasterizeGaussiansFeatures."""
+
+    @staticmethod
+    def forward(ctx, features, *inputs):
+        return _RasterizeLeafGaussians.forward(ctx, *inputs, _features=features)
+
+    @staticmethod
+    def backward(ctx, grad_color, _, *grads):
+        grad_depth, grad_alpha = grads[:2] if len(grads) == 3 else (None, None)
+        grad_features, rest = _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha, grads[-1])
+        return (grad_features, *rest)
 
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                              depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
-                             absgrad=None):
+                             absgrad=None, features=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -155,12 +197,17 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     GaussianRasterizer(raster_settings, antialiasing=True); the opacity gradient is w.r.t. the logits as always.
     contrib_stats / contrib_pixel_weight: the blend-weight statistics of GaussianRasterizer, updated by the forward.
     camera_grads: the settings' viewmatrix, projmatrix and campos take part in autograd, as in GaussianRasterizer.
-    absgrad: (abs_mean2D, abs_gradient_accum), the absolute screen-space gradients of GaussianRasterizer, written by the backward."""
+    absgrad: (abs_mean2D, abs_gradient_accum), the absolute screen-space gradients of GaussianRasterizer, written by the backward.
+    features: (P, K) float32 feature channels; the tuple then ends with feature_map (K, H, W), as GaussianRasterizer's (features=):
+    differentiable w.r.t. features and, through the colour backward's slots, w.r.t. the leaves."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
-    return _RasterizeLeafGaussians.apply(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats,
-                                         depth_alpha, _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad,
-                                         *camera_inputs(raster_settings, camera_grads))
+    inputs = (xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats, depth_alpha,
+              _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+    if features is None:
+        return _RasterizeLeafGaussians.apply(*inputs)
+    _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
+    return _RasterizeLeafGaussiansFeatures.apply(features, *inputs)
 
 
 class FusedAdam(torch.optim.Optimizer):

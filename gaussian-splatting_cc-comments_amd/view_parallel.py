@@ -239,7 +239,7 @@ class _RasterizeViewParallel(torch.autograd.Function):
 
 
 def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
-                            antialiasing=False, camera_grads=False, absgrad=None):
+                            antialiasing=False, camera_grads=False, absgrad=None, features=None):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
@@ -251,6 +251,9 @@ def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations,
     if absgrad is not None:
         raise NotImplementedError("rasterize_view_parallel: absolute gradients (absgrad) have no view-parallel form: the statistic "
                                   "is not folded over ranks (include/gsr_absgrad.h)")
+    if features is not None:
+        raise NotImplementedError("rasterize_view_parallel: feature channels (features=) have no view-parallel form: dL/dfeatures is "
+                                  "not exchanged over ranks (include/gsr_features.h)")
     return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
                                         _C.aa_flag(antialiasing))
 
@@ -368,9 +371,14 @@ class ViewsInFlight:
         # the previous view's per-Gaussian backward, instead of like phases of `in_flight` views running side by side
         self.staggered = staggered
 
-    def forward_backward(self, render_fns, upstream_grads):
+    def forward_backward(self, render_fns, upstream_grads, features=None):
         """Forward and backward of every view, `in_flight` at a time; returns the images (detached).  Work issued before the call on
-        the current stream is waited for by the side streams, and the current stream waits for them at the end."""
+        the current stream is waited for by the side streams, and the current stream waits for them at the end.
+        features: not supported (NotImplementedError) -- a render_fn returns its image alone, and a feature map's gradient has no
+        place in upstream_grads; render feature maps with GaussianRasterizer (features=) view by view."""
+        if features is not None:
+            raise NotImplementedError("ViewsInFlight: feature channels (features=) are not supported: a view's feature map and its "
+                                      "gradient have no place in render_fns / upstream_grads (include/gsr_features.h)")
         cur = torch.cuda.current_stream(self.device)
         n = len(self.streams)
         images = []
