@@ -14,6 +14,7 @@
 #include "../../include/gsr_aa.h"
 #include "../../include/gsr_contrib.h"
 #include "../../include/gsr_features.h"
+#include "../../include/gsr_distortion.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1247,6 +1248,70 @@ extern "C" int gsr_features_backward(const gsr_backward_args* args, int K, const
 		gsr_launch_features_fold(a.P, K, R, g, scratch, dL_dfeatures, s);
 	}
 	return gsr_stage_done(s, a.debug, "features_backward_fold");
+}
+
+// ---- depth-distortion map (include/gsr_distortion.h) ------------------------------------------------
+extern "C" size_t gsr_distortion_state_bytes(int width, int height)
+{
+	if (width <= 0 || height <= 0) return 0;
+	return gsr_align_up((size_t)3 * (size_t)width * (size_t)height * sizeof(float));   // the planes A, mu, S
+}
+
+extern "C" int gsr_distortion_forward(int P, int64_t R, int width, int height, const void* geometry, const void* binning, const void* image,
+                                      float* out_dist, void* state, void* stream, int debug)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_distortion_forward";
+	hipStream_t s = (hipStream_t)stream;
+	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
+	if (!out_dist || !state) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: out_dist or state is NULL", who);
+	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(state))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	int rc;
+	{
+		GsrProfScope p(s, "distortion_forward");
+		if (R == 0) {   // nothing blended: the map and the state are zeros
+			const size_t plane = (size_t)height * width * sizeof(float);
+			if ((rc = gsr_check_hip(hipMemsetAsync(out_dist, 0, plane, s), "hipMemsetAsync(distortion map)"))) return rc;
+			if ((rc = gsr_check_hip(hipMemsetAsync(state, 0, 3 * plane, s), "hipMemsetAsync(distortion state)"))) return rc;
+		} else {
+			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
+			GsrImage im = gsr_image_view((void*)image, width, height);
+			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
+			gsr_launch_distortion_forward(width, height, im, b.point_list, g.splat, out_dist, (float*)state, !(debug & GSR_DEBUG_NO_CULL), s);
+		}
+	}
+	return gsr_stage_done(s, debug, "distortion_forward");
+}
+
+extern "C" int gsr_distortion_backward(const gsr_backward_args* args, const void* state, const float* dL_ddist)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_distortion_backward";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	const gsr_backward_args& a = *args;
+	const int64_t R = a.num_rendered;
+	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (a.P == 0) return GSR_OK;
+	if (!state || !dL_ddist) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state or dL_ddist is NULL", who);
+	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(a.scratch) || !aligned16(state))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	if (R == 0) return GSR_OK;   // nothing blended: no slot to add into
+	hipStream_t s = (hipStream_t)a.stream;
+	{
+		GsrProfScope p(s, "distortion_backward");
+		GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
+		GsrImage im = gsr_image_view(a.image, a.width, a.height);
+		GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
+		gsr_launch_distortion_backward(a.width, a.height, im, b.point_list, g.splat, g.slot_base, (const float*)state, dL_ddist,
+		                               (GsrGradSlot*)a.scratch, !(a.debug & GSR_DEBUG_NO_CULL), s);
+	}
+	return gsr_stage_done(s, a.debug, "distortion_backward");
 }
 
 extern "C" size_t gsr_loss_scratch_bytes(int C, int H, int W)

@@ -270,6 +270,13 @@ void gsr_launch_features_backward_tiles(int W, int H, int K, int64_t R, GsrImage
                                         GsrGradSlot* slots, bool cull, hipStream_t s);
 void gsr_launch_features_fold(int P, int K, int64_t R, GsrGeometry g, const void* scratch, float* dL_dfeatures, hipStream_t s);
 
+// distortion.hip: the depth-distortion map of an aux-mode forward and its gradient (include/gsr_distortion.h).  state: the planes A, mu,
+// S [3][H][W]; slots: the gradient slots whose words 0..5 and 9 the backward adds into
+void gsr_launch_distortion_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out, float* state,
+                                   bool cull, hipStream_t s);
+void gsr_launch_distortion_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
+                                    const float* state, const float* dL_ddist, GsrGradSlot* slots, bool cull, hipStream_t s);
+
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
 	int P, D, M, W, H;

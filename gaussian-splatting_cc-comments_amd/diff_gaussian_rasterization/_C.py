@@ -193,6 +193,15 @@ def lib():
     L.gsr_features_forward.argtypes = [_i, _i64, _i, _i, _i] + [_vp] * 5 + [_vp, _i]
     L.gsr_features_backward.restype = _i
     L.gsr_features_backward.argtypes = [pb, _i, _vp, _vp, _vp, _vp, _i]
+    # include/gsr_distortion.h: the depth-distortion map of an aux-mode forward and its gradient.  (An older library loaded through
+    # use_library() for an A/B run has no such entry points: a call then fails with AttributeError, nothing stands in for them.)
+    if hasattr(L, "gsr_distortion_forward"):
+        L.gsr_distortion_state_bytes.restype = _sz
+        L.gsr_distortion_state_bytes.argtypes = [_i, _i]
+        L.gsr_distortion_forward.restype = _i
+        L.gsr_distortion_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 5 + [_vp, _i]
+        L.gsr_distortion_backward.restype = _i
+        L.gsr_distortion_backward.argtypes = [pb, _vp, _vp]
     _lib = L
     return L
 
@@ -430,7 +439,7 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
 
 
 def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None,
-                 features=None):
+                 features=None, distortion=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
@@ -442,7 +451,12 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     features: FeatureBackward (include/gsr_features.h) when a feature map took part in the loss: its pass runs between the blend (and
     the absgrad fold) and the per-Gaussian parts, adds the map's share of dL/dmean2D, dL/dconic and dL/dopacity into the slots and
     leaves dL/dfeatures in features.grad.  The slots are complete before the first part runs, so x, opacities, cam, absgrad and parts
-    work unchanged."""
+    work unchanged.
+    distortion: DistortionBackward (include/gsr_distortion.h) when the distortion map took part in the loss: its pass runs at the same
+    place, behind the features', and adds into the slots' words 0..5 and 9 -- x (the AuxArgs) is then required, so that the aux
+    kernels write and chain word 9."""
+    if distortion is not None and x is None:
+        raise RuntimeError("run_backward: the distortion map's backward needs the depth-and-alpha kernels (x is None)")
     if cam is not None and parts is not None:
         raise NotImplementedError("camera gradients need the whole scene in one per-Gaussian pass: not with `parts`")
     if absgrad is not None and parts is not None:
@@ -455,6 +469,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
         _check(L.gsr_absgrad_fold(ra, ctypes.byref(absgrad), 0, a.P))
     if features is not None:
         features.run(a, device, into_slots=True)
+    if distortion is not None:
+        distortion.run(a, device)
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
@@ -469,7 +485,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
 
 
 def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None,
-                    features=None):
+                    features=None, distortion=None):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -530,7 +546,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
                 run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
-                             absgrad=ab, features=features)
+                             absgrad=ab, features=features, distortion=distortion)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
@@ -573,15 +589,17 @@ def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, r
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
-                                             camera_grads=False, absgrad=None, features=None):
+                                             camera_grads=False, absgrad=None, features=None, distortion=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
     precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad /
-    features: as there."""
+    features: as there.  distortion: DistortionBackward(state, dL_ddistortion) when the map of distortion_forward() took part in
+    the loss; its share is in the eight results, dL/dv chained to dL_dmeans3D (include/gsr_distortion.h)."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
-                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features)
+                            imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features,
+                           distortion)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------
@@ -717,6 +735,55 @@ def features_backward_only(geomBuffer, binningBuffer, imgBuffer, num_rendered, P
     with torch.cuda.device(dev):
         a.stream = _stream(dev)
         return fb.run(a, dev, into_slots=False)
+
+
+# ---- the depth-distortion map (include/gsr_distortion.h) ---------------------------------------------------------------------------
+def distortion_flag(distortion, depth_alpha=None):
+    """Checks the `distortion` keyword: a bool (anything else raises TypeError), and True only together with a depth_alpha mode
+    (ValueError: the depth value v_i lives only in the records of a depth-and-alpha forward) -> the bool.  No library is touched."""
+    if not isinstance(distortion, bool):
+        raise TypeError(f"distortion must be a bool, got {type(distortion).__name__}")
+    if distortion and depth_alpha is None:
+        raise ValueError('distortion=True needs depth_alpha="depth" or "invdepth": the depth values v_i of the map live only in the '
+                         "records of a depth-and-alpha forward")
+    return distortion
+
+
+def distortion_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, P, W, H, debug=0):
+    """-> (distortion (1, H, W), state (3, H, W)): Dist = sum_{j<i} w_i w_j (v_i - v_j)^2 of the view whose depth-and-alpha forward
+    left the three state buffers, with the colour pass's own weights and the records' depth values, accumulated centred; state = the
+    per-pixel (A, mu, S) that DistortionBackward reads.  Zeros where fewer than two Gaussians blend.  Nothing of the state buffers is
+    written."""
+    P, R, W, H = int(P), int(num_rendered), int(W), int(H)
+    dev = imgBuffer.device
+    if not imgBuffer.is_cuda:
+        raise RuntimeError(f"imgBuffer must be a HIP (cuda) tensor (got {dev}); the HIP rasterizer has no CPU path")
+    with torch.cuda.device(dev):
+        alloc = torch.zeros if P == 0 else torch.empty
+        out = alloc((1, H, W), dtype=torch.float32, device=dev)
+        state = alloc((3, H, W), dtype=torch.float32, device=dev)
+        if P > 0:
+            _check(lib().gsr_distortion_forward(P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(out), _ptr(state),
+                                                _stream(dev), _dbg(debug)))
+    return out, state
+
+
+class DistortionBackward:
+    """The distortion map's part of one backward: the state distortion_forward() returned and dL_ddistortion (1, H, W) or (H, W).
+    run() adds its share into the gradient slots between the aux blend and the per-Gaussian pass."""
+
+    def __init__(self, state, dL_ddist):
+        self.state = state
+        self.dL_ddist = _dev_f32(dL_ddist, state.device, "dL_ddistortion")
+        if tuple(self.dL_ddist.shape[-2:]) != tuple(state.shape[-2:]) or self.dL_ddist.numel() != state.numel() // 3:
+            raise RuntimeError(f"dL_ddistortion must have shape (1, {state.size(1)}, {state.size(2)}), got {tuple(self.dL_ddist.shape)}")
+
+    def run(self, a, device):
+        if (int(a.height), int(a.width)) != tuple(self.state.shape[-2:]):
+            raise RuntimeError(f"the distortion state is of a {tuple(self.state.shape[-2:])} image, the backward of {(a.height, a.width)}")
+        if int(a.P) == 0:
+            return
+        _check(lib().gsr_distortion_backward(ctypes.byref(a), _ptr(self.state), _ptr(self.dL_ddist)))
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------

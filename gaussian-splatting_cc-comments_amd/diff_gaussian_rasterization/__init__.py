@@ -30,9 +30,12 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                   contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
 
 
-def _apply(features, *inputs):
+def _apply(features, *inputs, distortion=False):
     """features=None: the Function of every release so far, on its own inputs; a tensor: the Function that takes it in front of them
-    and returns the feature map behind the other outputs."""
+    and returns the feature map behind the other outputs.  distortion=True: the Function that returns the distortion map behind
+    depth and alpha, with `features` (a tensor or None) in front of the inputs."""
+    if distortion:
+        return _RasterizeGaussiansDistortion.apply(features, *inputs)
     if features is None:
         return _RasterizeGaussians.apply(*inputs)
     return _RasterizeGaussiansFeatures.apply(features, *inputs)
@@ -53,12 +56,14 @@ def camera_grad_results(needs, grads, inputs):
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
-                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None):
-    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, feature_map])"""
+                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None, distortion=False):
+    """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, distortion (1,H,W)]
+    [, feature_map])"""
     _C.aux_mode(depth_alpha)
+    distortion = _C.distortion_flag(distortion, depth_alpha)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), distortion=distortion)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -75,13 +80,17 @@ class _RasterizeGaussians(torch.autograd.Function):
     the backward writes the tensors; a non-tensor input, so the saved tensors stay as they are and the gradient tuple grows by a None.
 
     Feature channels (include/gsr_features.h): _RasterizeGaussiansFeatures below takes `features` (P, K) in front of these inputs
-    and runs this forward and backward with it; through apply() of this class nothing of them is reached."""
+    and runs this forward and backward with it; through apply() of this class nothing of them is reached.
+
+    Distortion map (include/gsr_distortion.h): _RasterizeGaussiansDistortion below runs this forward with _distortion=True, which
+    returns the map behind depth and alpha and saves its per-pixel state behind the aux buffer; the same holds for it."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None, absgrad=None, *camera, _features=None):
-        if _features is not None:       # refused before anything runs
+                contrib_pixel_weight=None, absgrad=None, *camera, _features=None, _distortion=False):
+        _C.distortion_flag(_distortion, depth_alpha)   # refused before anything runs
+        if _features is not None:       # the same
             _C.feature_tensor(_features, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
         if contrib_stats is not None:   # the same
             _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
@@ -139,36 +148,44 @@ class _RasterizeGaussians(torch.autograd.Function):
             fmap = (_C.features_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
                                         raster_settings.image_width, raster_settings.image_height, _features, raster_settings.debug),)
 
+        dmap = dstate = ()
+        if _distortion:
+            # the distortion map, from the same state and weights and the records' depth values
+            d, st = _C.distortion_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
+                                          raster_settings.image_width, raster_settings.image_height, raster_settings.debug)
+            dmap, dstate = (d,), (st,)
+
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
         ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
+        ctx.distortion = _distortion           # then input 0 is `features` too, a tensor or None
         ctx.num_rendered = num_rendered
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
         ctx.camera = len(camera) == 3
         ctx.absgrad = absgrad
-        # after the reference's ten: the aux state of the maps, and the opacity input that the anti-aliased backward reads (the records
-        # hold opacity * rho), each saved on its path only
+        # after the reference's ten: the aux state of the maps, the distortion map's per-pixel state, and the opacity input that the
+        # anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:],
+                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:], *dstate,
                               *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
         ctx.set_materialize_grads(False)
-        return (color, radii, *maps[:2], *fmap)
+        return (color, radii, *maps[:2], *dmap, *fmap)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
         return _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, None)[1]
 
     @staticmethod
-    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map):
+    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None):
         """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         num_rendered = ctx.num_rendered
         raster_settings = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, *extra) = ctx.saved_tensors
-        off = 1 if ctx.features else 0
+        off = 1 if (ctx.features or ctx.distortion) else 0
         n_in = 15 + (3 if ctx.camera else 0)
         fb = None
         if ctx.features:
@@ -183,6 +200,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_out_color is None:  # the image took no part in the loss: the zero gradient autograd would have materialised
             grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
                                          dtype=torch.float32, device=means3D.device)
+        if ctx.distortion and grad_distortion is not None:
+            # (no gradient reached the map: nothing of it runs, and without dL/dD and dL/dA the default backward kernels do)
+            kw_dist = {"distortion": _C.DistortionBackward(extra[1], grad_distortion)}
+        else:
+            kw_dist = {}
         kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
         cam_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera else ()
         if any(cam_needs):
@@ -216,10 +238,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             imgBuffer,
             raster_settings.debug,
         )
-        if grad_depth is not None or grad_alpha is not None:
+        if grad_depth is not None or grad_alpha is not None or kw_dist:
+            # (the map's gradient alone still takes the aux kernels: they write the slots' dL/dv word and chain it)
             hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
             grads = _C.rasterize_gaussians_backward_depth_alpha(ctx.depth_alpha, *args[:-1], extra[0], hw(grad_depth), hw(grad_alpha),
-                                                                raster_settings.debug, stats=ctx.densify_stats, **kw)
+                                                                raster_settings.debug, stats=ctx.densify_stats, **kw, **kw_dist)
         elif raster_settings.debug and ctx.depth_alpha is None and not any(cam_needs):  # reference __init__.py:141-148
             cpu_args = cpu_deep_copy_tuple(args)
             try:
@@ -277,6 +300,24 @@ class _RasterizeGaussiansFeatures(torch.autograd.Function):
     def backward(ctx, grad_out_color, _, *grads):
         grad_depth, grad_alpha = grads[:2] if len(grads) == 3 else (None, None)
         grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grads[-1])
+        return (grad_features, *rest)
+
+
+class _RasterizeGaussiansDistortion(torch.autograd.Function):
+    """_RasterizeGaussians with a depth_alpha mode and the distortion map -> (color, radii, depth, alpha, distortion (1, H, W)
+    [, feature_map]): distortion = sum_{j<i} w_i w_j (v_i - v_j)^2 with the colour pass's own weights and the depth values of the
+    depth map, differentiable w.r.t. every geometry input through the gradient slots of the aux backward
+    (include/gsr_distortion.h).  `features` (P, K) or None sits in front of the inputs, as in _RasterizeGaussiansFeatures.  The other
+    outputs have the bits of _RasterizeGaussians."""
+
+    @staticmethod
+    def forward(ctx, features, *inputs):
+        return _RasterizeGaussians.forward(ctx, *inputs, _features=features, _distortion=True)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, grad_depth, grad_alpha, grad_distortion, *grad_fmap):
+        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha,
+                                                                grad_fmap[0] if grad_fmap else None, grad_distortion)
         return (grad_features, *rest)
 
 
@@ -343,13 +384,25 @@ class GaussianRasterizer(nn.Module):
     gradient its backward pass is skipped; if `features` is the only input that requires a gradient, only dL/dfeatures is computed
     (no colour backward).  A CPU tensor, a wrong dtype or a wrong shape raise before anything runs.  Out of scope, each raising
     NotImplementedError: view_parallel.rasterize_view_parallel and ViewsInFlight with features, and SH-evaluated features (a
-    (P, M, K) coefficient tensor).  With None every call form, saved tensor and output is what it was without the keyword."""
+    (P, M, K) coefficient tensor).  With None every call form, saved tensor and output is what it was without the keyword.
+
+    distortion (extension, default False; needs depth_alpha): forward() then returns the depth-distortion map behind depth and
+    alpha, (color, radii, depth, alpha, distortion[, feature_map]) -- distortion (1, H, W) = sum_{j<i} w_i w_j (v_i - v_j)^2 with
+    w = alpha T the colour pass's own weights and v the depth values of the depth map (z for "depth", 1 / z for "invdepth"): the
+    per-ray spread of the blend weights along depth, Mip-NeRF 360's distortion loss in the pairwise squared form of 2DGS (gsplat's
+    `distloss`).  No background term, 0 where fewer than two Gaussians blend, invariant under v -> v - c and accumulated centred,
+    so a far scene keeps its digits (include/gsr_distortion.h).  Differentiable w.r.t. every geometry input, the depths included:
+    means2D.grad and densify_stats see the total gradient; absgrad stays the colour's moduli.  When the map's gradient reaches the
+    backward the depth-and-alpha backward kernels run, with or without dL/ddepth and dL/dalpha; when it does not, nothing of this
+    runs in the backward.  A bool, anything else raises TypeError; True without depth_alpha raises ValueError.  Out of scope
+    (NotImplementedError): view_parallel.rasterize_view_parallel and ViewsInFlight."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
-                 contrib_pixel_weight=None, camera_grads=False, absgrad=None):
+                 contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
+        self.distortion = _C.distortion_flag(distortion, depth_alpha)   # TypeError for anything but a bool, ValueError without a mode
         self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
         self.camera_grads = _C.camera_flag(camera_grads)   # the same
         self.raster_settings = raster_settings
@@ -394,7 +447,7 @@ class GaussianRasterizer(nn.Module):
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
                                                    self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
-                                                   self.absgrad, features)
+                                                   self.absgrad, features, self.distortion)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
                                    self.contrib_pixel_weight, self.camera_grads, self.absgrad, features)

@@ -83,8 +83,9 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                 depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, absgrad=None, *camera,
-                _features=None):
-        if _features is not None:       # refused before anything runs
+                _features=None, _distortion=False):
+        _C.distortion_flag(_distortion, depth_alpha)   # refused before anything runs
+        if _features is not None:       # the same
             _C.feature_tensor(_features, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
         if contrib_stats is not None:   # the same
             _C.contrib_stat_tensors(contrib_stats, int(xyz.size(0)))
@@ -101,29 +102,35 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         if _features is not None:   # the feature map of GaussianRasterizer (features=), from the state the render just left
             fmap = (_C.features_forward(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width,
                                         raster_settings.image_height, _features, raster_settings.debug),)
+        dmap = dstate = ()
+        if _distortion:   # the distortion map of GaussianRasterizer (distortion=True), from the same state
+            d, dst = _C.distortion_forward(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width,
+                                           raster_settings.image_height, raster_settings.debug)
+            dmap, dstate = (d,), (dst,)
         ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
+        ctx.distortion = _distortion           # then input 0 is `features` too, a tensor or None
         ctx.antialiasing = antialiasing
         ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
-        # after the state: the aux state of the maps, and the opacity logits that the anti-aliased backward reads (the records hold
-        # sigmoid(logit) * rho), each saved on its path only
+        # after the state: the aux state of the maps, the distortion map's per-pixel state, and the opacity logits that the anti-aliased
+        # backward reads (the records hold sigmoid(logit) * rho), each saved on its path only
         ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
-                              *(() if _features is None else (_features,)), *maps[2:], *((opacity,) if antialiasing else ()))
+                              *(() if _features is None else (_features,)), *maps[2:], *dstate, *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
-        return (color, radii, *maps[:2], *fmap)
+        return (color, radii, *maps[:2], *dmap, *fmap)
 
     @staticmethod
     def backward(ctx, grad_color, _, grad_depth=None, grad_alpha=None):
         return _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha, None)[1]
 
     @staticmethod
-    def backward_with(ctx, grad_color, grad_depth, grad_alpha, grad_features_map):
+    def backward_with(ctx, grad_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None):
         """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
         xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *extra = ctx.saved_tensors
         dev = xyz.device
-        off = 1 if ctx.features else 0
+        off = 1 if (ctx.features or ctx.distortion) else 0
         fb = None
         if ctx.features:
             features, extra = extra[0], extra[1:]
@@ -152,14 +159,18 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                 _C.set_backward_outputs(a, dL_dmean2D=d_means2D, dL_dmean3D=d_xyz, dL_dsh=d_dc, dL_dsh_rest=d_rest,
                                         dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
                 _C.set_backward_stats(a, ctx.stats, P, dev)
-                x = None
-                if grad_depth is not None or grad_alpha is not None:
+                x = db = None
+                if ctx.distortion and grad_distortion is not None:   # (no gradient reached the map: nothing of it runs)
+                    db = _C.DistortionBackward(extra[1], grad_distortion)
+                if grad_depth is not None or grad_alpha is not None or db is not None:
+                    # (the distortion map's gradient alone still takes the aux kernels: they write the slots' dL/dv word and chain it)
                     hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
                     x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
                 if any(cam_needs):
                     cam, outs = _C.camera_backward_args(P, dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
-                                absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb)
+                                absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb,
+                                distortion=db)
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
@@ -186,9 +197,25 @@ class _RasterizeLeafGaussiansFeatures(torch.autograd.Function):
         return (grad_features, *rest)
 
 
+class _RasterizeLeafGaussiansDistortion(torch.autograd.Function):
+    """_RasterizeLeafGaussians with a depth_alpha mode and the distortion map -> (color, radii, depth, alpha, distortion (1, H, W)
+    [, feature_map]), `features` (P, K) or None in front of its inputs: the counterpart of
+    diff_gaussian_rasterization._RasterizeGaussiansDistortion."""
+
+    @staticmethod
+    def forward(ctx, features, *inputs):
+        return _RasterizeLeafGaussians.forward(ctx, *inputs, _features=features, _distortion=True)
+
+    @staticmethod
+    def backward(ctx, grad_color, _, grad_depth, grad_alpha, grad_distortion, *grad_fmap):
+        grad_features, rest = _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha,
+                                                                    grad_fmap[0] if grad_fmap else None, grad_distortion)
+        return (grad_features, *rest)
+
+
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                              depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
-                             absgrad=None, features=None):
+                             absgrad=None, features=None, distortion=False):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -199,14 +226,20 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     camera_grads: the settings' viewmatrix, projmatrix and campos take part in autograd, as in GaussianRasterizer.
     absgrad: (abs_mean2D, abs_gradient_accum), the absolute screen-space gradients of GaussianRasterizer, written by the backward.
     features: (P, K) float32 feature channels; the tuple then ends with feature_map (K, H, W), as GaussianRasterizer's (features=):
-    differentiable w.r.t. features and, through the colour backward's slots, w.r.t. the leaves."""
+    differentiable w.r.t. features and, through the colour backward's slots, w.r.t. the leaves.
+    distortion: True (with depth_alpha) puts the depth-distortion map (1, H, W) behind depth and alpha, as GaussianRasterizer's
+    (distortion=True): differentiable w.r.t. the leaves, xyz's depth included."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
+    distortion = _C.distortion_flag(distortion, depth_alpha)
     inputs = (xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats, depth_alpha,
               _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+    if features is not None:
+        _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
+    if distortion:
+        return _RasterizeLeafGaussiansDistortion.apply(features, *inputs)
     if features is None:
         return _RasterizeLeafGaussians.apply(*inputs)
-    _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
     return _RasterizeLeafGaussiansFeatures.apply(features, *inputs)
 
 

@@ -239,7 +239,7 @@ class _RasterizeViewParallel(torch.autograd.Function):
 
 
 def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
-                            antialiasing=False, camera_grads=False, absgrad=None, features=None):
+                            antialiasing=False, camera_grads=False, absgrad=None, features=None, distortion=False):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
@@ -254,6 +254,9 @@ def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations,
     if features is not None:
         raise NotImplementedError("rasterize_view_parallel: feature channels (features=) have no view-parallel form: dL/dfeatures is "
                                   "not exchanged over ranks (include/gsr_features.h)")
+    if distortion is not False:
+        raise NotImplementedError("rasterize_view_parallel: the distortion map (distortion=) has no view-parallel form: the view-parallel "
+                                  "render has no depth-and-alpha maps (include/gsr_distortion.h)")
     return _RasterizeViewParallel.apply(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats,
                                         _C.aa_flag(antialiasing))
 
@@ -371,14 +374,18 @@ class ViewsInFlight:
         # the previous view's per-Gaussian backward, instead of like phases of `in_flight` views running side by side
         self.staggered = staggered
 
-    def forward_backward(self, render_fns, upstream_grads, features=None):
+    def forward_backward(self, render_fns, upstream_grads, features=None, distortion=False):
         """Forward and backward of every view, `in_flight` at a time; returns the images (detached).  Work issued before the call on
         the current stream is waited for by the side streams, and the current stream waits for them at the end.
         features: not supported (NotImplementedError) -- a render_fn returns its image alone, and a feature map's gradient has no
-        place in upstream_grads; render feature maps with GaussianRasterizer (features=) view by view."""
+        place in upstream_grads; render feature maps with GaussianRasterizer (features=) view by view.
+        distortion: not supported either (NotImplementedError), for the same reason."""
         if features is not None:
             raise NotImplementedError("ViewsInFlight: feature channels (features=) are not supported: a view's feature map and its "
                                       "gradient have no place in render_fns / upstream_grads (include/gsr_features.h)")
+        if distortion is not False:
+            raise NotImplementedError("ViewsInFlight: the distortion map (distortion=) is not supported: a view's map and its gradient "
+                                      "have no place in render_fns / upstream_grads (include/gsr_distortion.h)")
         cur = torch.cuda.current_stream(self.device)
         n = len(self.streams)
         images = []

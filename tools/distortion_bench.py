@@ -1,0 +1,143 @@
+"""Cost of the depth-distortion map (include/gsr_distortion.h, GaussianRasterizer(depth_alpha=..., distortion=True)) at a bench.py
+configuration:
+
+  (a) through gsr_profile_*: the forward pass against render_forward of the same step (the same walk with three colour accumulators:
+      the floor), and the backward tile pass against render_backward;
+  (b) the whole step -- forward and backward of colour, depth, alpha and the distortion loss, every input requiring a gradient --
+      against the moments workaround a user had before (features = (v - c, (v - c)^2) through `features=` plus depth_alpha,
+      A Q - D^2 formed in torch, v computed in torch so that its gradient reaches means3D) and against the plain depth_alpha step
+      without any distortion term.  Wall time between two events on the stream, the three alternated step by step; medians;
+  (c) with --parent-library: bench.py's default step (--gpus 1) with this tree's library against the parent commit's, a fresh
+      process each, alternated this / parent / this / parent; the expectation is that the two libraries differ by no more than the
+      parent's own two runs do.
+
+One JSON line, printed and appended to profiles/distortion_bench.jsonl.
+
+    python tools/distortion_bench.py --config C3 --steps 20 --warmup 3 [--parent-library libgsr_hip_parent.so]
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (R, os.path.join(R, "gaussian-splatting_cc-comments_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def bench_default_step(library, steps, warmup, config):
+    """one fresh bench.py process -> ms per step"""
+    cmd = [sys.executable, os.path.join(R, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--config", config]
+    if library:
+        cmd += ["--library", library]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, check=True).stdout
+    return json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])["ms_per_step"]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C3")
+    ap.add_argument("--mode", default="depth", choices=["depth", "invdepth"])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--parent-library", default=None, help="the parent commit's libgsr_hip.so: adds measurement (c)")
+    ap.add_argument("--bench-steps", type=int, default=200, help="(c): bench.py --steps")
+    ap.add_argument("--bench-warmup", type=int, default=20, help="(c): bench.py --warmup")
+    ap.add_argument("--out", default=os.path.join(R, "profiles", "distortion_bench.jsonl"))
+    args = ap.parse_args()
+
+    c = None
+    if args.parent_library:   # first, before this process opens the device: one process on it at a time
+        runs = {"this": [], "parent": []}
+        for _ in range(2):
+            runs["this"].append(bench_default_step(None, args.bench_steps, args.bench_warmup, args.config))
+            runs["parent"].append(bench_default_step(os.path.abspath(args.parent_library), args.bench_steps, args.bench_warmup, args.config))
+        spread = abs(runs["parent"][0] - runs["parent"][1])
+        diff = statistics.mean(runs["this"]) - statistics.mean(runs["parent"])
+        c = {"bench_steps": args.bench_steps, "bench_warmup": args.bench_warmup, "this_ms": runs["this"], "parent_ms": runs["parent"], "parent_spread_ms": round(spread, 4), "this_minus_parent_ms": round(diff, 4),
+             "within_parent_spread": bool(abs(diff) <= spread)}
+
+    import torch
+
+    import gsr_scene
+    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
+    dev = torch.device("cuda:0")
+    scene, cam, D = gsr_scene.make_config(args.config, seed=0)
+    H, W, P = cam.image_height, cam.image_width, int(scene.means3D.size(0))
+    to = lambda t: t.to(dev).contiguous()
+    st = GaussianRasterizationSettings(image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=to(scene.bg),
+                                       scale_modifier=1.0, viewmatrix=to(cam.world_view_transform), projmatrix=to(cam.full_proj_transform),
+                                       sh_degree=D, campos=to(cam.camera_center), prefiltered=False, debug=False)
+    leaf = lambda t: to(t).requires_grad_(True)
+    t = dict(means3D=leaf(scene.means3D), shs=leaf(scene.shs), opacities=leaf(scene.opacities), scales=leaf(scene.scales),
+             rotations=leaf(scene.rotations))
+    t["means2D"] = torch.zeros(P, 3, device=dev, requires_grad=True)
+    gen = torch.Generator().manual_seed(1)
+    dpix = to(torch.randn(3, H, W, generator=gen))
+    g, dD, dA = (to(torch.randn(1, H, W, generator=gen)) for _ in range(3))
+    V = st.viewmatrix
+
+    def clear():
+        for v in t.values():
+            v.grad = None
+
+    def step_new():
+        color, radii, depth, alpha, dist = GaussianRasterizer(st, depth_alpha=args.mode, distortion=True)(**t)
+        ((color * dpix).sum() + (depth * dD).sum() + (alpha * dA).sum() + (dist * g).sum()).backward()
+
+    def step_moments():
+        z = t["means3D"] @ V[:3, 2] + V[3, 2]
+        v = z if args.mode == "depth" else 1.0 / z
+        u = v - v.detach().mean()
+        color, radii, depth, alpha, m = GaussianRasterizer(st, depth_alpha=args.mode)(**t, features=torch.stack([u, u * u], 1))
+        dist = alpha[0] * m[1] - m[0] * m[0]
+        ((color * dpix).sum() + (depth * dD).sum() + (alpha * dA).sum() + (dist * g[0]).sum()).backward()
+
+    def step_plain():
+        color, radii, depth, alpha = GaussianRasterizer(st, depth_alpha=args.mode)(**t)
+        ((color * dpix).sum() + (depth * dD).sum() + (alpha * dA).sum()).backward()
+
+    wall = {"new": [], "moments": [], "plain": []}
+    stages = {}
+    for it in range(args.warmup + args.steps):
+        for name, f in (("new", step_new), ("moments", step_moments), ("plain", step_plain)):
+            clear()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(dev)
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize(dev)
+            if it >= args.warmup:
+                wall[name].append(e0.elapsed_time(e1))
+        # the stages of the new step, recorded in a step of their own (event pairs around every stage cost the step time)
+        clear()
+        _C.profile_begin(device=dev)
+        step_new()
+        for name, ms in _C.profile_end(device=dev):
+            if it >= args.warmup:
+                stages.setdefault(name, []).append(ms)
+    med = {n: statistics.median(v) for n, v in stages.items()}
+    new, mom, plain = (statistics.median(wall[k]) for k in ("new", "moments", "plain"))
+    out = {"config": args.config, "mode": args.mode, "P": P, "W": W, "H": H, "steps": args.steps, "warmup": args.warmup,
+           "a_forward_ms": {"distortion_forward": round(med["distortion_forward"], 4), "render_forward": round(med["render_forward"], 4),
+                            "over_render_forward": round(med["distortion_forward"] / med["render_forward"], 3)},
+           "a_backward_ms": {"distortion_backward": round(med["distortion_backward"], 4), "render_backward": round(med["render_backward"], 4),
+                             "over_render_backward": round(med["distortion_backward"] / med["render_backward"], 3)},
+           "b_step_ms": {"with_distortion": round(new, 4), "moments_workaround": round(mom, 4), "plain_depth_alpha": round(plain, 4),
+                         "ratio_to_workaround": round(new / mom, 3), "added_over_plain_ms": round(new - plain, 4),
+                         "workaround_added_over_plain_ms": round(mom - plain, 4), "beats_workaround": bool(new < mom)}}
+    if c is not None:
+        out["c_default_step_ms"] = c
+    line = json.dumps(out)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as fh:
+        fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
