@@ -15,6 +15,7 @@
 #include "../../include/gsr_contrib.h"
 #include "../../include/gsr_features.h"
 #include "../../include/gsr_distortion.h"
+#include "../../include/gsr_median.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1312,6 +1313,75 @@ extern "C" int gsr_distortion_backward(const gsr_backward_args* args, const void
 		                               (GsrGradSlot*)a.scratch, !(a.debug & GSR_DEBUG_NO_CULL), s);
 	}
 	return gsr_stage_done(s, a.debug, "distortion_backward");
+}
+
+// ---- median-depth and per-pixel index maps (include/gsr_median.h) -----------------------------------
+extern "C" size_t gsr_median_state_bytes(int width, int height)
+{
+	if (width <= 0 || height <= 0) return 0;
+	return gsr_align_up((size_t)width * (size_t)height * sizeof(uint32_t));   // the median's list position per pixel
+}
+
+extern "C" int gsr_median_forward(int P, int64_t R, int width, int height, const void* geometry, const void* binning, const void* image,
+                                  float* out_median_depth, int32_t* out_median_index, int32_t* out_dominant_index, float* out_dominant_weight,
+                                  void* state, void* stream, int debug)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_median_forward";
+	hipStream_t s = (hipStream_t)stream;
+	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
+	if (!out_median_depth && !out_median_index && !out_dominant_index && !out_dominant_weight)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every output is NULL", who);
+	if (out_median_depth && !state) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: out_median_depth needs state", who);
+	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(state))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	int rc;
+	{
+		GsrProfScope p(s, "median_forward");
+		if (R == 0) {   // nothing blended: depth and weight 0, indices -1, no position in the state
+			const size_t plane = (size_t)height * width * 4;
+			void* const outs[5] = {out_median_depth, out_dominant_weight, out_median_index, out_dominant_index, state};
+			for (int i = 0; i < 5; i++)
+				if (outs[i] && (rc = gsr_check_hip(hipMemsetAsync(outs[i], i < 2 ? 0 : 0xFF, plane, s), "hipMemsetAsync(median maps)"))) return rc;
+		} else {
+			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
+			GsrImage im = gsr_image_view((void*)image, width, height);
+			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
+			gsr_launch_median_forward(width, height, im, b.point_list, g.splat, out_median_depth, out_median_index, out_dominant_index,
+			                          out_dominant_weight, (uint32_t*)state, !(debug & GSR_DEBUG_NO_CULL), (debug & GSR_DEBUG_MEDIAN_FULL_WALK) != 0, s);
+		}
+	}
+	return gsr_stage_done(s, debug, "median_forward");
+}
+
+extern "C" int gsr_median_backward(const gsr_backward_args* args, const void* state, const float* dL_dmedian)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_median_backward";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	const gsr_backward_args& a = *args;
+	const int64_t R = a.num_rendered;
+	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (a.P == 0) return GSR_OK;
+	if (!state || !dL_dmedian) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state or dL_dmedian is NULL", who);
+	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(a.scratch) || !aligned16(state))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
+	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	if (R == 0) return GSR_OK;   // nothing blended: no slot to add into
+	hipStream_t s = (hipStream_t)a.stream;
+	{
+		GsrProfScope p(s, "median_backward");
+		GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
+		GsrImage im = gsr_image_view(a.image, a.width, a.height);
+		GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
+		gsr_launch_median_backward(a.width, a.height, im, b.point_list, g.splat, g.slot_base, (const uint32_t*)state, dL_dmedian,
+		                           (GsrGradSlot*)a.scratch, s);
+	}
+	return gsr_stage_done(s, a.debug, "median_backward");
 }
 
 extern "C" size_t gsr_loss_scratch_bytes(int C, int H, int W)

@@ -277,6 +277,14 @@ void gsr_launch_distortion_forward(int W, int H, GsrImage img, const uint32_t* p
 void gsr_launch_distortion_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
                                     const float* state, const float* dL_ddist, GsrGradSlot* slots, bool cull, hipStream_t s);
 
+// median.hip: the median-depth map, the per-pixel index maps and the median depth's gradient (include/gsr_median.h).  Outputs: NULL =
+// not wanted; state: the median's list position per pixel [H][W]; slots: the gradient slots whose word 9 the backward adds into
+void gsr_launch_median_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out_depth,
+                               int32_t* out_median, int32_t* out_dominant, float* out_weight, uint32_t* state, bool cull, bool full_walk,
+                               hipStream_t s);
+void gsr_launch_median_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
+                                const uint32_t* state, const float* dL_dmedian, GsrGradSlot* slots, hipStream_t s);
+
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
 	int P, D, M, W, H;

@@ -1,0 +1,271 @@
+// median.hip -- the median-depth map and the per-pixel Gaussian index maps of a forward, and the median depth's gradient
+// (include/gsr_median.h).  For pixel p, over its blended Gaussians in list order, T_i the transmittance in front of Gaussian i and
+// w_i = alpha_i T_i:
+//   median(p)   = the LAST blended Gaussian with T_i > 0.5 (2DGS: `if (T > 0.5) median = this`, before T is updated)
+//   dominant(p) = the FIRST blended Gaussian with the largest w_i (strict >)
+// Two kernels, no atomics, no workgroup barrier, bitwise reproducible.  None of the default kernels is touched: both passes read the
+// state a forward left, the way contrib.hip, features.hip and distortion.hip do.
+//
+// Decomposition (render_common.h): one wave64 per 16x16 tile, four pixels per lane, 64 instances staged per batch into the wave's LDS
+// slice behind gsr_tile_band_mask (`cull`).
+//
+// Forward: distortion.hip's forward walk (list positions [0, min(range length, tile_max_contrib)), per pixel only those in front of
+// its n_contrib; `power`, alpha, the two thresholds and T's update are render_forward.hip's instruction sequence on the same records),
+// so every decision and every w has the colour pass's bits.  Per hit, with T the value in front of the hit:
+//   if (T > 0.5) med = position;      w = alpha T;      if (w > best) { best = w; best_pos = position; }
+// Only list positions are carried; the Gaussian ids (point_list[range.x + position]) and the median's depth value v (the last word of
+// its splat record, the record's bits) are gathered once per pixel at the end -- two loads per pixel instead of a staged word and a
+// select per hit.  Outputs that were not requested (NULL) cost no stores and no gathers.  The state plane [H][W] of uint32 holds the
+// median's list position (0xFFFFFFFF: nothing blended) for the backward.
+//
+// Early exit (template argument EXIT; the twin without it is launched for GSR_DEBUG_MEDIAN_FULL_WALK).  After every batch a band whose
+// every pixel is finished stops: a pixel is finished when it has no position left in front of its n_contrib, or when T <= 0.5 and
+// T <= best.  Proof that the full walk changes nothing more for such a pixel.  Let T be its transmittance after the batch and T', alpha'
+// those of any later hit.  (i) T' <= T: every update is T <- fmul_rn(T, fsub_rn(1, alpha)) with 0 < fsub_rn(1, alpha) < 1 (alpha in
+// [1/255, 0.99]); the exact product is below T, T is representable, and rounding to nearest is monotone, so the rounded product is <= T.
+// (ii) The median test of a later hit is T' > 0.5, false by T' <= T <= 0.5: med keeps its value.  (iii) Its weight is
+// w' = fmul_rn(alpha', T') with alpha' <= 0.99 < 1: the exact product is below T', so w' <= T' <= T <= best, and the strict w' > best
+// is false: best and best_pos keep their values.  T itself is not an output.  A band is skipped by setting its wave-uniform
+// band_last to 0, the test the walk already makes per instance; the batch loop ends when no band is left.  Hence bit-identical outputs,
+// and tests compare the two instantiations.
+//
+// Backward: dL/dv_i = sum_{p : median(p) = i} g(p), nothing through alpha or T (the choice of i is piecewise constant).  No alpha is
+// recomputed and no list is walked: the wave reads its 256 state positions and g, and loops over the DISTINCT positions present (at
+// most 256; 88 over the four tiles of the 32x32 test scene) instead of the tile's list (hundreds to thousands of instances, each with a
+// staged record, a band test and the pair arithmetic on four pixels): per distinct position q one ballot, one readlane, four selects
+// and a six-step xor butterfly of the lanes' partial sums -- a fixed order, every lane ends with the same bits.  The
+// (q, total) pairs go to the wave's LDS; then lane l takes pairs l, l + 64, ...: id = point_list[range.x + q], the slot as
+// distortion.hip forms it (slot_base[id] plus the rect offset from the record), and one read-modify-write of word 9 (pad0, the aux
+// blend's own dL/dv).  Distinct positions of one tile are distinct Gaussians, so distinct slots: each (Gaussian, tile) slot receives
+// at most one addition per launch and the order across instances is irrelevant.  The median blended, so its slot is one the colour
+// blend validated; the unchanged aux per-Gaussian backward chains word 9 along the view z axis.  Heavy tiles are one wave like any other.
+//
+// Registers (hipcc 7.x, gfx950, -O3 -ffp-contract=off; `make audit`, .audit/median.s): see DESIGN.md 6k.
+#include "render_common.h"
+
+#define GSR_MEDIAN_NONE 0xFFFFFFFFu
+
+template <bool EXIT>
+__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_median_forward_kernel(
+	int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+	const GsrSplat* __restrict__ splat, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,
+	float* __restrict__ out_depth, int32_t* __restrict__ out_median, int32_t* __restrict__ out_dominant, float* __restrict__ out_weight,
+	uint32_t* __restrict__ state, int cull)
+{
+	// the surviving instances of a batch: (x, y, -0.5 conic a, conic b), (-0.5 conic c, opacity, list position, -)
+	__shared__ float4 s_rec[GSR_WAVES_PER_WG][2][64];
+	__shared__ uint32_t s_bands[GSR_WAVES_PER_WG][64];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int tile = blockIdx.x * GSR_WAVES_PER_WG + wave;
+	if (tile >= ntiles) return;  // wave-uniform; no barriers below
+	float4(*rec)[64] = s_rec[wave];
+	uint32_t* recb = s_bands[wave];
+
+	const int tx = tile % gx, ty = tile / gx;
+	const int px = tx * GSR_TILE_X + (lane & 15);
+	const int py0 = ty * GSR_TILE_Y + (lane >> 4);
+	const float pfx = (float)px;
+	const float x0f = (float)(tx * GSR_TILE_X), y0f = (float)(ty * GSR_TILE_Y);
+
+	const uint2 range = ranges[tile];
+	const int n = (int)min(range.y - range.x, tile_max_contrib[tile]);  // the tail was never blended; 0: the tile's pixels get "none"
+	const uint32_t* plist = point_list + range.x;
+
+	float T[GSR_PIX_PER_LANE], pfy[GSR_PIX_PER_LANE];
+	float best[GSR_PIX_PER_LANE];           // the largest w so far
+	uint32_t med[GSR_PIX_PER_LANE];         // list position of the last hit with T > 0.5
+	uint32_t bpos[GSR_PIX_PER_LANE];        // list position of the first hit with w = best
+	uint32_t last[GSR_PIX_PER_LANE];        // the pixel's n_contrib: it blended positions in front of this one only (0 outside the image)
+	uint32_t band_last[GSR_PIX_PER_LANE];   // wave-uniform: the largest of them in band k; 0 once the band has finished (EXIT)
+#pragma unroll
+	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+		const int py = py0 + 4 * k;
+		const bool inside = px < W && py < H;
+		const uint32_t pix_id = inside ? (uint32_t)(W * py + px) : 0u;
+		pfy[k] = (float)py;
+		T[k] = 1.0f;
+		best[k] = 0.f;
+		med[k] = GSR_MEDIAN_NONE; bpos[k] = GSR_MEDIAN_NONE;
+		last[k] = inside ? n_contrib[pix_id] : 0u;
+		uint32_t lm = last[k];
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) lm = max(lm, (uint32_t)__shfl_xor((int)lm, off, 64));
+		band_last[k] = __builtin_amdgcn_readfirstlane(lm);
+	}
+
+	// software pipeline: records one batch ahead, ids two batches ahead
+	float4 ra = make_float4(0, 0, 0, 0), rb = ra;
+	if (lane < n) {
+		const uint32_t id = plist[lane];
+		const float4* p = reinterpret_cast<const float4*>(splat + id);
+		ra = p[0]; rb = p[1];
+	}
+	uint32_t id_next = (64 + lane < n) ? plist[64 + lane] : 0u;
+
+	for (int base = 0; base < n; base += 64) {
+		const uint32_t bands = (base + lane < n) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
+		const bool keep = bands != 0u;
+		const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
+		const int cnt = __popcll(mask);
+		if (keep) {
+			const int pos = gsr_mbcnt(mask);
+			rec[0][pos] = make_float4(ra.x, ra.y, -0.5f * ra.z, ra.w);  // conic a, c pre-multiplied by -0.5 (exact)
+			rec[1][pos] = make_float4(-0.5f * rb.x, rb.y, __uint_as_float((uint32_t)(base + lane)), 0.f);
+			recb[pos] = bands;
+		}
+		if (base + 64 + lane < n) {
+			const float4* p = reinterpret_cast<const float4*>(splat + id_next);
+			ra = p[0]; rb = p[1];
+		}
+		id_next = (base + 128 + lane < n) ? plist[base + 128 + lane] : 0u;
+		__builtin_amdgcn_wave_barrier();
+
+		for (int j = 0; j < cnt; j++) {
+			const float4 RA = rec[0][j];   // x, y, -0.5 conic a, conic b
+			const float4 RB = rec[1][j];   // -0.5 conic c, opacity, list position, -
+			const uint32_t position = __builtin_amdgcn_readfirstlane(__float_as_uint(RB.z));   // wave-uniform
+			const uint32_t jbands = __builtin_amdgcn_readfirstlane(recb[j]);                  // wave-uniform
+			const float dx = RA.x - pfx;
+			const float ax2 = __fmul_rn(__fmul_rn(RA.z, dx), dx), bdx = __fmul_rn(RA.w, dx);
+#pragma unroll
+			for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+				if (!(jbands & (1u << k)) || position >= band_last[k]) continue;  // scalar branch: the band cannot be reached, or it had finished
+				const float dy = RA.y - pfy[k];
+				const float power = gsr_pair_power_halved(ax2, bdx, RB.x, dy);
+				const float alpha = fminf(0.99f, RB.y * __expf(power));
+				const unsigned long long hitm = __builtin_amdgcn_ballot_w64(position < last[k]) & __builtin_amdgcn_ballot_w64(!(power > 0.0f)) &
+				                                __builtin_amdgcn_ballot_w64(!(alpha < 1.0f / 255.0f));
+				if (hitm == 0ull) continue;  // wave-uniform
+				const bool hit = __builtin_amdgcn_inverse_ballot_w64(hitm);
+				const float Tk = T[k];                                                // T in front of this instance
+				const float w = hit ? __fmul_rn(alpha, Tk) : 0.0f;                    // the forward's alpha * T; 0 never beats best >= 0
+				T[k] = hit ? __fmul_rn(Tk, __fsub_rn(1.0f, alpha)) : Tk;              // ... and its T (1 - alpha), rounded as there
+				med[k] = (hit && Tk > 0.5f) ? position : med[k];
+				const bool better = w > best[k];
+				best[k] = better ? w : best[k];
+				bpos[k] = better ? position : bpos[k];
+			}
+		}
+		__builtin_amdgcn_wave_barrier();
+
+		if (EXIT) {
+			// a band stops once each of its pixels has blended its last position or can change no more (the proof is in the header)
+			const uint32_t next = (uint32_t)base + 64u;   // every position below it has been walked
+			bool any = false;
+#pragma unroll
+			for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+				if (band_last[k] <= next) continue;   // finished, here or by its n_contrib
+				const bool open = next < last[k] && (T[k] > 0.5f || T[k] > best[k]);
+				if (__builtin_amdgcn_ballot_w64(open) == 0ull) band_last[k] = 0u;
+				else any = true;
+			}
+			if (!any) break;   // wave-uniform
+		}
+	}
+
+#pragma unroll
+	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+		const int py = py0 + 4 * k;
+		if (px < W && py < H) {
+			const size_t pix_id = (size_t)W * py + px;
+			const bool some = med[k] != GSR_MEDIAN_NONE;   // one hit sets both positions: the first hit has T = 1 and w > 0
+			if (state) state[pix_id] = med[k];
+			if (out_depth || out_median) {
+				const uint32_t id = some ? plist[med[k]] : 0u;
+				if (out_median) out_median[pix_id] = some ? (int32_t)id : -1;
+				if (out_depth) out_depth[pix_id] = some ? reinterpret_cast<const float*>(splat + id)[11] : 0.f;   // the record's v
+			}
+			if (out_dominant) out_dominant[pix_id] = some ? (int32_t)plist[bpos[k]] : -1;
+			if (out_weight) out_weight[pix_id] = best[k];
+		}
+	}
+}
+
+__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_median_backward_kernel(
+	int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+	const GsrSplat* __restrict__ splat, const uint32_t* __restrict__ slot_base, const uint32_t* __restrict__ state,
+	const float* __restrict__ dL_dmedian, GsrGradSlot* slots)
+{
+	// the distinct median positions of the tile and the sum of g over the pixels of each
+	__shared__ uint32_t s_q[GSR_WAVES_PER_WG][256];
+	__shared__ float s_t[GSR_WAVES_PER_WG][256];
+	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const int tile = blockIdx.x * GSR_WAVES_PER_WG + wave;
+	if (tile >= ntiles) return;  // wave-uniform; no barriers below
+	uint32_t* sq = s_q[wave];
+	float* stot = s_t[wave];
+
+	const int tx = tile % gx, ty = tile / gx;
+	const int px = tx * GSR_TILE_X + (lane & 15);
+	const int py0 = ty * GSR_TILE_Y + (lane >> 4);
+	const uint2 range = ranges[tile];
+	const uint32_t len = range.y - range.x;
+	if (len == 0u) return;
+	const uint32_t* plist = point_list + range.x;
+
+	uint32_t pos[GSR_PIX_PER_LANE];   // the pixel's median position; GSR_MEDIAN_NONE: none, outside the image, or already summed
+	float g[GSR_PIX_PER_LANE];
+#pragma unroll
+	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+		const int py = py0 + 4 * k;
+		const bool inside = px < W && py < H;
+		const size_t pix_id = inside ? (size_t)W * py + px : 0;
+		pos[k] = inside ? state[pix_id] : GSR_MEDIAN_NONE;
+		g[k] = inside ? dL_dmedian[pix_id] : 0.f;
+	}
+
+	int cnt = 0;   // wave-uniform; at most 256: every round retires at least one of the 256 pixels
+	for (;;) {
+		// the next position: that of the lowest lane's lowest pixel still waiting
+		const uint32_t cur = pos[0] != GSR_MEDIAN_NONE ? pos[0] : pos[1] != GSR_MEDIAN_NONE ? pos[1] : pos[2] != GSR_MEDIAN_NONE ? pos[2] : pos[3];
+		const unsigned long long waiting = __builtin_amdgcn_ballot_w64(cur != GSR_MEDIAN_NONE);
+		if (waiting == 0ull) break;   // wave-uniform
+		const uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)cur, __builtin_ctzll(waiting));
+		// the lane's pixels in the order k = 0..3, then the lanes by a xor butterfly: a fixed order, and every lane ends with the same
+		// bits (an addition commutes bit for bit)
+		float t = 0.f;
+#pragma unroll
+		for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+			const bool mine = pos[k] == q;
+			t += mine ? g[k] : 0.f;
+			pos[k] = mine ? GSR_MEDIAN_NONE : pos[k];
+		}
+#pragma unroll
+		for (int off = 1; off < 64; off <<= 1) t += __shfl_xor(t, off, 64);
+		if (lane == 0) { sq[cnt] = q; stot[cnt] = t; }
+		cnt++;
+	}
+	__builtin_amdgcn_wave_barrier();   // a wave's LDS operations execute in program order; this keeps the compiler from moving them
+
+	for (int e = lane; e < cnt; e += 64) {
+		const uint32_t q = sq[e];
+		if (q >= len) continue;   // the state is the caller's buffer: a plane that is not this view's must not index past the list
+		const uint32_t id = plist[q];
+		const uint2 r = reinterpret_cast<const uint2*>(splat + id)[3];   // rect_min, rect_wh
+		const uint32_t slot = slot_base[id] + ((uint32_t)ty - (r.x >> 16)) * (r.y & 0xffffu) + ((uint32_t)tx - (r.x & 0xffffu));
+		float* w = reinterpret_cast<float*>(slots + slot) + 9;   // pad0, the blend's own dL/dv
+		*w = *w + stot[e];
+	}
+}
+
+void gsr_launch_median_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out_depth,
+                               int32_t* out_median, int32_t* out_dominant, float* out_weight, uint32_t* state, bool cull, bool full_walk,
+                               hipStream_t s)
+{
+	const int gx = gsr_grid_x(W), ntiles = gx * gsr_grid_y(H);
+	const dim3 grid((ntiles + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG), block(64 * GSR_WAVES_PER_WG);
+	if (full_walk)
+		gsr_launch(gsr_median_forward_kernel<false>, grid, block, 0, s, nullptr, nullptr, W, H, gx, ntiles, img.ranges, point_list, splat,
+		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
+	else
+		gsr_launch(gsr_median_forward_kernel<true>, grid, block, 0, s, nullptr, nullptr, W, H, gx, ntiles, img.ranges, point_list, splat,
+		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
+}
+
+void gsr_launch_median_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
+                                const uint32_t* state, const float* dL_dmedian, GsrGradSlot* slots, hipStream_t s)
+{
+	const int gx = gsr_grid_x(W), ntiles = gx * gsr_grid_y(H);
+	gsr_launch(gsr_median_backward_kernel, dim3((ntiles + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG), dim3(64 * GSR_WAVES_PER_WG), 0, s, nullptr, nullptr, W, H, gx, ntiles,
+	           img.ranges, point_list, splat, slot_base, state, dL_dmedian, slots);
+}

@@ -81,6 +81,7 @@ class AuxLayout(ctypes.Structure):
 # bits of the C ABI's `debug` mask (include/gsr.h GSR_DEBUG_*).  The reference's bool `debug` is DEBUG_SYNC; tests pass the
 # diagnostic bits as an int in the same argument, per call -- nothing is read from the environment.
 DEBUG_SYNC, DEBUG_NO_CULL, DEBUG_SERIAL, DEBUG_NO_SPLIT, DEBUG_TILE_SORT, DEBUG_RADIX_DEPTH, DEBUG_NO_TRIM = 1, 2, 4, 8, 16, 32, 64
+DEBUG_MEDIAN_FULL_WALK = 128   # include/gsr_median.h: median_forward() without its early exit
 
 
 def _dbg(debug):
@@ -202,6 +203,15 @@ def lib():
         L.gsr_distortion_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 5 + [_vp, _i]
         L.gsr_distortion_backward.restype = _i
         L.gsr_distortion_backward.argtypes = [pb, _vp, _vp]
+    # include/gsr_median.h: the median-depth map, the per-pixel index maps and the median depth's gradient (the same holds for an
+    # older library)
+    if hasattr(L, "gsr_median_forward"):
+        L.gsr_median_state_bytes.restype = _sz
+        L.gsr_median_state_bytes.argtypes = [_i, _i]
+        L.gsr_median_forward.restype = _i
+        L.gsr_median_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 9 + [_i]
+        L.gsr_median_backward.restype = _i
+        L.gsr_median_backward.argtypes = [pb, _vp, _vp]
     _lib = L
     return L
 
@@ -439,7 +449,7 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
 
 
 def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None,
-                 features=None, distortion=None):
+                 features=None, distortion=None, median=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
@@ -454,9 +464,13 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     work unchanged.
     distortion: DistortionBackward (include/gsr_distortion.h) when the distortion map took part in the loss: its pass runs at the same
     place, behind the features', and adds into the slots' words 0..5 and 9 -- x (the AuxArgs) is then required, so that the aux
-    kernels write and chain word 9."""
+    kernels write and chain word 9.
+    median: MedianBackward (include/gsr_median.h) when the median-depth map took part in the loss: its pass runs at the same place and
+    adds into the slots' word 9 alone; x is required as for distortion."""
     if distortion is not None and x is None:
         raise RuntimeError("run_backward: the distortion map's backward needs the depth-and-alpha kernels (x is None)")
+    if median is not None and x is None:
+        raise RuntimeError("run_backward: the median-depth map's backward needs the depth-and-alpha kernels (x is None)")
     if cam is not None and parts is not None:
         raise NotImplementedError("camera gradients need the whole scene in one per-Gaussian pass: not with `parts`")
     if absgrad is not None and parts is not None:
@@ -471,6 +485,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
         features.run(a, device, into_slots=True)
     if distortion is not None:
         distortion.run(a, device)
+    if median is not None:
+        median.run(a, device)
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
@@ -485,7 +501,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
 
 
 def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None,
-                    features=None, distortion=None):
+                    features=None, distortion=None, median=None):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -546,7 +562,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
                 run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
-                             absgrad=ab, features=features, distortion=distortion)
+                             absgrad=ab, features=features, distortion=distortion, median=median)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
@@ -589,17 +605,19 @@ def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, r
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
-                                             camera_grads=False, absgrad=None, features=None, distortion=None):
+                                             camera_grads=False, absgrad=None, features=None, distortion=None, median=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
     precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad /
     features: as there.  distortion: DistortionBackward(state, dL_ddistortion) when the map of distortion_forward() took part in
-    the loss; its share is in the eight results, dL/dv chained to dL_dmeans3D (include/gsr_distortion.h)."""
+    the loss; its share is in the eight results, dL/dv chained to dL_dmeans3D (include/gsr_distortion.h).  median:
+    MedianBackward(state, dL_dmedian_depth) when the median-depth map of median_forward() did; its dL/dv is chained the same way
+    (include/gsr_median.h)."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features,
-                           distortion)
+                           distortion, median)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------
@@ -784,6 +802,96 @@ class DistortionBackward:
         if int(a.P) == 0:
             return
         _check(lib().gsr_distortion_backward(ctypes.byref(a), _ptr(self.state), _ptr(self.dL_ddist)))
+
+
+# ---- the median-depth map and the per-pixel index maps (include/gsr_median.h) -------------------------------------------------------
+def median_flag(median_depth, depth_alpha=None):
+    """Checks the `median_depth` keyword: a bool (anything else raises TypeError), and True only together with a depth_alpha mode
+    (ValueError: the depth value v_i lives only in the records of a depth-and-alpha forward) -> the bool.  No library is touched."""
+    if not isinstance(median_depth, bool):
+        raise TypeError(f"median_depth must be a bool, got {type(median_depth).__name__}")
+    if median_depth and depth_alpha is None:
+        raise ValueError('median_depth=True needs depth_alpha="depth" or "invdepth": the depth values v_i of the map live only in the '
+                         "records of a depth-and-alpha forward")
+    return median_depth
+
+
+def index_map_tensors(index_maps, W, H, device=None):
+    """Checks the `index_maps` keyword: None, or a 3-tuple (median_index int32, dominant_index int32, dominant_weight float32) of
+    contiguous (H, W) or (1, H, W) HIP tensors on one device (`device` when given), any of them None but not all -> their device, or
+    None for index_maps=None.  Anything but None or a 3-tuple raises TypeError, wrong tensors ValueError.  No kernel and no library is
+    touched."""
+    if index_maps is None:
+        return None
+    if not isinstance(index_maps, (tuple, list)) or len(index_maps) != 3:
+        raise TypeError("index_maps must be a 3-tuple (median_index, dominant_index, dominant_weight), "
+                        f"got {type(index_maps).__name__}" + (f" of {len(index_maps)}" if isinstance(index_maps, (tuple, list)) else ""))
+    if all(t is None for t in index_maps):
+        raise ValueError("index_maps needs at least one tensor")
+    W, H = int(W), int(H)
+    for name, t, dt in zip(("median_index", "dominant_index", "dominant_weight"), index_maps, (torch.int32, torch.int32, torch.float32)):
+        if t is None:
+            continue
+        tn = str(dt).replace("torch.", "")
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a {tn} tensor or None, got {type(t).__name__}")
+        if t.dtype != dt:
+            raise ValueError(f"{name} must be {tn} (got {t.dtype})")
+        if tuple(t.shape) not in ((H, W), (1, H, W)) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {tn} tensor of shape ({H}, {W}) or (1, {H}, {W}) (got shape {tuple(t.shape)})")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a HIP (cuda) tensor (got {t.device}); the HIP rasterizer has no CPU path")
+        device = t.device if device is None else device
+        if t.device != device:
+            raise ValueError(f"{name} must be on {device} (got {t.device})")
+    return device
+
+
+def median_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, P, W, H, index_maps=None, depth=True, debug=0):
+    """-> (median_depth (1, H, W), state (H, W) int32), or (None, None) with depth=False: the median-depth map of the view whose
+    forward left the three state buffers -- v of the last blended Gaussian in front of which the transmittance is above 0.5, the
+    record's bits (all zeros after a forward without a depth_alpha mode) -- and the median's position in its tile's list per pixel
+    (-1: nothing blended), which MedianBackward reads.  index_maps: None, or (median_index, dominant_index, dominant_weight) as
+    index_map_tensors() checks them, overwritten in place by the same launch: the Gaussian id of the median, the id of the blended
+    Gaussian with the largest weight alpha T (the first on a tie), -1 where nothing blends, and that weight.  debug:
+    DEBUG_MEDIAN_FULL_WALK switches the early exit off.  Nothing of the state buffers is written."""
+    P, R, W, H = int(P), int(num_rendered), int(W), int(H)
+    dev = imgBuffer.device
+    if not imgBuffer.is_cuda:
+        raise RuntimeError(f"imgBuffer must be a HIP (cuda) tensor (got {dev}); the HIP rasterizer has no CPU path")
+    index_map_tensors(index_maps, W, H, dev)
+    maps = (None, None, None) if index_maps is None else tuple(index_maps)
+    if not depth and index_maps is None:
+        raise ValueError("median_forward: nothing is asked for (depth=False and index_maps=None)")
+    with torch.cuda.device(dev):
+        out = torch.empty((1, H, W), dtype=torch.float32, device=dev) if depth else None
+        state = torch.empty((H, W), dtype=torch.int32, device=dev) if depth else None
+        if P > 0:
+            _check(lib().gsr_median_forward(P, R, W, H, _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imgBuffer), _ptr(out), _ptr(maps[0]),
+                                            _ptr(maps[1]), _ptr(maps[2]), _ptr(state), _stream(dev), _dbg(debug)))
+        else:   # no Gaussian: nothing is launched
+            for t, fill in ((out, 0), (state, -1), (maps[0], -1), (maps[1], -1), (maps[2], 0)):
+                if t is not None:
+                    t.fill_(fill)
+    return out, state
+
+
+class MedianBackward:
+    """The median-depth map's part of one backward: the state median_forward() returned and dL_dmedian_depth (1, H, W) or (H, W).
+    run() adds dL/dv into word 9 of the gradient slots between the aux blend and the per-Gaussian pass."""
+
+    def __init__(self, state, dL_dmedian):
+        self.state = state
+        self.dL_dmedian = _dev_f32(dL_dmedian, state.device, "dL_dmedian_depth")
+        if tuple(self.dL_dmedian.shape[-2:]) != tuple(state.shape[-2:]) or self.dL_dmedian.numel() != state.numel():
+            raise RuntimeError(f"dL_dmedian_depth must have shape (1, {state.size(-2)}, {state.size(-1)}), got {tuple(self.dL_dmedian.shape)}")
+
+    def run(self, a, device):
+        if (int(a.height), int(a.width)) != tuple(self.state.shape[-2:]):
+            raise RuntimeError(f"the median state is of a {tuple(self.state.shape[-2:])} image, the backward of {(a.height, a.width)}")
+        if int(a.P) == 0:
+            return
+        _check(lib().gsr_median_backward(ctypes.byref(a), _ptr(self.state), _ptr(self.dL_dmedian)))
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------

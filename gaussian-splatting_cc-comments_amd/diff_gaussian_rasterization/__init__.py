@@ -22,18 +22,24 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
-                        camera_grads=False, absgrad=None, features=None):
+                        camera_grads=False, absgrad=None, features=None, index_maps=None):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
-    statistics, the camera gradients, the absolute gradients and the feature channels, see GaussianRasterizer)"""
+    statistics, the camera gradients, the absolute gradients, the feature channels and the per-pixel index maps, see
+    GaussianRasterizer)"""
+    if index_maps is not None:
+        _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), index_maps=index_maps)
 
 
-def _apply(features, *inputs, distortion=False):
+def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=None):
     """features=None: the Function of every release so far, on its own inputs; a tensor: the Function that takes it in front of them
     and returns the feature map behind the other outputs.  distortion=True: the Function that returns the distortion map behind
-    depth and alpha, with `features` (a tensor or None) in front of the inputs."""
+    depth and alpha, with `features` (a tensor or None) in front of the inputs.  median_depth=True or index_maps: the Function that
+    takes all four in front of the inputs."""
+    if median_depth or index_maps is not None:
+        return _RasterizeGaussiansMedian.apply(features, distortion, median_depth, index_maps, *inputs)
     if distortion:
         return _RasterizeGaussiansDistortion.apply(features, *inputs)
     if features is None:
@@ -56,14 +62,19 @@ def camera_grad_results(needs, grads, inputs):
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
-                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None, distortion=False):
+                                    contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None, distortion=False,
+                                    median_depth=False, index_maps=None):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, distortion (1,H,W)]
-    [, feature_map])"""
+    [, median_depth (1,H,W)][, feature_map])"""
     _C.aux_mode(depth_alpha)
     distortion = _C.distortion_flag(distortion, depth_alpha)
+    median_depth = _C.median_flag(median_depth, depth_alpha)
+    if index_maps is not None:
+        _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), distortion=distortion)
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), distortion=distortion,
+                  median_depth=median_depth, index_maps=index_maps)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -83,13 +94,22 @@ class _RasterizeGaussians(torch.autograd.Function):
     and runs this forward and backward with it; through apply() of this class nothing of them is reached.
 
     Distortion map (include/gsr_distortion.h): _RasterizeGaussiansDistortion below runs this forward with _distortion=True, which
-    returns the map behind depth and alpha and saves its per-pixel state behind the aux buffer; the same holds for it."""
+    returns the map behind depth and alpha and saves its per-pixel state behind the aux buffer; the same holds for it.
+
+    Median depth and index maps (include/gsr_median.h): _RasterizeGaussiansMedian below runs this forward with _median and / or
+    _index_maps: one launch after the render writes the caller's index tensors in place and, with _median=True, returns the
+    median-depth map behind the distortion map's place and saves its state behind the distortion state; the same holds for it."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None, absgrad=None, *camera, _features=None, _distortion=False):
+                contrib_pixel_weight=None, absgrad=None, *camera, _features=None, _distortion=False, _median=False,
+                _index_maps=None, _lead=None):
         _C.distortion_flag(_distortion, depth_alpha)   # refused before anything runs
+        _C.median_flag(_median, depth_alpha)           # the same
+        if _index_maps is not None:   # the same
+            _C.index_map_tensors(_index_maps, raster_settings.image_width, raster_settings.image_height,
+                                 means3D.device if means3D.is_cuda else None)
         if _features is not None:       # the same
             _C.feature_tensor(_features, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
         if contrib_stats is not None:   # the same
@@ -155,37 +175,49 @@ class _RasterizeGaussians(torch.autograd.Function):
                                           raster_settings.image_width, raster_settings.image_height, raster_settings.debug)
             dmap, dstate = (d,), (st,)
 
+        mmap = mstate = ()
+        if _median or _index_maps is not None:
+            # the median-depth map and / or the caller's index maps, from the same state: one launch for both, gradients enabled or not
+            md, mst = _C.median_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
+                                        raster_settings.image_width, raster_settings.image_height, _index_maps, _median,
+                                        raster_settings.debug)
+            if _median:
+                mmap, mstate = (md,), (mst,)
+
         ctx.raster_settings = raster_settings
         ctx.densify_stats = densify_stats
         ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
         ctx.distortion = _distortion           # then input 0 is `features` too, a tensor or None
+        ctx.median = _median
+        # how many inputs of the applied Function sit in front of this class's own
+        ctx.lead = _lead if _lead is not None else (1 if (_features is not None or _distortion) else 0)
         ctx.num_rendered = num_rendered
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
         ctx.camera = len(camera) == 3
         ctx.absgrad = absgrad
-        # after the reference's ten: the aux state of the maps, the distortion map's per-pixel state, and the opacity input that the
-        # anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
+        # after the reference's ten: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the
+        # opacity input that the anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:], *dstate,
+                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:], *dstate, *mstate,
                               *((opacities,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
         ctx.set_materialize_grads(False)
-        return (color, radii, *maps[:2], *dmap, *fmap)
+        return (color, radii, *maps[:2], *dmap, *mmap, *fmap)
 
     @staticmethod
     def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
         return _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, None)[1]
 
     @staticmethod
-    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None):
+    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None, grad_median=None):
         """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         num_rendered = ctx.num_rendered
         raster_settings = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, *extra) = ctx.saved_tensors
-        off = 1 if (ctx.features or ctx.distortion) else 0
+        off = ctx.lead
         n_in = 15 + (3 if ctx.camera else 0)
         fb = None
         if ctx.features:
@@ -205,6 +237,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             kw_dist = {"distortion": _C.DistortionBackward(extra[1], grad_distortion)}
         else:
             kw_dist = {}
+        if ctx.median and grad_median is not None:   # the same for the median depth; its state sits behind the distortion state
+            kw_dist["median"] = _C.MedianBackward(extra[2 if ctx.distortion else 1], grad_median)
         kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
         cam_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera else ()
         if any(cam_needs):
@@ -321,6 +355,30 @@ class _RasterizeGaussiansDistortion(torch.autograd.Function):
         return (grad_features, *rest)
 
 
+class _RasterizeGaussiansMedian(torch.autograd.Function):
+    """_RasterizeGaussians with the median-depth map and / or the per-pixel index maps (include/gsr_median.h) ->
+    (color, radii[, depth, alpha[, distortion][, median_depth (1, H, W)]][, feature_map]).  In front of the inputs: `features` (P, K)
+    or None, the distortion and median_depth flags, and index_maps = None or (median_index, dominant_index, dominant_weight), written
+    in place by the forward.  median_depth is v of the last blended Gaussian with T > 0.5, differentiable in v only: its gradient is
+    added into the aux backward's slots and chained to means3D along the view z axis.  The other outputs have the bits of
+    _RasterizeGaussians."""
+
+    @staticmethod
+    def forward(ctx, features, distortion, median_depth, index_maps, *inputs):
+        return _RasterizeGaussians.forward(ctx, *inputs, _features=features, _distortion=distortion, _median=median_depth,
+                                           _index_maps=index_maps, _lead=4)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, _, *grads):
+        g = list(grads)
+        grad_depth, grad_alpha = (g.pop(0), g.pop(0)) if ctx.depth_alpha is not None else (None, None)
+        grad_distortion = g.pop(0) if ctx.distortion else None
+        grad_median = g.pop(0) if ctx.median else None
+        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, g[0] if g else None,
+                                                                grad_distortion, grad_median)
+        return (grad_features, None, None, None, *rest)
+
+
 class GaussianRasterizationSettings(NamedTuple):
     """reference __init__.py:168-180"""
     image_height: int
@@ -395,14 +453,39 @@ class GaussianRasterizer(nn.Module):
     means2D.grad and densify_stats see the total gradient; absgrad stays the colour's moduli.  When the map's gradient reaches the
     backward the depth-and-alpha backward kernels run, with or without dL/ddepth and dL/dalpha; when it does not, nothing of this
     runs in the backward.  A bool, anything else raises TypeError; True without depth_alpha raises ValueError.  Out of scope
-    (NotImplementedError): view_parallel.rasterize_view_parallel and ViewsInFlight."""
+    (NotImplementedError): view_parallel.rasterize_view_parallel and ViewsInFlight.
+
+    median_depth (extension, default False; needs depth_alpha): forward() then returns the median-depth map behind alpha (behind
+    distortion when that is present, in front of feature_map, which stays last): (color, radii, depth, alpha[, distortion],
+    median_depth[, feature_map]) -- median_depth (1, H, W) = v of the LAST blended Gaussian in front of which the transmittance is
+    above 0.5 (2DGS's `if (T > 0.5) median = this`; the last blended Gaussian where T never falls to 0.5), the depth that TSDF fusion
+    takes instead of D / A, which floats between surfaces at silhouettes; 0 where nothing blends (include/gsr_median.h).  It is
+    differentiable in v only -- dL/dv_i = the sum of the map's gradient over the pixels whose median is i, chained to means3D along
+    the view z axis (and to the camera tensors with camera_grads); nothing goes through alpha or T, as in 2DGS and gsplat, so
+    means2D.grad, densify_stats and absgrad do not see it.  When the map's gradient reaches the backward the depth-and-alpha backward
+    kernels run, with or without dL/ddepth and dL/dalpha; when it does not, nothing of this runs in the backward.  A bool, anything
+    else raises TypeError; True without depth_alpha raises ValueError.  Out of scope (NotImplementedError): the view-parallel paths.
+
+    index_maps (extension, optional; with or without depth_alpha): (median_index, dominant_index, dominant_weight) -- contiguous
+    int32, int32 and float32 tensors (H, W) or (1, H, W) on the render's device, any of them None -- that forward() overwrites in
+    place right after the render, with or without gradients enabled (a no_grad picking pass works): the Gaussian id of the pixel's
+    median, the id of the blended Gaussian with the largest weight alpha T (the first in list order on a tie), both -1 where nothing
+    blends, and that weight with the forward's bits (0 there).  The per-pixel answer to the question contrib_stats answers per
+    Gaussian: picking, lifting 2-D masks to Gaussians, keyframe bookkeeping.  The returned tuple is unchanged; no gradients.  Together
+    with median_depth one launch serves both.  Anything but a 3-tuple raises TypeError, wrong tensors ValueError, before anything
+    runs.  Out of scope (NotImplementedError): the view-parallel paths."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
-                 contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False):
+                 contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
         self.distortion = _C.distortion_flag(distortion, depth_alpha)   # TypeError for anything but a bool, ValueError without a mode
+        self.median_depth = _C.median_flag(median_depth, depth_alpha)   # the same
+        # TypeError for anything but a 3-tuple, ValueError for wrong tensors
+        if index_maps is not None:
+            _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
+        self.index_maps = index_maps
         self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
         self.camera_grads = _C.camera_flag(camera_grads)   # the same
         self.raster_settings = raster_settings
@@ -447,7 +530,7 @@ class GaussianRasterizer(nn.Module):
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
                                                    self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
-                                                   self.absgrad, features, self.distortion)
+                                                   self.absgrad, features, self.distortion, self.median_depth, self.index_maps)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
-                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad, features)
+                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad, features, self.index_maps)

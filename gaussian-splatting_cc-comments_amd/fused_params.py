@@ -83,8 +83,12 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                 depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, absgrad=None, *camera,
-                _features=None, _distortion=False):
+                _features=None, _distortion=False, _median=False, _index_maps=None, _lead=None):
         _C.distortion_flag(_distortion, depth_alpha)   # refused before anything runs
+        _C.median_flag(_median, depth_alpha)           # the same
+        if _index_maps is not None:   # the same
+            _C.index_map_tensors(_index_maps, raster_settings.image_width, raster_settings.image_height,
+                                 xyz.device if xyz.is_cuda else None)
         if _features is not None:       # the same
             _C.feature_tensor(_features, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
         if contrib_stats is not None:   # the same
@@ -107,30 +111,40 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             d, dst = _C.distortion_forward(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width,
                                            raster_settings.image_height, raster_settings.debug)
             dmap, dstate = (d,), (dst,)
+        mmap = mstate = ()
+        if _median or _index_maps is not None:   # the median-depth map and / or the index maps of GaussianRasterizer: one launch
+            md, mst = _C.median_forward(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width,
+                                        raster_settings.image_height, _index_maps, _median, raster_settings.debug)
+            if _median:
+                mmap, mstate = (md,), (mst,)
         ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
         ctx.distortion = _distortion           # then input 0 is `features` too, a tensor or None
+        ctx.median = _median
+        # how many inputs of the applied Function sit in front of this class's own
+        ctx.lead = _lead if _lead is not None else (1 if (_features is not None or _distortion) else 0)
         ctx.antialiasing = antialiasing
         ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
-        # after the state: the aux state of the maps, the distortion map's per-pixel state, and the opacity logits that the anti-aliased
-        # backward reads (the records hold sigmoid(logit) * rho), each saved on its path only
+        # after the state: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the opacity logits
+        # that the anti-aliased backward reads (the records hold sigmoid(logit) * rho), each saved on its path only
         ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
-                              *(() if _features is None else (_features,)), *maps[2:], *dstate, *((opacity,) if antialiasing else ()))
+                              *(() if _features is None else (_features,)), *maps[2:], *dstate, *mstate,
+                              *((opacity,) if antialiasing else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)   # no zero tensor for the radii output on the way back
-        return (color, radii, *maps[:2], *dmap, *fmap)
+        return (color, radii, *maps[:2], *dmap, *mmap, *fmap)
 
     @staticmethod
     def backward(ctx, grad_color, _, grad_depth=None, grad_alpha=None):
         return _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha, None)[1]
 
     @staticmethod
-    def backward_with(ctx, grad_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None):
+    def backward_with(ctx, grad_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None, grad_median=None):
         """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
         st, R, M = ctx.raster_settings, ctx.num_rendered, ctx.M
         xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img, *extra = ctx.saved_tensors
         dev = xyz.device
-        off = 1 if (ctx.features or ctx.distortion) else 0
+        off = ctx.lead
         fb = None
         if ctx.features:
             features, extra = extra[0], extra[1:]
@@ -159,18 +173,21 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                 _C.set_backward_outputs(a, dL_dmean2D=d_means2D, dL_dmean3D=d_xyz, dL_dsh=d_dc, dL_dsh_rest=d_rest,
                                         dL_dopacity=d_opacity, dL_dscale=d_scaling, dL_drot=d_rotation)
                 _C.set_backward_stats(a, ctx.stats, P, dev)
-                x = db = None
+                x = db = mb = None
+                if ctx.median and grad_median is not None:   # the same for the median depth; its state sits behind the distortion state
+                    mb = _C.MedianBackward(extra[2 if ctx.distortion else 1], grad_median)
                 if ctx.distortion and grad_distortion is not None:   # (no gradient reached the map: nothing of it runs)
                     db = _C.DistortionBackward(extra[1], grad_distortion)
-                if grad_depth is not None or grad_alpha is not None or db is not None:
-                    # (the distortion map's gradient alone still takes the aux kernels: they write the slots' dL/dv word and chain it)
+                if grad_depth is not None or grad_alpha is not None or db is not None or mb is not None:
+                    # (the distortion map's or the median depth's gradient alone still takes the aux kernels: they write the slots' dL/dv
+                    # word and chain it)
                     hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
                     x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
                 if any(cam_needs):
                     cam, outs = _C.camera_backward_args(P, dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
                                 absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb,
-                                distortion=db)
+                                distortion=db, median=mb)
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
@@ -213,9 +230,29 @@ class _RasterizeLeafGaussiansDistortion(torch.autograd.Function):
         return (grad_features, *rest)
 
 
+class _RasterizeLeafGaussiansMedian(torch.autograd.Function):
+    """_RasterizeLeafGaussians with the median-depth map and / or the per-pixel index maps; `features` or None, the distortion and
+    median_depth flags and index_maps in front of its inputs: the counterpart of diff_gaussian_rasterization._RasterizeGaussiansMedian."""
+
+    @staticmethod
+    def forward(ctx, features, distortion, median_depth, index_maps, *inputs):
+        return _RasterizeLeafGaussians.forward(ctx, *inputs, _features=features, _distortion=distortion, _median=median_depth,
+                                               _index_maps=index_maps, _lead=4)
+
+    @staticmethod
+    def backward(ctx, grad_color, _, *grads):
+        g = list(grads)
+        grad_depth, grad_alpha = (g.pop(0), g.pop(0)) if ctx.depth_alpha is not None else (None, None)
+        grad_distortion = g.pop(0) if ctx.distortion else None
+        grad_median = g.pop(0) if ctx.median else None
+        grad_features, rest = _RasterizeLeafGaussians.backward_with(ctx, grad_color, grad_depth, grad_alpha, g[0] if g else None,
+                                                                    grad_distortion, grad_median)
+        return (grad_features, None, None, None, *rest)
+
+
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                              depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
-                             absgrad=None, features=None, distortion=False):
+                             absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -228,14 +265,22 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     features: (P, K) float32 feature channels; the tuple then ends with feature_map (K, H, W), as GaussianRasterizer's (features=):
     differentiable w.r.t. features and, through the colour backward's slots, w.r.t. the leaves.
     distortion: True (with depth_alpha) puts the depth-distortion map (1, H, W) behind depth and alpha, as GaussianRasterizer's
-    (distortion=True): differentiable w.r.t. the leaves, xyz's depth included."""
+    (distortion=True): differentiable w.r.t. the leaves, xyz's depth included.
+    median_depth: True (with depth_alpha) puts the median-depth map (1, H, W) behind alpha (and distortion), in front of the feature
+    map, as GaussianRasterizer's (median_depth=True): differentiable w.r.t. xyz along the view z axis.
+    index_maps: (median_index, dominant_index, dominant_weight), overwritten in place by the forward, as GaussianRasterizer's."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
     distortion = _C.distortion_flag(distortion, depth_alpha)
+    median_depth = _C.median_flag(median_depth, depth_alpha)
+    if index_maps is not None:
+        _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     inputs = (xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats, depth_alpha,
               _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
     if features is not None:
         _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
+    if median_depth or index_maps is not None:
+        return _RasterizeLeafGaussiansMedian.apply(features, distortion, median_depth, index_maps, *inputs)
     if distortion:
         return _RasterizeLeafGaussiansDistortion.apply(features, *inputs)
     if features is None:

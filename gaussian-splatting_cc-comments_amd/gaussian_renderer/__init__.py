@@ -46,26 +46,29 @@ def _python_sh_colors(camera, pc):
     return torch.clamp_min(eval_sh(pc.active_sh_degree, per_channel, view_dir) + 0.5, 0.0)
 
 
-def _result(image, screenspace_points, radii, aux=None, feature_map=None, distortion=None):
+def _result(image, screenspace_points, radii, aux=None, feature_map=None, distortion=None, median_depth=None):
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
     if aux is not None:
         out["depth"], out["alpha"] = aux
     if distortion is not None:
         out["distortion"] = distortion
+    if median_depth is not None:
+        out["median_depth"] = median_depth
     if feature_map is not None:
         out["features"] = feature_map
     return out
 
 
-def _unpack(out, depth_alpha, features, distortion=False):
-    """(color, radii[, depth, alpha[, distortion]][, feature_map]) -> the arguments of _result() behind the screen-space points"""
+def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
+    """(color, radii[, depth, alpha[, distortion][, median_depth]][, feature_map]) -> the arguments of _result() behind the
+    screen-space points"""
     return (out[1], (out[2:4] if depth_alpha is not None else None), (out[-1] if features is not None else None),
-            (out[4] if distortion else None))
+            (out[4] if distortion else None), (out[5 if distortion else 4] if median_depth else None))
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
-           absgrad=None, features=None, distortion=False):
+           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -81,7 +84,11 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     with the colour pass's own weights and differentiable -- see GaussianRasterizer; on both paths.
     distortion (extension): True (with depth_alpha) adds "distortion" (1, H, W) to the dict, the depth-distortion map
     sum_{j<i} w_i w_j (v_i - v_j)^2 of the same weights and the depth map's values, differentiable -- see GaussianRasterizer; on
-    both paths."""
+    both paths.
+    median_depth (extension): True (with depth_alpha) adds "median_depth" (1, H, W) to the dict, the depth value of the last blended
+    Gaussian with T > 0.5, differentiable in that value -- see GaussianRasterizer; on both paths.
+    index_maps (extension): (median_index, dominant_index, dominant_weight) tensors that the render overwrites in place -- see
+    GaussianRasterizer; the dict is unchanged; on both paths."""
     if camera_grads is None:
         camera_grads = getattr(pipe, "camera_grads", False)
     if antialiasing is None:
@@ -103,6 +110,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     feat = {} if features is None else dict(features=features)   # ... and the feature channels, a keyword of the call itself
     if distortion is not False:   # ... and the distortion map (a non-bool reaches the check that refuses it)
         extras["distortion"] = distortion
+    if median_depth is not False:   # ... the median-depth map, the same way
+        extras["median_depth"] = median_depth
+    if index_maps is not None:      # ... and the caller's index maps
+        extras["index_maps"] = index_maps
 
     python_cov = bool(pipe.compute_cov3D_python)
     python_sh = bool(pipe.convert_SHs_python)
@@ -111,7 +122,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         out = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                        pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha,
                                        antialiasing=antialiasing, **feat, **extras)
-        return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion))
+        return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth))
 
     inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
                   shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None)
@@ -128,4 +139,4 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
     out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha,
                              antialiasing=antialiasing, **extras)(**inputs, **feat)
-    return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion))
+    return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth))
