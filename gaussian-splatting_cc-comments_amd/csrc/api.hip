@@ -16,6 +16,7 @@
 #include "../../include/gsr_features.h"
 #include "../../include/gsr_distortion.h"
 #include "../../include/gsr_median.h"
+#include "../../include/gsr_normals.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1382,6 +1383,78 @@ extern "C" int gsr_median_backward(const gsr_backward_args* args, const void* st
 		                           (GsrGradSlot*)a.scratch, s);
 	}
 	return gsr_stage_done(s, a.debug, "median_backward");
+}
+
+// ---- per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h) ----
+static int gsr_gaussian_normals_check(const char* who, int P, const void* scales, const void* rotations, const void* means3D,
+                                      const void* viewmatrix, int space, const void* in, const void* out)
+{
+	if (P < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative P (%d)", who, P);
+	if (space != GSR_NORMALS_VIEW && space != GSR_NORMALS_WORLD)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: space must be GSR_NORMALS_VIEW or GSR_NORMALS_WORLD (got %d)", who, space);
+	if (P == 0) return GSR_OK;
+	if (!scales || !rotations || !means3D || !viewmatrix || !in || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL pointer", who);
+	if (!aligned16(rotations)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: rotations must be 16-byte aligned", who);
+	return GSR_OK;
+}
+
+extern "C" int gsr_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix,
+                                    int space, float* out, void* stream)
+{
+	g_err[0] = 0;
+	const int rc = gsr_gaussian_normals_check("gsr_gaussian_normals", P, scales, rotations, means3D, viewmatrix, space, scales, out);
+	if (rc != GSR_OK || P == 0) return rc;
+	gsr_launch_gaussian_normals(P, scales, rotations, means3D, viewmatrix, space == GSR_NORMALS_WORLD, out, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "gaussian_normals");
+}
+
+extern "C" int gsr_gaussian_normals_backward(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix,
+                                             int space, const float* dL_dout, float* dL_drotations, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_gaussian_normals_backward";
+	const int rc = gsr_gaussian_normals_check(who, P, scales, rotations, means3D, viewmatrix, space, dL_dout, dL_drotations);
+	if (rc != GSR_OK || P == 0) return rc;
+	if (!aligned16(dL_drotations)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_drotations must be 16-byte aligned", who);
+	gsr_launch_gaussian_normals_backward(P, scales, rotations, means3D, viewmatrix, space == GSR_NORMALS_WORLD, dL_dout, dL_drotations,
+	                                     (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "gaussian_normals_backward");
+}
+
+extern "C" size_t gsr_normals_scratch_bytes(int W, int H)
+{
+	if (W <= 0 || H <= 0) return 0;
+	return gsr_normals_scratch_size(W, H);
+}
+
+extern "C" int gsr_depth_normals(int W, int H, const float* depth, float tanfovx, float tanfovy, float* out, void* stream)
+{
+	g_err[0] = 0;
+	if (W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_normals: bad image size (%d x %d)", W, H);
+	if (!depth || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_normals: NULL pointer");
+	gsr_launch_depth_normals(W, H, depth, tanfovx, tanfovy, out, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "depth_normals");
+}
+
+extern "C" int gsr_depth_normals_backward(int W, int H, const float* depth, float tanfovx, float tanfovy, const float* dL_dout,
+                                          float* dL_ddepth, void* stream)
+{
+	g_err[0] = 0;
+	if (W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_normals_backward: bad image size (%d x %d)", W, H);
+	if (!depth || !dL_dout || !dL_ddepth) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_depth_normals_backward: NULL pointer");
+	gsr_launch_depth_normals_backward(W, H, depth, tanfovx, tanfovy, dL_dout, dL_ddepth, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "depth_normals_backward");
+}
+
+extern "C" int gsr_normal_consistency_loss(int W, int H, const float* normal_map, const float* depth, const float* alpha, float tanfovx,
+                                           float tanfovy, float* vals, float* dL_dnormal_map, float* dL_ddepth, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	if (W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_normal_consistency_loss: bad image size (%d x %d)", W, H);
+	if (!normal_map || !depth || !vals || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_normal_consistency_loss: NULL pointer");
+	gsr_launch_normal_consistency_loss(W, H, normal_map, depth, alpha, tanfovx, tanfovy, vals, dL_dnormal_map, dL_ddepth, scratch,
+	                                   (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "normal_consistency_loss");
 }
 
 extern "C" size_t gsr_loss_scratch_bytes(int C, int H, int W)

@@ -346,6 +346,18 @@ size_t gsr_loss_scratch_layout(int C, int H, int W, size_t* maps_off, size_t* pa
 void gsr_launch_l1_ssim(int C, int H, int W, const float* img, const float* gt, float lambda, float* loss_out, float* dL_dimg,
                         void* scratch, hipStream_t s);
 
+// normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
+void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
+                                 float* out, hipStream_t s);
+void gsr_launch_gaussian_normals_backward(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix,
+                                          int world, const float* dL_dout, float* dL_drot, hipStream_t s);
+size_t gsr_normals_scratch_size(int W, int H);
+void gsr_launch_depth_normals(int W, int H, const float* depth, float tanfovx, float tanfovy, float* out, hipStream_t s);
+void gsr_launch_depth_normals_backward(int W, int H, const float* depth, float tanfovx, float tanfovy, const float* dL_dout, float* dL_ddepth,
+                                       hipStream_t s);
+void gsr_launch_normal_consistency_loss(int W, int H, const float* normal_map, const float* depth, const float* alpha, float tanfovx,
+                                        float tanfovy, float* vals, float* dL_dnormal, float* dL_ddepth, void* scratch, hipStream_t s);
+
 // optimizer.hip
 int gsr_launch_adam(int ngroups, const gsr_adam_group* groups, double beta1, double beta2, double eps, const int* radii, hipStream_t s);
 

@@ -212,6 +212,21 @@ def lib():
         L.gsr_median_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 9 + [_i]
         L.gsr_median_backward.restype = _i
         L.gsr_median_backward.argtypes = [pb, _vp, _vp]
+    # include/gsr_normals.h: per-Gaussian normals, depth normals and the normal-consistency loss (fused_geometry.py; the same holds
+    # for an older library)
+    if hasattr(L, "gsr_gaussian_normals"):
+        L.gsr_gaussian_normals.restype = _i
+        L.gsr_gaussian_normals.argtypes = [_i] + [_vp] * 4 + [_i, _vp, _vp]
+        L.gsr_gaussian_normals_backward.restype = _i
+        L.gsr_gaussian_normals_backward.argtypes = [_i] + [_vp] * 4 + [_i, _vp, _vp, _vp]
+        L.gsr_normals_scratch_bytes.restype = _sz
+        L.gsr_normals_scratch_bytes.argtypes = [_i, _i]
+        L.gsr_depth_normals.restype = _i
+        L.gsr_depth_normals.argtypes = [_i, _i, _vp, _f, _f, _vp, _vp]
+        L.gsr_depth_normals_backward.restype = _i
+        L.gsr_depth_normals_backward.argtypes = [_i, _i, _vp, _f, _f, _vp, _vp, _vp]
+        L.gsr_normal_consistency_loss.restype = _i
+        L.gsr_normal_consistency_loss.argtypes = [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]
     _lib = L
     return L
 
@@ -892,6 +907,17 @@ class MedianBackward:
         if int(a.P) == 0:
             return
         _check(lib().gsr_median_backward(ctypes.byref(a), _ptr(self.state), _ptr(self.dL_dmedian)))
+
+
+# ---- the normal map of render(normals=True) (include/gsr_normals.h, fused_geometry.py) ----------------------------------------------
+NORMAL_SPACES = {"view": 0, "world": 1}   # GSR_NORMALS_VIEW / GSR_NORMALS_WORLD
+
+
+def normals_flag(normals):
+    """The `normals` keyword -> bool; anything but a bool raises TypeError, like `distortion`.  No library is touched."""
+    if not isinstance(normals, bool):
+        raise TypeError(f"normals must be a bool, got {type(normals).__name__}")
+    return normals
 
 
 # ---- the backward in two stages (include/gsr.h gsr_backward_blend / gsr_backward_gaussians) ------------------

@@ -46,7 +46,9 @@ def _python_sh_colors(camera, pc):
     return torch.clamp_min(eval_sh(pc.active_sh_degree, per_channel, view_dir) + 0.5, 0.0)
 
 
-def _result(image, screenspace_points, radii, aux=None, feature_map=None, distortion=None, median_depth=None):
+def _result(image, screenspace_points, radii, aux=None, feature_map=None, distortion=None, median_depth=None, user_channels=None):
+    """user_channels: None, or the number K of the caller's own feature channels in front of the three normal channels of
+    render(normals=True): "features" keeps exactly those K (absent for K = 0), "normal" gets the last three"""
     out = {"render": image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
     if aux is not None:
         out["depth"], out["alpha"] = aux
@@ -54,9 +56,22 @@ def _result(image, screenspace_points, radii, aux=None, feature_map=None, distor
         out["distortion"] = distortion
     if median_depth is not None:
         out["median_depth"] = median_depth
+    if user_channels is not None:
+        feature_map, out["normal"] = (feature_map[:user_channels] if user_channels else None), feature_map[user_channels:]
     if feature_map is not None:
         out["features"] = feature_map
     return out
+
+
+def _gaussian_normals(camera, pc, leaf, camera_grads):
+    """(P, 3) per-Gaussian normals for the feature pass, in view space.  The kernel reads the raw leaves on the leaf path (log-scales
+    choose the same axis, the quaternion is normalised inside).  With camera gradients it returns world-space normals and the rotation
+    into view space is done here in torch, so that world_view_transform receives that gradient."""
+    from fused_geometry import gaussian_normals
+    scales, rotations = (pc._scaling, pc._rotation) if leaf else (pc.get_scaling, pc.get_rotation)
+    if camera_grads:
+        return gaussian_normals(scales, rotations, pc.get_xyz, camera.world_view_transform, "world") @ camera.world_view_transform[:3, :3]
+    return gaussian_normals(scales, rotations, pc.get_xyz, camera.world_view_transform, "view")
 
 
 def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
@@ -68,7 +83,7 @@ def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
-           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None):
+           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -88,7 +103,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     median_depth (extension): True (with depth_alpha) adds "median_depth" (1, H, W) to the dict, the depth value of the last blended
     Gaussian with T > 0.5, differentiable in that value -- see GaussianRasterizer; on both paths.
     index_maps (extension): (median_index, dominant_index, dominant_weight) tensors that the render overwrites in place -- see
-    GaussianRasterizer; the dict is unchanged; on both paths."""
+    GaussianRasterizer; the dict is unchanged; on both paths.
+    normals (extension): True adds "normal" (3, H, W) to the dict, the blend sum_i n_i alpha_i T_i of the per-Gaussian view-space
+    normals of fused_geometry.gaussian_normals(), differentiable (rotations through n_i, everything else through the weights): three
+    more channels of the feature pass behind the caller's `features`, split off again -- "features" keeps exactly the caller's
+    channels; on both paths.  The input of fused_geometry.normal_consistency_loss()."""
+    from diff_gaussian_rasterization import _C
+    _C.normals_flag(normals)   # a switch: anything but a bool is refused
     if camera_grads is None:
         camera_grads = getattr(pipe, "camera_grads", False)
     if antialiasing is None:
@@ -107,6 +128,17 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         extras["camera_grads"] = camera_grads
     if absgrad is not None:
         extras["absgrad"] = absgrad
+    python_cov = bool(pipe.compute_cov3D_python)
+    python_sh = bool(pipe.convert_SHs_python)
+    leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh
+    user_channels = None
+    if normals:   # three more feature channels behind the caller's own
+        n = _gaussian_normals(viewpoint_camera, pc, leaf, camera_grads is True)
+        if features is None:
+            user_channels, features = 0, n
+        else:
+            user_channels = _C.feature_tensor(features, xyz.size(0), xyz.device)
+            features = torch.cat((features, n), dim=1)
     feat = {} if features is None else dict(features=features)   # ... and the feature channels, a keyword of the call itself
     if distortion is not False:   # ... and the distortion map (a non-bool reaches the check that refuses it)
         extras["distortion"] = distortion
@@ -115,14 +147,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     if index_maps is not None:      # ... and the caller's index maps
         extras["index_maps"] = index_maps
 
-    python_cov = bool(pipe.compute_cov3D_python)
-    python_sh = bool(pipe.convert_SHs_python)
-    if getattr(pipe, "fused_activations", False) and override_color is None and not python_cov and not python_sh:
+    if leaf:
         from fused_params import rasterize_leaf_gaussians
         out = rasterize_leaf_gaussians(pc._xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity,
                                        pc._scaling, pc._rotation, settings, densify_stats, depth_alpha=depth_alpha,
                                        antialiasing=antialiasing, **feat, **extras)
-        return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth))
+        return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth),
+                       user_channels=user_channels)
 
     inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
                   shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None)
@@ -139,4 +170,5 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
     out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha,
                              antialiasing=antialiasing, **extras)(**inputs, **feat)
-    return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth))
+    return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth),
+                   user_channels=user_channels)
