@@ -6,12 +6,8 @@
 // Two kernels, no atomics, no workgroup barrier, bitwise reproducible.  None of the default kernels is touched: both passes read the
 // state a forward left, the way contrib.hip, features.hip and distortion.hip do.
 //
-// Decomposition (render_common.h): one wave64 per 16x16 tile, four pixels per lane, 64 instances staged per batch into the wave's LDS
-// slice behind gsr_tile_band_mask (`cull`).
-//
-// Forward: distortion.hip's forward walk (list positions [0, min(range length, tile_max_contrib)), per pixel only those in front of
-// its n_contrib; `power`, alpha, the two thresholds and T's update are render_forward.hip's instruction sequence on the same records),
-// so every decision and every w has the colour pass's bits.  Per hit, with T the value in front of the hit:
+// Forward: the replay walk of gsr_replay.h, front to back, no payload: every decision and every w has the colour pass's bits.  Per
+// hit, with T the value in front of the hit:
 //   if (T > 0.5) med = position;      w = alpha T;      if (w > best) { best = w; best_pos = position; }
 // Only list positions are carried; the Gaussian ids (point_list[range.x + position]) and the median's depth value v (the last word of
 // its splat record, the record's bits) are gathered once per pixel at the end -- two loads per pixel instead of a staged word and a
@@ -41,142 +37,72 @@
 // blend validated; the unchanged aux per-Gaussian backward chains word 9 along the view z axis.  Heavy tiles are one wave like any other.
 //
 // Registers (hipcc 7.x, gfx950, -O3 -ffp-contract=off; `make audit`, .audit/median.s): see DESIGN.md 6k.
-#include "render_common.h"
+#include "gsr_replay.h"
 
 #define GSR_MEDIAN_NONE 0xFFFFFFFFu
 
 template <bool EXIT>
-__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_median_forward_kernel(
+struct GsrMedianPass : GsrReplayPass {
+	float best[GSR_PIX_PER_LANE];      // the largest w so far
+	uint32_t med[GSR_PIX_PER_LANE];    // list position of the last hit with T > 0.5
+	uint32_t bpos[GSR_PIX_PER_LANE];   // list position of the first hit with w = best
+	__device__ __forceinline__ void pixel(const GsrTileWalk&, const GsrInstance& in, int k, float, const GsrPairFwd& p, None&)
+	{
+		med[k] = (p.hit && p.Tfront > 0.5f) ? in.position : med[k];
+		const bool better = p.w > best[k];   // w = 0 without a hit never beats best >= 0
+		best[k] = better ? p.w : best[k];
+		bpos[k] = better ? in.position : bpos[k];
+	}
+	// EXIT: a band stops once each of its pixels has blended its last position or can change no more (the proof is in the header);
+	// band_last = 0 is the test the walk already makes per instance
+	__device__ __forceinline__ bool batch_done(GsrTileWalk& w, uint32_t next) const
+	{
+		if (!EXIT) return true;
+		bool any = false;
+#pragma unroll
+		for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+			if (w.band_last[k] <= next) continue;   // finished, here or by its n_contrib
+			const bool open = next < w.last[k] && (w.T[k] > 0.5f || w.T[k] > best[k]);
+			if (__builtin_amdgcn_ballot_w64(open) == 0ull) w.band_last[k] = 0u;
+			else any = true;
+		}
+		return any;   // wave-uniform
+	}
+};
+
+// each twin is declared for its occupancy: left to itself the allocator takes 82 VGPRs for the full walk, a wave less
+template <bool EXIT>
+__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu(EXIT ? 5 : 6))) gsr_median_forward_kernel(
 	int W, int H, int gx, int ntiles, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
 	const GsrSplat* __restrict__ splat, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,
 	float* __restrict__ out_depth, int32_t* __restrict__ out_median, int32_t* __restrict__ out_dominant, float* __restrict__ out_weight,
 	uint32_t* __restrict__ state, int cull)
 {
-	// the surviving instances of a batch: (x, y, -0.5 conic a, conic b), (-0.5 conic c, opacity, list position, -)
-	__shared__ float4 s_rec[GSR_WAVES_PER_WG][2][64];
-	__shared__ uint32_t s_bands[GSR_WAVES_PER_WG][64];
-	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const int tile = blockIdx.x * GSR_WAVES_PER_WG + wave;
-	if (tile >= ntiles) return;  // wave-uniform; no barriers below
-	float4(*rec)[64] = s_rec[wave];
-	uint32_t* recb = s_bands[wave];
-
-	const int tx = tile % gx, ty = tile / gx;
-	const int px = tx * GSR_TILE_X + (lane & 15);
-	const int py0 = ty * GSR_TILE_Y + (lane >> 4);
-	const float pfx = (float)px;
-	const float x0f = (float)(tx * GSR_TILE_X), y0f = (float)(ty * GSR_TILE_Y);
-
-	const uint2 range = ranges[tile];
-	const int n = (int)min(range.y - range.x, tile_max_contrib[tile]);  // the tail was never blended; 0: the tile's pixels get "none"
-	const uint32_t* plist = point_list + range.x;
-
-	float T[GSR_PIX_PER_LANE], pfy[GSR_PIX_PER_LANE];
-	float best[GSR_PIX_PER_LANE];           // the largest w so far
-	uint32_t med[GSR_PIX_PER_LANE];         // list position of the last hit with T > 0.5
-	uint32_t bpos[GSR_PIX_PER_LANE];        // list position of the first hit with w = best
-	uint32_t last[GSR_PIX_PER_LANE];        // the pixel's n_contrib: it blended positions in front of this one only (0 outside the image)
-	uint32_t band_last[GSR_PIX_PER_LANE];   // wave-uniform: the largest of them in band k; 0 once the band has finished (EXIT)
-#pragma unroll
-	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
-		const int py = py0 + 4 * k;
-		const bool inside = px < W && py < H;
-		const uint32_t pix_id = inside ? (uint32_t)(W * py + px) : 0u;
-		pfy[k] = (float)py;
-		T[k] = 1.0f;
-		best[k] = 0.f;
-		med[k] = GSR_MEDIAN_NONE; bpos[k] = GSR_MEDIAN_NONE;
-		last[k] = inside ? n_contrib[pix_id] : 0u;
-		uint32_t lm = last[k];
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) lm = max(lm, (uint32_t)__shfl_xor((int)lm, off, 64));
-		band_last[k] = __builtin_amdgcn_readfirstlane(lm);
-	}
-
-	// software pipeline: records one batch ahead, ids two batches ahead
-	float4 ra = make_float4(0, 0, 0, 0), rb = ra;
-	if (lane < n) {
-		const uint32_t id = plist[lane];
-		const float4* p = reinterpret_cast<const float4*>(splat + id);
-		ra = p[0]; rb = p[1];
-	}
-	uint32_t id_next = (64 + lane < n) ? plist[64 + lane] : 0u;
-
-	for (int base = 0; base < n; base += 64) {
-		const uint32_t bands = (base + lane < n) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
-		const bool keep = bands != 0u;
-		const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
-		const int cnt = __popcll(mask);
-		if (keep) {
-			const int pos = gsr_mbcnt(mask);
-			rec[0][pos] = make_float4(ra.x, ra.y, -0.5f * ra.z, ra.w);  // conic a, c pre-multiplied by -0.5 (exact)
-			rec[1][pos] = make_float4(-0.5f * rb.x, rb.y, __uint_as_float((uint32_t)(base + lane)), 0.f);
-			recb[pos] = bands;
-		}
-		if (base + 64 + lane < n) {
-			const float4* p = reinterpret_cast<const float4*>(splat + id_next);
-			ra = p[0]; rb = p[1];
-		}
-		id_next = (base + 128 + lane < n) ? plist[base + 128 + lane] : 0u;
-		__builtin_amdgcn_wave_barrier();
-
-		for (int j = 0; j < cnt; j++) {
-			const float4 RA = rec[0][j];   // x, y, -0.5 conic a, conic b
-			const float4 RB = rec[1][j];   // -0.5 conic c, opacity, list position, -
-			const uint32_t position = __builtin_amdgcn_readfirstlane(__float_as_uint(RB.z));   // wave-uniform
-			const uint32_t jbands = __builtin_amdgcn_readfirstlane(recb[j]);                  // wave-uniform
-			const float dx = RA.x - pfx;
-			const float ax2 = __fmul_rn(__fmul_rn(RA.z, dx), dx), bdx = __fmul_rn(RA.w, dx);
-#pragma unroll
-			for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
-				if (!(jbands & (1u << k)) || position >= band_last[k]) continue;  // scalar branch: the band cannot be reached, or it had finished
-				const float dy = RA.y - pfy[k];
-				const float power = gsr_pair_power_halved(ax2, bdx, RB.x, dy);
-				const float alpha = fminf(0.99f, RB.y * __expf(power));
-				const unsigned long long hitm = __builtin_amdgcn_ballot_w64(position < last[k]) & __builtin_amdgcn_ballot_w64(!(power > 0.0f)) &
-				                                __builtin_amdgcn_ballot_w64(!(alpha < 1.0f / 255.0f));
-				if (hitm == 0ull) continue;  // wave-uniform
-				const bool hit = __builtin_amdgcn_inverse_ballot_w64(hitm);
-				const float Tk = T[k];                                                // T in front of this instance
-				const float w = hit ? __fmul_rn(alpha, Tk) : 0.0f;                    // the forward's alpha * T; 0 never beats best >= 0
-				T[k] = hit ? __fmul_rn(Tk, __fsub_rn(1.0f, alpha)) : Tk;              // ... and its T (1 - alpha), rounded as there
-				med[k] = (hit && Tk > 0.5f) ? position : med[k];
-				const bool better = w > best[k];
-				best[k] = better ? w : best[k];
-				bpos[k] = better ? position : bpos[k];
-			}
-		}
-		__builtin_amdgcn_wave_barrier();
-
-		if (EXIT) {
-			// a band stops once each of its pixels has blended its last position or can change no more (the proof is in the header)
-			const uint32_t next = (uint32_t)base + 64u;   // every position below it has been walked
-			bool any = false;
-#pragma unroll
-			for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
-				if (band_last[k] <= next) continue;   // finished, here or by its n_contrib
-				const bool open = next < last[k] && (T[k] > 0.5f || T[k] > best[k]);
-				if (__builtin_amdgcn_ballot_w64(open) == 0ull) band_last[k] = 0u;
-				else any = true;
-			}
-			if (!any) break;   // wave-uniform
-		}
-	}
+	__shared__ GsrBatchLds s_batch[GSR_WAVES_PER_WG];
+	GsrTileWalk w;
+	gsr_walk_tile(w, gx);
+	if (w.tile >= ntiles) return;
+	gsr_walk_list(w, ranges, point_list, tile_max_contrib);   // n = 0: the tile's pixels get "none"
+	GsrMedianPass<EXIT> pass;
+	gsr_walk_pixels<uint32_t>(w, W, H, n_contrib, nullptr, [&](int k, bool, uint32_t) {
+		pass.best[k] = 0.f;
+		pass.med[k] = GSR_MEDIAN_NONE; pass.bpos[k] = GSR_MEDIAN_NONE;
+	});
+	GSR_REPLAY(false, false, w, s_batch[w.wave], splat, (const uint32_t*)nullptr, cull, pass);
 
 #pragma unroll
 	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
-		const int py = py0 + 4 * k;
-		if (px < W && py < H) {
-			const size_t pix_id = (size_t)W * py + px;
-			const bool some = med[k] != GSR_MEDIAN_NONE;   // one hit sets both positions: the first hit has T = 1 and w > 0
-			if (state) state[pix_id] = med[k];
+		if (w.px < W && w.py(k) < H) {
+			const size_t pix_id = (size_t)W * w.py(k) + w.px;
+			const bool some = pass.med[k] != GSR_MEDIAN_NONE;   // one hit sets both positions: the first hit has T = 1 and w > 0
+			if (state) state[pix_id] = pass.med[k];
 			if (out_depth || out_median) {
-				const uint32_t id = some ? plist[med[k]] : 0u;
+				const uint32_t id = some ? w.plist[pass.med[k]] : 0u;
 				if (out_median) out_median[pix_id] = some ? (int32_t)id : -1;
 				if (out_depth) out_depth[pix_id] = some ? reinterpret_cast<const float*>(splat + id)[11] : 0.f;   // the record's v
 			}
-			if (out_dominant) out_dominant[pix_id] = some ? (int32_t)plist[bpos[k]] : -1;
-			if (out_weight) out_weight[pix_id] = best[k];
+			if (out_dominant) out_dominant[pix_id] = some ? (int32_t)w.plist[pass.bpos[k]] : -1;
+			if (out_weight) out_weight[pix_id] = pass.best[k];
 		}
 	}
 }
@@ -242,7 +168,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_median_backward_ker
 		if (q >= len) continue;   // the state is the caller's buffer: a plane that is not this view's must not index past the list
 		const uint32_t id = plist[q];
 		const uint2 r = reinterpret_cast<const uint2*>(splat + id)[3];   // rect_min, rect_wh
-		const uint32_t slot = slot_base[id] + ((uint32_t)ty - (r.x >> 16)) * (r.y & 0xffffu) + ((uint32_t)tx - (r.x & 0xffffu));
+		const uint32_t slot = gsr_slot_index(slot_base[id], r.x, r.y, tx, ty);
 		float* w = reinterpret_cast<float*>(slots + slot) + 9;   // pad0, the blend's own dL/dv
 		*w = *w + stot[e];
 	}
@@ -252,20 +178,19 @@ void gsr_launch_median_forward(int W, int H, GsrImage img, const uint32_t* point
                                int32_t* out_median, int32_t* out_dominant, float* out_weight, uint32_t* state, bool cull, bool full_walk,
                                hipStream_t s)
 {
-	const int gx = gsr_grid_x(W), ntiles = gx * gsr_grid_y(H);
-	const dim3 grid((ntiles + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG), block(64 * GSR_WAVES_PER_WG);
+	const GsrTileGrid t = gsr_tile_grid(W, H);
 	if (full_walk)
-		gsr_launch(gsr_median_forward_kernel<false>, grid, block, 0, s, nullptr, nullptr, W, H, gx, ntiles, img.ranges, point_list, splat,
+		gsr_launch(gsr_median_forward_kernel<false>, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
 		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
 	else
-		gsr_launch(gsr_median_forward_kernel<true>, grid, block, 0, s, nullptr, nullptr, W, H, gx, ntiles, img.ranges, point_list, splat,
+		gsr_launch(gsr_median_forward_kernel<true>, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
 		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
 }
 
 void gsr_launch_median_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
                                 const uint32_t* state, const float* dL_dmedian, GsrGradSlot* slots, hipStream_t s)
 {
-	const int gx = gsr_grid_x(W), ntiles = gx * gsr_grid_y(H);
-	gsr_launch(gsr_median_backward_kernel, dim3((ntiles + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG), dim3(64 * GSR_WAVES_PER_WG), 0, s, nullptr, nullptr, W, H, gx, ntiles,
+	const GsrTileGrid t = gsr_tile_grid(W, H);
+	gsr_launch(gsr_median_backward_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles,
 	           img.ranges, point_list, splat, slot_base, state, dL_dmedian, slots);
 }

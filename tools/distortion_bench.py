@@ -47,6 +47,7 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=200, help="(c): bench.py --steps")
     ap.add_argument("--bench-warmup", type=int, default=20, help="(c): bench.py --warmup")
     ap.add_argument("--out", default=os.path.join(R, "profiles", "distortion_bench.jsonl"))
+    ap.add_argument("--library", help="another build of the C ABI for every measurement of this process (_C.use_library)")
     args = ap.parse_args()
 
     c = None
@@ -64,6 +65,8 @@ def main():
 
     import gsr_scene
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
+    if args.library:
+        _C.use_library(args.library)
     dev = torch.device("cuda:0")
     scene, cam, D = gsr_scene.make_config(args.config, seed=0)
     H, W, P = cam.image_height, cam.image_width, int(scene.means3D.size(0))
@@ -122,7 +125,7 @@ def main():
                 stages.setdefault(name, []).append(ms)
     med = {n: statistics.median(v) for n, v in stages.items()}
     new, mom, plain = (statistics.median(wall[k]) for k in ("new", "moments", "plain"))
-    out = {"config": args.config, "mode": args.mode, "P": P, "W": W, "H": H, "steps": args.steps, "warmup": args.warmup,
+    out = {"library": _C.library_path(), "config": args.config, "mode": args.mode, "P": P, "W": W, "H": H, "steps": args.steps, "warmup": args.warmup,
            "a_forward_ms": {"distortion_forward": round(med["distortion_forward"], 4), "render_forward": round(med["render_forward"], 4),
                             "over_render_forward": round(med["distortion_forward"] / med["render_forward"], 3)},
            "a_backward_ms": {"distortion_backward": round(med["distortion_backward"], 4), "render_backward": round(med["render_backward"], 4),

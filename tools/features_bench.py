@@ -33,7 +33,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(R, "profiles", "features_bench.jsonl"))
+    ap.add_argument("--library", help="another build of the C ABI for every measurement of this process (_C.use_library)")
     args = ap.parse_args()
+    if args.library:
+        _C.use_library(args.library)
     dev = torch.device("cuda:0")
     scene, cam, D = gsr_scene.make_config(args.config, seed=0)
     H, W, P = cam.image_height, cam.image_width, int(scene.means3D.size(0))
@@ -96,7 +99,7 @@ def main():
                     stages.setdefault(name, []).append(ms)
         med = {n: statistics.median(v) for n, v in stages.items()}
         new, old = statistics.median(wall["new"]), statistics.median(wall["old"])
-        out = {"config": args.config, "P": P, "W": W, "H": H, "K": K, "chunks": nchunks, "steps": args.steps, "warmup": args.warmup,
+        out = {"library": _C.library_path(), "config": args.config, "P": P, "W": W, "H": H, "K": K, "chunks": nchunks, "steps": args.steps, "warmup": args.warmup,
                "a_forward_ms": {"features_forward": round(med["features_forward"], 4), "per_chunk": round(med["features_forward"] / nchunks, 4),
                                 "render_forward": round(med["render_forward"], 4),
                                 "per_chunk_over_render_forward": round(med["features_forward"] / nchunks / med["render_forward"], 3)},

@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=200, help="(c): bench.py --steps")
     ap.add_argument("--bench-warmup", type=int, default=20, help="(c): bench.py --warmup")
     ap.add_argument("--out", default=os.path.join(R, "profiles", "median_bench.jsonl"))
+    ap.add_argument("--library", help="another build of the C ABI for every measurement of this process (_C.use_library)")
     args = ap.parse_args()
 
     c = None
@@ -63,6 +64,8 @@ def main():
 
     import gsr_scene
     from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, _C
+    if args.library:
+        _C.use_library(args.library)
     dev = torch.device("cuda:0")
     scene, cam, D = gsr_scene.make_config(args.config, seed=0)
     H, W, P = cam.image_height, cam.image_width, int(scene.means3D.size(0))
@@ -122,7 +125,7 @@ def main():
                 "forward_over_render_forward": round(m["median_forward"] / m["render_forward"], 3),
                 "median_backward": round(m["median_backward"], 4), "render_backward": round(m["render_backward"], 4),
                 "backward_over_render_backward": round(m["median_backward"] / m["render_backward"], 3)}
-    out = {"config": args.config, "mode": args.mode, "P": P, "W": W, "H": H, "steps": args.steps, "warmup": args.warmup,
+    out = {"library": _C.library_path(), "config": args.config, "mode": args.mode, "P": P, "W": W, "H": H, "steps": args.steps, "warmup": args.warmup,
            "a_stages_ms": a_of(med["exit"]), "a_stages_full_walk_ms": a_of(med["full_walk"]),
            "b_step_ms": {"plain_depth_alpha": round(plain, 4), "with_median_depth": round(new, 4), "with_median_depth_and_index_maps": round(both, 4),
                          "ratio_to_plain": round(new / plain, 3), "added_over_plain_ms": round(new - plain, 4),
