@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -331,6 +332,18 @@ static int gsr_option_check(const char* who, int antialiasing, const gsr_aux_arg
 	return GSR_OK;
 }
 
+// The one validity check of a camera model (include/gsr_camera_model.h), called once by every *_cm entry point with a model
+static int gsr_camera_model_check(const char* who, const gsr_camera_model& m)
+{
+	if (m.model != GSR_CAMERA_PINHOLE && m.model != GSR_CAMERA_FISHEYE)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: unknown camera model %d", who, m.model);
+	if (!(m.fx > 0.f) || !(m.fy > 0.f) || !std::isfinite(m.fx) || !std::isfinite(m.fy))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: fx and fy must be finite and positive, got %g, %g", who, (double)m.fx, (double)m.fy);
+	if (!std::isfinite(m.cx) || !std::isfinite(m.cy))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cx and cy must be finite, got %g, %g", who, (double)m.cx, (double)m.cy);
+	return GSR_OK;
+}
+
 GsrGeometry gsr_geometry_view(void* blob, int P)
 {
 	gsr_geometry_layout l;
@@ -494,9 +507,9 @@ static thread_local GsrLastStage1 g_last_stage1;
 // ---- forward, stage 1 --------------------------------------------------------------------------
 // `in`: the caller's inputs (gsr_preprocess_inputs / gsr_preprocess_leaves); what stage 1 derives itself (focal lengths, trim, the
 // geometry view) is filled in here.  aux: 0 or a GSR_AUX_* mode; aa: the screen-space filter.  Both stay outside the struct, which
-// is the kernels' argument.
+// is the kernels' argument.  cm: NULL, or a checked camera model (include/gsr_camera_model.h): projmatrix and the tangents are not read.
 static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geometry, int64_t* num_rendered_host, void* stream, int debug,
-                                       int aux, int aa)
+                                       int aux, int aa, const gsr_camera_model* cm = nullptr)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
@@ -506,7 +519,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	*num_rendered_host = 0;
 	if (P < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "bad P / image size");
 	if (P == 0) return GSR_OK;  // rasterize_points.cu:94: nothing is launched for an empty scene
-	if (!a.means3D || !a.opacities || !a.viewmatrix || !a.projmatrix || !geometry)  // radii is optional (rasterizer.h:52)
+	if (!a.means3D || !a.opacities || !a.viewmatrix || (!a.projmatrix && !cm) || !geometry)  // radii is optional (rasterizer.h:52)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess: required pointer is NULL");
 	if (!a.colors_precomp && !a.shs)  // rasterizer_impl.cu:281-284
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "For non-RGB, provide precomputed Gaussian colors!");
@@ -522,6 +535,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	if (a.leaf && a.M > 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: at most 16 SH coefficients (degree 3), M = %d", a.M);
 	a.focal_y = height / (2.0f * a.tan_fovy);  // rasterizer_impl.cu:251-252
 	a.focal_x = width / (2.0f * a.tan_fovx);
+	if (cm) { a.focal_x = cm->fx; a.focal_y = cm->fy; }
 	a.g = gsr_geometry_view(geometry, P);
 
 	int rc;
@@ -574,7 +588,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	                         gsr_helper_stream(&td.copy_stream, &td.copy_fork, nullptr);
 	{
 		GsrProfScope p(s, "preprocess");
-		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux, aa);
+		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux, aa, cm);
 	}
 	if ((rc = gsr_stage_done(s, debug, "preprocess"))) return rc;
 	if (color && !beside) {
@@ -770,6 +784,56 @@ extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_ar
 	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing);
 }
 
+// a camera model (include/gsr_camera_model.h): model NULL = the *_aa call; else the model, the sizes and the geometry buffer are
+// checked first, under this call's name
+static int gsr_forward_cm_check(const char* who, const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int width,
+                                int height, const void* geometry)
+{
+	int rc;
+	if ((rc = gsr_camera_model_check(who, *model))) return rc;
+	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
+	if (P < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad P / image size", who);
+	if (P > 0 && !geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
+	return GSR_OK;
+}
+
+extern "C" int gsr_forward_preprocess_cm(const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int D, int M,
+                                         int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
+                                         const float* opacities, const float* scales, float scale_modifier, const float* rotations,
+                                         const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                         const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, int* radii,
+                                         void* geometry, int64_t* num_rendered_host, void* stream, int debug)
+{
+	if (!model)
+		return gsr_forward_preprocess_aa(antialiasing, aux, P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
+		                                 rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii,
+		                                 geometry, num_rendered_host, stream, debug);
+	int rc;
+	if ((rc = gsr_forward_cm_check("gsr_forward_preprocess_cm", model, antialiasing, aux, P, width, height, geometry))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing, model);
+}
+
+extern "C" int gsr_forward_preprocess_leaf_cm(const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int D, int M,
+                                              int width, int height, const float* xyz, const float* features_dc,
+                                              const float* features_rest, const float* opacity_logits, const float* log_scales,
+                                              float scale_modifier, const float* raw_rotations, const float* viewmatrix,
+                                              const float* projmatrix, const float* cam_pos, float tan_fovx, float tan_fovy,
+                                              int prefiltered, int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
+                                              int debug)
+{
+	if (!model)
+		return gsr_forward_preprocess_leaf_aa(antialiasing, aux, P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales,
+		                                      scale_modifier, raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
+		                                      radii, geometry, num_rendered_host, stream, debug);
+	int rc;
+	if ((rc = gsr_forward_cm_check("gsr_forward_preprocess_leaf_cm", model, antialiasing, aux, P, width, height, geometry))) return rc;
+	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
+	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing, model);
+}
+
 // ---- forward, stage 2 --------------------------------------------------------------------------
 static int gsr_forward_render_impl(int P, int64_t R, int width, int height, const float* background,
                                    const int* radii, void* geometry, void* binning, void* image, float* out_color,
@@ -874,11 +938,12 @@ extern "C" int gsr_forward_render_aux(const gsr_aux_args* aux, int P, int64_t R,
 }
 
 // ---- backward ----------------------------------------------------------------------------------
-static int gsr_backward_check(const gsr_backward_args& a, const char* who)
+// has_model: a camera model stands in for projmatrix (include/gsr_camera_model.h)
+static int gsr_backward_check(const gsr_backward_args& a, const char* who, bool has_model = false)
 {
 	if (a.P < 0 || a.num_rendered < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
 	if (a.P == 0) return GSR_OK;
-	if (!a.background || !a.means3D || !a.viewmatrix || !a.projmatrix || !a.geometry || !a.image || !a.dL_dpix ||
+	if (!a.background || !a.means3D || !a.viewmatrix || (!a.projmatrix && !has_model) || !a.geometry || !a.image || !a.dL_dpix ||
 	    !a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D || !a.dL_dscale || !a.dL_drot || (a.num_rendered > 0 && (!a.binning || !a.scratch)))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: required pointer is NULL");
 	// dL_dconic is an intermediate; dL_dcolor / dL_dcov3D are only results when the colours / covariances were
@@ -952,14 +1017,15 @@ extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_a
 
 // aux: 0 or a GSR_AUX_* mode; aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h), NULL: the default ones
 // cam: NULL, or the camera gradients (include/gsr_cam.h; checked by the caller): the twin kernels, then the fold of their rows
+// cm: NULL, or a checked camera model (include/gsr_camera_model.h; never with cam): its twin kernels
 static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities,
-                                       const gsr_cam_args* cam = nullptr)
+                                       const gsr_cam_args* cam = nullptr, const gsr_camera_model* cm = nullptr)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
 	const gsr_backward_args& b = *args;
 	int rc;
-	if ((rc = gsr_backward_check(b, "gsr_backward_gaussians"))) return rc;
+	if ((rc = gsr_backward_check(b, "gsr_backward_gaussians", cm != nullptr))) return rc;
 	if (first < 0 || count < 0 || (int64_t)first + count > b.P || (first & 63) || (out_row0 != 0 && out_row0 != first))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: bad range [%d, %d + %d) of %d Gaussians (first must be a multiple "
 		                "of 64, out_row0 must be 0 or first)", first, first, count, b.P);
@@ -982,6 +1048,7 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.tan_fovx = b.tan_fovx; a.tan_fovy = b.tan_fovy;
 	a.focal_y = b.height / (2.0f * b.tan_fovy);
 	a.focal_x = b.width / (2.0f * b.tan_fovx);
+	if (cm) { a.focal_x = cm->fx; a.focal_y = cm->fy; }
 	a.radii = b.radii; a.g = gsr_geometry_view(b.geometry, b.P);
 	a.slots = (const GsrGradSlot*)b.scratch; a.slot_valid = gsr_slot_valid_of(b);
 	a.dL_dmean2D = b.dL_dmean2D; a.dL_dconic = b.dL_dconic; a.dL_dopacity = b.dL_dopacity; a.dL_dcolor = b.dL_dcolor;
@@ -989,7 +1056,7 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam ? (float*)cam->scratch : nullptr);
+		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam ? (float*)cam->scratch : nullptr, cm);
 	}
 	if (!cam) return gsr_stage_done(s, b.debug, "gaussian_backward");
 	if ((rc = gsr_stage_done(s, b.debug, "gaussian_backward"))) return rc;
@@ -1021,6 +1088,22 @@ extern "C" int gsr_backward_gaussians_aa(const gsr_backward_args* args, int anti
 	if (antialiasing && args && args->P > 0 && count > 0 && !opacities)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians_aa: the opacity input is NULL");
 	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr);
+}
+
+// a camera model (include/gsr_camera_model.h): model NULL = gsr_backward_gaussians_aa
+extern "C" int gsr_backward_gaussians_cm(const gsr_backward_args* args, const gsr_camera_model* model, int antialiasing, const float* opacities,
+                                         const gsr_aux_args* aux, int first, int count, int out_row0)
+{
+	if (!model) return gsr_backward_gaussians_aa(args, antialiasing, opacities, aux, first, count, out_row0);
+	const char* who = "gsr_backward_gaussians_cm";
+	int rc;
+	if ((rc = gsr_camera_model_check(who, *model))) return rc;
+	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	if (args->P < 0 || args->num_rendered < 0 || args->width <= 0 || args->height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (args->P > 0 && !args->geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
+	if (antialiasing && args->P > 0 && count > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, nullptr, model);
 }
 
 // ---- camera gradients (include/gsr_cam.h) ----

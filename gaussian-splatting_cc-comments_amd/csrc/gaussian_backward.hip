@@ -7,6 +7,7 @@
 // rasterize_points.cu:168-178: every output element is written exactly once.
 #include "gsr_internal.h"
 #include "gsr_aa.h"
+#include "gsr_camera_model.h"
 #include "gsr_depth_key.h"   // gsr_sync()
 #include <type_traits>
 
@@ -202,13 +203,18 @@ template <typename Base>
 struct GsrGaussianBackwardCam : Base {
 	float* cam_partials;   // [waves of the launch][GSR_CAM_ROW]
 };
+// CM: a camera model (include/gsr_camera_model.h; never together with CAM).  gsr_cm_cov2d recomputes the forward's values, the
+// covariance chain also forms dL/dJ01 and dL/dJ10, and dL/dt -- from the six dL/dJ and from dL/dmean2D, which no longer goes through
+// the projection matrix -- comes from gsr_cm_backward (gsr_camera_model.h).  The arguments get the model behind them (GsrWithCameraModel).
 #define GSR_GB_THREADS 64
-template <bool LEAF, int AUX, bool AA, bool CAM>
+template <bool AA> using GsrGbArgs = typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type;
+template <bool LEAF, int AUX, bool AA, bool CAM, bool CM>
 __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
-	typename std::conditional<CAM, GsrGaussianBackwardCam<typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type>,
-	                          typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type>::type a,
+	typename std::conditional<CAM, GsrGaussianBackwardCam<GsrGbArgs<AA>>,
+	                          typename std::conditional<CM, GsrWithCameraModel<GsrGbArgs<AA>>, GsrGbArgs<AA>>::type>::type a,
 	int sh_via_lds, int skip_dsh)
 {
+	static_assert(!(CAM && CM), "the camera gradients differentiate the projection matrix: no camera-model form");
 	// staging of the dL/dsh output block: rows of 13 float4; the packed layout goes out in two halves of 32 rows
 	// (6.6 KB per wave), the split leaf tensors as one linear 12 KB block
 	__shared__ float4 s_sh[GSR_GB_THREADS / 64][(LEAF ? 64 : 32) * GSR_SH_ROW4];
@@ -363,10 +369,19 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 		}
 		const float dcx = dconic[0], dcy = dconic[1], dcz = dconic[3];
 		GsrCov2D c2;
-		gsr_cov2d(mean, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, a.viewmatrix, c2);
+		[[maybe_unused]] GsrCmExtra cm_e;
+		if constexpr (CM) {
+			float cm_u, cm_v;
+			gsr_cm_cov2d(mean, a.cm_model, a.focal_x, a.focal_y, a.cm_cx, a.cm_cy, a.W, a.H, cov3D, a.viewmatrix, c2, cm_e, cm_u, cm_v);
+		} else {
+			gsr_cov2d(mean, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, a.viewmatrix, c2);
+		}
 		const float h_x = a.focal_x, h_y = a.focal_y;
-		const float x_grad_mul = (c2.txtz < -c2.limx || c2.txtz > c2.limx) ? 0.f : 1.f;
-		const float y_grad_mul = (c2.tytz < -c2.limy || c2.tytz > c2.limy) ? 0.f : 1.f;
+		// the core camera's symmetric band, read by the !CM branch below alone.  (They stand here, in front of the covariance chain, because
+		// inside that branch the default instantiations compile to another instruction order; with CM they are dead code -- limx and limy
+		// are 0 -- and gsr_cm_backward tests the model's own band from GsrCmExtra.)
+		[[maybe_unused]] const float x_grad_mul = (c2.txtz < -c2.limx || c2.txtz > c2.limx) ? 0.f : 1.f;
+		[[maybe_unused]] const float y_grad_mul = (c2.tytz < -c2.limy || c2.tytz > c2.limy) ? 0.f : 1.f;
 		const GsrMat3& T = c2.T;
 		const GsrMat3& Wm = c2.W;
 		const GsrMat3& Vrk = c2.Vrk;
@@ -411,27 +426,39 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 		const float dL_dJ02 = Wm.m[2][0] * dL_dT00 + Wm.m[2][1] * dL_dT01 + Wm.m[2][2] * dL_dT02;
 		const float dL_dJ11 = Wm.m[1][0] * dL_dT10 + Wm.m[1][1] * dL_dT11 + Wm.m[1][2] * dL_dT12;
 		const float dL_dJ12 = Wm.m[2][0] * dL_dT10 + Wm.m[2][1] * dL_dT11 + Wm.m[2][2] * dL_dT12;
-		const float tz = 1.f / t.z;
-		const float tz2 = tz * tz;
-		const float tz3 = tz2 * tz;
-		const float dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
-		const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
-		const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 + (2 * h_y * t.y) * tz3 * dL_dJ12;
 		const float* vm = a.viewmatrix;  // transformVec4x3Transpose, auxiliary.h:91-99
-		dmean3D[0] = vm[0] * dL_dtx + vm[1] * dL_dty + vm[2] * dL_dtz;
-		dmean3D[1] = vm[4] * dL_dtx + vm[5] * dL_dty + vm[6] * dL_dtz;
-		dmean3D[2] = vm[8] * dL_dtx + vm[9] * dL_dty + vm[10] * dL_dtz;
+		[[maybe_unused]] float dL_dtx = 0.f, dL_dty = 0.f, dL_dtz = 0.f, gx2 = 0.f, gy2 = 0.f, m_w = 0.f, mul1 = 0.f, mul2 = 0.f;
+		if constexpr (CM) {
+			const float dJ[6] = {dL_dJ00, Wm.m[1][0] * dL_dT00 + Wm.m[1][1] * dL_dT01 + Wm.m[1][2] * dL_dT02, dL_dJ02,
+			                     Wm.m[0][0] * dL_dT10 + Wm.m[0][1] * dL_dT11 + Wm.m[0][2] * dL_dT12, dL_dJ11, dL_dJ12};
+			// dL/dmean2D is in the units of the core camera's NDC chain: 0.5 W dL/du, 0.5 H dL/dv
+			float dt[3];
+			gsr_cm_backward(a.cm_model, h_x, h_y, c2, cm_e, dJ, dmean2D[0] / (0.5f * (float)a.W), dmean2D[1] / (0.5f * (float)a.H), dt);
+			dmean3D[0] = vm[0] * dt[0] + vm[1] * dt[1] + vm[2] * dt[2];
+			dmean3D[1] = vm[4] * dt[0] + vm[5] * dt[1] + vm[6] * dt[2];
+			dmean3D[2] = vm[8] * dt[0] + vm[9] * dt[1] + vm[10] * dt[2];
+		} else {
+			const float tz = 1.f / t.z;
+			const float tz2 = tz * tz;
+			const float tz3 = tz2 * tz;
+			dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
+			dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
+			dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 + (2 * h_y * t.y) * tz3 * dL_dJ12;
+			dmean3D[0] = vm[0] * dL_dtx + vm[1] * dL_dty + vm[2] * dL_dtz;
+			dmean3D[1] = vm[4] * dL_dtx + vm[5] * dL_dty + vm[6] * dL_dtz;
+			dmean3D[2] = vm[8] * dL_dtx + vm[9] * dL_dty + vm[10] * dL_dtz;
 
-		// ---- preprocessCUDA backward, backward.cu:349-399 ----
-		const float* proj = a.projmatrix;
-		const float m_hom_w = proj[3] * mean.x + proj[7] * mean.y + proj[11] * mean.z + proj[15];
-		const float m_w = 1.0f / (m_hom_w + 0.0000001f);
-		const float mul1 = (proj[0] * mean.x + proj[4] * mean.y + proj[8] * mean.z + proj[12]) * m_w * m_w;
-		const float mul2 = (proj[1] * mean.x + proj[5] * mean.y + proj[9] * mean.z + proj[13]) * m_w * m_w;
-		const float gx2 = dmean2D[0], gy2 = dmean2D[1];
-		dmean3D[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
-		dmean3D[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
-		dmean3D[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
+			// ---- preprocessCUDA backward, backward.cu:349-399 ----
+			const float* proj = a.projmatrix;
+			const float m_hom_w = proj[3] * mean.x + proj[7] * mean.y + proj[11] * mean.z + proj[15];
+			m_w = 1.0f / (m_hom_w + 0.0000001f);
+			mul1 = (proj[0] * mean.x + proj[4] * mean.y + proj[8] * mean.z + proj[12]) * m_w * m_w;
+			mul2 = (proj[1] * mean.x + proj[5] * mean.y + proj[9] * mean.z + proj[13]) * m_w * m_w;
+			gx2 = dmean2D[0]; gy2 = dmean2D[1];
+			dmean3D[0] += (proj[0] * m_w - proj[3] * mul1) * gx2 + (proj[1] * m_w - proj[3] * mul2) * gy2;
+			dmean3D[1] += (proj[4] * m_w - proj[7] * mul1) * gx2 + (proj[5] * m_w - proj[7] * mul2) * gy2;
+			dmean3D[2] += (proj[8] * m_w - proj[11] * mul1) * gx2 + (proj[9] * m_w - proj[11] * mul2) * gy2;
+		}
 		if (AUX) {   // the depth value's own path: v = z or 1 / z, z = (V mean)_z
 			const float dv = acc[NACC - 1];
 			const float dz = AUX == GSR_AUX_INVDEPTH ? -dv / (t.z * t.z) : dv;
@@ -572,7 +599,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 
 // one instantiation per (LEAF, depth-and-alpha mode, AA): the AA ones are those that receive the struct with the opacity input
 template <typename Args>
-static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux, float* cam_partials)
+static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux, float* cam_partials, const gsr_camera_model* cm)
 {
 	constexpr bool AA = std::is_same<Args, GsrGaussianBackwardArgsAA>::value;
 	// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
@@ -585,21 +612,29 @@ static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux
 			GsrGaussianBackwardCam<Args> c;
 			static_cast<Args&>(c) = a;
 			c.cam_partials = cam_partials;
-			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
+			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true, false>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
 			return;
 		}
-		gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, false>, grid, dim3(GSR_GB_THREADS), 0, s,
+		if (cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
+			GsrWithCameraModel<Args> c;
+			static_cast<Args&>(c) = a;
+			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
+			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, false, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
+			return;
+		}
+		gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, false, false>, grid, dim3(GSR_GB_THREADS), 0, s,
 		           nullptr, nullptr, a, sh_via_lds, skip_dsh);
 	});
 }
 
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials)
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials,
+                                  const gsr_camera_model* cm)
 {
-	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux, cam_partials);
+	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux, cam_partials, cm);
 	GsrGaussianBackwardArgsAA x;
 	static_cast<GsrGaussianBackwardArgs&>(x) = a;
 	x.opacities = aa_opacities;
-	gsr_launch_gaussian_backward_t(x, s, aux, cam_partials);
+	gsr_launch_gaussian_backward_t(x, s, aux, cam_partials, cm);
 }
 
 // ---- fold of the camera partials (include/gsr_cam.h) ---------------------------------------------------------------------------

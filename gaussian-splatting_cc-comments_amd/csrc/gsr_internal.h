@@ -11,6 +11,7 @@
 #include "../../include/gsr_aux.h"
 #include "../../include/gsr_cam.h"
 #include "../../include/gsr_absgrad.h"
+#include "../../include/gsr_camera_model.h"
 #include "gsr_device.h"
 
 #define GSR_PREPROCESS_BLOCK 256  // Gaussians per workgroup of the binning kernels (granularity of their scans)
@@ -184,7 +185,8 @@ struct GsrPreprocessArgs {
 // aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the kernels then also store the depth value v in the splat record's last word
 // aa: the anti-aliased path (include/gsr_aa.h): the record's opacity is opacity * rho (gsr_aa.h); the colour kernel has no such variant
 // done: NULL, or an event signalled when the kernel has finished (gsr_launch)
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa);
+// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h; checked by the caller), with a.focal_x / a.focal_y = fx, fy
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa, const gsr_camera_model* cm = nullptr);
 void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done);
 bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a);
 void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu, int aux);
@@ -335,7 +337,9 @@ struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
 // dL/dcov3D and dL/dmean3D
 // cam_partials: NULL, or the camera-gradient kernels (include/gsr_cam.h), which also store one row of 32 floats per wave of 64
 // Gaussians there (gsr_cam_rows(count) rows; first must be 0); gsr_launch_camera_grad_fold adds the rows into the 35 outputs
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials = nullptr);
+// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h; never with cam_partials), with a.focal_x / a.focal_y = fx, fy
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials = nullptr,
+                                  const gsr_camera_model* cm = nullptr);
 size_t gsr_cam_rows(int P);
 void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,

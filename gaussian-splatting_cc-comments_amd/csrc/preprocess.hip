@@ -8,6 +8,7 @@
 #include "gsr_internal.h"
 #include "gsr_rect_trim.h"
 #include "gsr_aa.h"
+#include "gsr_camera_model.h"
 
 // forward.cu:21-81 computeColorFromSH, one channel at a time in the glm::vec3 expression order
 __device__ __forceinline__ float gsr_sh_channel(int deg, const float* sh, int ch, float x, float y, float z)
@@ -46,9 +47,13 @@ __device__ __forceinline__ float gsr_sh_channel(int deg, const float* sh, int ch
 // AUX: 0, or the depth-and-alpha mode (include/gsr.h GSR_AUX_*): the colors_precomp path then stores the depth value v in the
 // record's last word (the colour kernel does it on the SH path).
 // AA: the anti-aliased path (include/gsr_aa.h): the record and the trim get opacity * rho of the undilated 2D covariance (gsr_aa.h)
-template <bool LEAF, int AUX, bool AA>
-__global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(GsrPreprocessArgs a, uint32_t* __restrict__ clear, size_t clear_words,
-                                                                              uint32_t* __restrict__ clear2, size_t clear2_words)
+// CM: a camera model (include/gsr_camera_model.h): pixel mean and 2D covariance come from gsr_cm_cov2d (gsr_camera_model.h) instead of the
+// projection matrix and gsr_cov2d; everything behind them consumes (pixel mean, covariance) as before.  The arguments get the model
+// behind them in a struct of its own (GsrWithCameraModel).
+template <bool LEAF, int AUX, bool AA, bool CM>
+__global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(
+	typename std::conditional<CM, GsrWithCameraModel<GsrPreprocessArgs>, GsrPreprocessArgs>::type a, uint32_t* __restrict__ clear, size_t clear_words,
+	uint32_t* __restrict__ clear2, size_t clear2_words)
 {
 	const int idx = blockIdx.x * GSR_PREPROCESS_BLOCK + threadIdx.x;
 	// The Gaussian's inputs, unconditionally (a culled Gaussian wastes 44 bytes): every load of the wave is in flight at
@@ -83,12 +88,15 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 				if (a.prefiltered) atomicOr(&a.g.status[0], 1u);
 				break;
 			}
-			const float* pm = a.projmatrix;
-			float hx = pm[0] * p_orig.x + pm[4] * p_orig.y + pm[8] * p_orig.z + pm[12];
-			float hy = pm[1] * p_orig.x + pm[5] * p_orig.y + pm[9] * p_orig.z + pm[13];
-			float hw = pm[3] * p_orig.x + pm[7] * p_orig.y + pm[11] * p_orig.z + pm[15];
-			float p_w = 1.0f / (hw + 0.0000001f);
-			float p_proj_x = hx * p_w, p_proj_y = hy * p_w;
+			float p_proj_x = 0.f, p_proj_y = 0.f;
+			if constexpr (!CM) {
+				const float* pm = a.projmatrix;
+				float hx = pm[0] * p_orig.x + pm[4] * p_orig.y + pm[8] * p_orig.z + pm[12];
+				float hy = pm[1] * p_orig.x + pm[5] * p_orig.y + pm[9] * p_orig.z + pm[13];
+				float hw = pm[3] * p_orig.x + pm[7] * p_orig.y + pm[11] * p_orig.z + pm[15];
+				float p_w = 1.0f / (hw + 0.0000001f);
+				p_proj_x = hx * p_w; p_proj_y = hy * p_w;
+			}
 
 			float cov3D[6];
 			if (a.cov3D_precomp) {
@@ -102,7 +110,13 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 				gsr_cov3d(sc, a.scale_modifier, q, cov3D);
 			}
 			GsrCov2D c2;
-			gsr_cov2d(p_orig, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, a.viewmatrix, c2);
+			float pix = 0.f, piy = 0.f;
+			if constexpr (CM) {
+				GsrCmExtra ce;
+				gsr_cm_cov2d(p_orig, a.cm_model, a.focal_x, a.focal_y, a.cm_cx, a.cm_cy, a.W, a.H, cov3D, a.viewmatrix, c2, ce, pix, piy);
+			} else {
+				gsr_cov2d(p_orig, a.focal_x, a.focal_y, a.tan_fovx, a.tan_fovy, cov3D, a.viewmatrix, c2);
+			}
 			const float cx = c2.a, cy = c2.b, cz = c2.c;
 			float det = (cx * cz - cy * cy);
 			if (det == 0.0f) break;
@@ -112,7 +126,7 @@ __global__ void __launch_bounds__(GSR_PREPROCESS_BLOCK) gsr_preprocess_kernel(Gs
 			float lambda1 = mid + sqrtf(fmaxf(0.1f, mid * mid - det));
 			float lambda2 = mid - sqrtf(fmaxf(0.1f, mid * mid - det));
 			float my_radius = ceilf(3.f * sqrtf(fmaxf(lambda1, lambda2)));
-			float pix = gsr_ndc2pix(p_proj_x, a.W), piy = gsr_ndc2pix(p_proj_y, a.H);
+			if constexpr (!CM) { pix = gsr_ndc2pix(p_proj_x, a.W); piy = gsr_ndc2pix(p_proj_y, a.H); }
 			int minx, miny, maxx, maxy;
 			gsr_get_rect(pix, piy, gsr_f2i(my_radius), gx, gy, minx, miny, maxx, maxy);
 			if ((maxx - minx) * (maxy - miny) == 0) break;
@@ -299,8 +313,9 @@ void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done)
 	gsr_launch(gsr_zero_status_kernel, dim3(1), dim3(256), 0, s, nullptr, done, status);
 }
 
-// one instantiation per (LEAF, depth-and-alpha mode, AA); done: the event the count's read-back waits for (api.hip)
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa)
+// one instantiation per (LEAF, depth-and-alpha mode, AA) and, with a camera model, one more each; done: the event the count's
+// read-back waits for (api.hip)
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa, const gsr_camera_model* cm)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
 	uint32_t* clear = (uint32_t*)a.g.sort_table;
@@ -308,7 +323,15 @@ void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t
 	uint32_t* clear2 = (uint32_t*)a.g.col_table;
 	const size_t clear2_words = gsr_tilebin_col_clear_words((size_t)a.P);
 	gsr_variant(a.leaf, aux, aa, [&](auto LEAF, auto AUX, auto AA) {
-		gsr_launch(gsr_preprocess_kernel<LEAF(), AUX(), AA()>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done,
+		if (cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
+			GsrWithCameraModel<GsrPreprocessArgs> c;
+			static_cast<GsrPreprocessArgs&>(c) = a;
+			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
+			gsr_launch(gsr_preprocess_kernel<LEAF(), AUX(), AA(), true>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done,
+			           c, clear, clear_words, clear2, clear2_words);
+			return;
+		}
+		gsr_launch(gsr_preprocess_kernel<LEAF(), AUX(), AA(), false>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done,
 		           a, clear, clear_words, clear2, clear2_words);
 	});
 }

@@ -10,7 +10,9 @@ provider here: every tensor is handed to the C ABI (include/gsr.h) as a raw devi
 There is no CPU fallback: a missing library or a non-HIP tensor raises.
 """
 import ctypes
+import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -72,6 +74,26 @@ class CamArgs(ctypes.Structure):
 class AbsgradArgs(ctypes.Structure):
     """include/gsr_absgrad.h gsr_absgrad_args"""
     _fields_ = [("abs_dL_dmean2D", _vp), ("stat_abs_gradient_accum", _vp)]
+
+
+class CameraModelArgs(ctypes.Structure):
+    """include/gsr_camera_model.h gsr_camera_model"""
+    _fields_ = [("model", _i), ("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f)]
+
+
+CAMERA_MODELS = {"pinhole": 0, "fisheye": 1}   # GSR_CAMERA_PINHOLE / GSR_CAMERA_FISHEYE
+
+
+class CameraModel(NamedTuple):
+    """A camera model of include/gsr_camera_model.h: model "pinhole" (with intrinsics: an off-centre principal point) or "fisheye"
+    (equidistant, no distortion coefficients); fx, fy in pixels; cx, cy in pixels in the OpenCV / COLMAP convention (origin at the
+    corner of the first pixel, pixel centres at +0.5).  The default camera of a W x H image is
+    CameraModel("pinhole", W / (2 tanfovx), H / (2 tanfovy), W / 2, H / 2)."""
+    model: str
+    fx: float
+    fy: float
+    cx: float
+    cy: float
 
 
 class AuxLayout(ctypes.Structure):
@@ -227,6 +249,14 @@ def lib():
         L.gsr_depth_normals_backward.argtypes = [_i, _i, _vp, _f, _f, _vp, _vp, _vp]
         L.gsr_normal_consistency_loss.restype = _i
         L.gsr_normal_consistency_loss.argtypes = [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]
+    # include/gsr_camera_model.h: the *_aa calls with a camera model (the same holds for an older library)
+    if hasattr(L, "gsr_forward_preprocess_cm"):
+        pm = ctypes.POINTER(CameraModelArgs)
+        for name, argtypes in (("gsr_forward_preprocess_cm", [pm] + list(L.gsr_forward_preprocess_aa.argtypes)),
+                               ("gsr_forward_preprocess_leaf_cm", [pm] + list(L.gsr_forward_preprocess_leaf_aa.argtypes)),
+                               ("gsr_backward_gaussians_cm", [pb, pm, _i, _vp, pa, _i, _i, _i])):
+            getattr(L, name).restype = _i
+            getattr(L, name).argtypes = argtypes
     _lib = L
     return L
 
@@ -282,6 +312,49 @@ def camera_flag(camera_grads):
     return camera_grads
 
 
+def camera_model(cm):
+    """Checks the `camera_model` keyword: None, a CameraModel or any 5-tuple (model, fx, fy, cx, cy) -> None or a CameraModel of
+    Python floats.  Anything else raises TypeError (numbers that are no real numbers too); a model string other than "pinhole" /
+    "fisheye", a focal length that is not finite and positive and a principal point that is not finite raise ValueError.  No
+    library is touched."""
+    if cm is None:
+        return None
+    if not isinstance(cm, tuple) or len(cm) != 5:
+        raise TypeError(f"camera_model must be a CameraModel or a 5-tuple (model, fx, fy, cx, cy), got {cm!r}")
+    model, *nums = cm
+    if not isinstance(model, str):
+        raise TypeError(f"camera_model: model must be a string, got {model!r}")
+    if model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model: model must be one of {sorted(CAMERA_MODELS)}, got {model!r}")
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in nums):
+        raise TypeError(f"camera_model: fx, fy, cx, cy must be real numbers, got {tuple(nums)!r}")
+    fx, fy, cx, cy = (float(v) for v in nums)
+    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0):
+        raise ValueError(f"camera_model: fx and fy must be finite and positive, got {fx}, {fy}")
+    if not (math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"camera_model: cx and cy must be finite, got {cx}, {cy}")
+    return CameraModel(model, fx, fy, cx, cy)
+
+
+def camera_model_args(cm):
+    """A checked CameraModel (camera_model()) or None -> CameraModelArgs or None"""
+    if cm is None:
+        return None
+    return CameraModelArgs(CAMERA_MODELS[cm.model], cm.fx, cm.fy, cm.cx, cm.cy)
+
+
+def camera_model_excludes(cm, camera_grads=False, what=None):
+    """The combinations a camera model has no form for, refused with NotImplementedError before anything runs: the camera gradients
+    (their 27 terms differentiate projmatrix), and `what`, the name of a path without one."""
+    if cm is None:
+        return
+    if what is not None:
+        raise NotImplementedError(f"{what} has no camera_model form")
+    if camera_grads is True:
+        raise NotImplementedError("camera_grads=True has no camera_model form: the camera gradients differentiate projmatrix, "
+                                  "which a camera model ignores")
+
+
 def absgrad_tensors(absgrad, P, device=None):
     """Checks the `absgrad` keyword: (abs_mean2D float32 [P, 2] or None, abs_gradient_accum float32 [P] or None), contiguous tensors
     on `device` (None: any HIP device, the same for both) -> AbsgradArgs.  Anything but a 2-tuple raises TypeError; a wrong dtype,
@@ -327,18 +400,27 @@ def camera_backward_args(P, device):
 
 
 # ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
-def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, absgrad=False):
+def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, absgrad=False, cm=None):
     """-> (function of L, the arguments that precede the default entry point's own).  stage: "preprocess" | "render" (the two forward
     calls) | "blend" | "gaussians" (the two backward stages: their leading arguments follow the gsr_backward_args pointer); leaf: the
     inputs are the optimiser's leaves (fused_params.py); x: the AuxArgs of a call with depth and alpha maps, or None; aa: the
     screen-space filter, whose per-Gaussian backward reads the forward's opacity input at address `opacities`.  The *_aa entry
     points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice.
     cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None.
-    absgrad: the blend that also leaves the sums of per-pixel moduli in the slots (include/gsr_absgrad.h)."""
+    absgrad: the blend that also leaves the sums of per-pixel moduli in the slots (include/gsr_absgrad.h).
+    cm: the CameraModelArgs of a call with a camera model (include/gsr_camera_model.h), or None: the *_cm entry points take the model in
+    front of the *_aa arguments; the stages that only read the splat records have none."""
     xr = None if x is None else ctypes.byref(x)
-    if stage == "preprocess":
+    if cm is not None and cam is not None:
+        raise NotImplementedError("camera gradients have no camera_model form")
+    if stage == "preprocess" and cm is not None:
+        name = "gsr_forward_preprocess_leaf_cm" if leaf else "gsr_forward_preprocess_cm"
+        lead = (ctypes.byref(cm), int(aa), xr)
+    elif stage == "preprocess":
         name = "gsr_forward_preprocess_leaf" if leaf else "gsr_forward_preprocess"
         name, lead = (name + "_aa", (1, xr)) if aa else (name + "_aux", (xr,)) if x is not None else (name, ())
+    elif stage == "gaussians" and cm is not None:
+        name, lead = "gsr_backward_gaussians_cm", (ctypes.byref(cm), int(aa), opacities if aa else None, xr)
     elif stage == "gaussians" and cam is not None:
         name, lead = "gsr_backward_gaussians_cam", (int(aa), opacities if aa else None, xr, ctypes.byref(cam))
     elif stage == "gaussians":
@@ -353,11 +435,13 @@ def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, abs
 
 
 # ---- the forward of every variant ------------------------------------------------------------------------------------------------
-def run_forward(leaf, mode, antialiasing, background, named, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug):
+def run_forward(leaf, mode, antialiasing, background, named, degree, M, W, H, scale_modifier, tan_fovx, tan_fovy, prefiltered, debug,
+                camera_model=None):
     """Validate, allocate, preprocess, read the count back, allocate the binning state, render.
     named: the tensor arguments of the preprocess entry point in its order, as (tensor, name in error messages): the Gaussians first
     (five tensors, means3D leading, before scale_modifier; the rest after it), then viewmatrix, projmatrix, campos.
     mode: None, or aux_mode() of the depth and alpha maps to produce.
+    camera_model: None, or a checked CameraModel (include/gsr_camera_model.h): projmatrix, tan_fovx and tan_fovy are then ignored.
     -> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer, the contiguous tensors of `named`,
         () or (depth (1,H,W), alpha (1,H,W), auxBuffer))"""
     aa = aa_flag(antialiasing)
@@ -387,7 +471,7 @@ def run_forward(leaf, mode, antialiasing, background, named, degree, M, W, H, sc
         if mode is not None:
             x = AuxArgs()
             x.mode = mode   # all that preprocess reads of it; the outputs are set once the count is known
-        preprocess, pre_lead = _entry(L, "preprocess", leaf, x, aa)
+        preprocess, pre_lead = _entry(L, "preprocess", leaf, x, aa, cm=camera_model_args(camera_model))
         render, ren_lead = _entry(L, "render", leaf, x)
         R = _i64(0)
         stream, dbg = _stream(dev), _dbg(debug)
@@ -405,36 +489,38 @@ def run_forward(leaf, mode, antialiasing, background, named, degree, M, W, H, sc
 
 
 def _forward_plain(mode, antialiasing, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                   viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug):
+                   viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
+                   cm=None):
     """The reference's argument list (rasterize_points.cu:38-59) -> run_forward()'s, in gsr_forward_preprocess's order."""
     r = run_forward(False, mode, antialiasing, background,
                     ((means3D, "means3D"), (sh, "shs"), (colors, "colors_precomp"), (opacity, "opacities"), (scales, "scales"),
                      (rotations, "rotations"), (cov3D_precomp, "cov3D_precomp"), (viewmatrix, "viewmatrix"),
                      (projmatrix, "projmatrix"), (campos, "campos")),
                     degree, int(sh.size(1)) if sh.numel() != 0 else 0, image_width, image_height, scale_modifier, tan_fovx,
-                    tan_fovy, prefiltered, debug)
+                    tan_fovy, prefiltered, debug, camera_model(cm))
     return r[:6] + r[7]
 
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, debug, *, antialiasing=False):
+                        prefiltered, debug, *, antialiasing=False, camera_model=None):
     """-> (num_rendered, out_color (3,H,W) f32, radii (P,) i32, geomBuffer, binningBuffer, imgBuffer)
-    antialiasing: the screen-space filter (include/gsr_aa.h): the splat records carry opacity * rho"""
+    antialiasing: the screen-space filter (include/gsr_aa.h): the splat records carry opacity * rho
+    camera_model: a CameraModel (include/gsr_camera_model.h): projmatrix, tan_fovx and tan_fovy are then ignored"""
     return _forward_plain(None, antialiasing, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                           cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                          prefiltered, debug)
+                          prefiltered, debug, camera_model)
 
 
 def rasterize_gaussians_depth_alpha(depth_alpha, background, means3D, colors, opacity, scales, rotations, scale_modifier,
                                     cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                                    degree, campos, prefiltered, debug, *, antialiasing=False):
+                                    degree, campos, prefiltered, debug, *, antialiasing=False, camera_model=None):
     """rasterize_gaussians() with the depth and alpha maps of mode `depth_alpha` ("depth" / "invdepth") from the same blend pass
     -> (num_rendered, out_color, radii, geomBuffer, binningBuffer, imgBuffer, depth (1,H,W), alpha (1,H,W), auxBuffer).
     Colour, radii and the state buffers are bit-identical with rasterize_gaussians()'s (with the same `antialiasing`)."""
     return _forward_plain(aux_mode(depth_alpha), antialiasing, background, means3D, colors, opacity, scales, rotations,
                           scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh,
-                          degree, campos, prefiltered, debug)
+                          degree, campos, prefiltered, debug, camera_model)
 
 
 # ---- the backward of every variant -----------------------------------------------------------------------------------------------
@@ -464,7 +550,7 @@ def aux_backward_args(mode, scratch, dL_ddepth, dL_dalpha, device):
 
 
 def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_part=None, after_part=None, cam=None, absgrad=None,
-                 features=None, distortion=None, median=None):
+                 features=None, distortion=None, median=None, camera_model=None):
     """The two-stage backward of a filled BackwardArgs `a` (inputs, outputs, stats; `scratch` is the tensor behind a.scratch): the
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
@@ -481,7 +567,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     place, behind the features', and adds into the slots' words 0..5 and 9 -- x (the AuxArgs) is then required, so that the aux
     kernels write and chain word 9.
     median: MedianBackward (include/gsr_median.h) when the median-depth map took part in the loss: its pass runs at the same place and
-    adds into the slots' word 9 alone; x is required as for distortion."""
+    adds into the slots' word 9 alone; x is required as for distortion.
+    camera_model: the checked CameraModel of the forward (include/gsr_camera_model.h), or None; not with cam."""
     if distortion is not None and x is None:
         raise RuntimeError("run_backward: the distortion map's backward needs the depth-and-alpha kernels (x is None)")
     if median is not None and x is None:
@@ -505,7 +592,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     aa = opacities is not None
     if aa and not isinstance(opacities, int):
         opacities = _ptr(_dev_f32(opacities, device, "opacities"))
-    gaussians, lead = _entry(L, "gaussians", x=x, aa=aa, opacities=opacities, cam=cam)
+    gaussians, lead = _entry(L, "gaussians", x=x, aa=aa, opacities=opacities, cam=cam, cm=camera_model_args(camera_model))
     for k, (first, count) in enumerate(((0, a.P),) if parts is None else parts):
         if before_part is not None:
             before_part(k)
@@ -516,7 +603,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
 
 
 def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None,
-                    features=None, distortion=None, median=None):
+                    features=None, distortion=None, median=None, cm=None):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -524,6 +611,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
     aa = aa_flag(antialiasing)
     if aa and opacities is None:
         raise RuntimeError(f"{who}: antialiasing=True needs the forward's opacities")
+    cm = camera_model(cm)
+    camera_model_excludes(cm, camera_flag(camera_grads))
     cam, cam_grads = None, ()
     L = lib()
     dev = means3D.device
@@ -556,7 +645,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
             if camera_flag(camera_grads):
                 cam, cam_grads = camera_backward_args(P, dev)
             ab = None if absgrad is None else absgrad_tensors(absgrad, P, dev)
-            if stats is None and not aa and aux is None and cam is None and ab is None and features is None:   # nothing but the reference's backward: one call for both stages
+            if stats is None and not aa and aux is None and cam is None and ab is None and features is None and cm is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
                                       _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
                                       _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), float(tan_fovx), float(tan_fovy),
@@ -577,7 +666,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                                      dL_dscale=dL_dscales, dL_drot=dL_drotations)
                 set_backward_stats(a, stats, P, dev)
                 run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
-                             absgrad=ab, features=features, distortion=distortion, median=median)
+                             absgrad=ab, features=features, distortion=distortion, median=median, camera_model=cm)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
@@ -589,7 +678,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
                                  debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False, absgrad=None,
-                                 features=None):
+                                 features=None, camera_model=None):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -608,31 +697,33 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 the pixels of |dL_p/dmean2D| per component, the second gets their norm added for the visible Gaussians
                 (include/gsr_absgrad.h)
       features  FeatureBackward(features, dL_dfeature_map): the feature map of features_forward() took part in the loss; its share
-                of the geometry gradients is in the eight results, dL/dfeatures is left in features.grad (include/gsr_features.h)"""
+                of the geometry gradients is in the eight results, dL/dfeatures is left in features.grad (include/gsr_features.h)
+      camera_model  the CameraModel of the forward (include/gsr_camera_model.h); not with camera_grads"""
     return _backward_plain("rasterize_gaussians_backward", None,
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads, absgrad,
-                           features)
+                           features, cm=camera_model)
 
 
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
                                              cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh,
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
-                                             camera_grads=False, absgrad=None, features=None, distortion=None, median=None):
+                                             camera_grads=False, absgrad=None, features=None, distortion=None, median=None,
+                                             camera_model=None):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
     precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad /
     features: as there.  distortion: DistortionBackward(state, dL_ddistortion) when the map of distortion_forward() took part in
     the loss; its share is in the eight results, dL/dv chained to dL_dmeans3D (include/gsr_distortion.h).  median:
     MedianBackward(state, dL_dmedian_depth) when the median-depth map of median_forward() did; its dL/dv is chained the same way
-    (include/gsr_median.h)."""
+    (include/gsr_median.h).  camera_model: as there."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features,
-                           distortion, median)
+                           distortion, median, camera_model)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------

@@ -22,15 +22,16 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
-                        camera_grads=False, absgrad=None, features=None, index_maps=None):
+                        camera_grads=False, absgrad=None, features=None, index_maps=None, camera_model=None):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
-    statistics, the camera gradients, the absolute gradients, the feature channels and the per-pixel index maps, see
-    GaussianRasterizer)"""
+    statistics, the camera gradients, the absolute gradients, the feature channels, the per-pixel index maps and the camera model,
+    see GaussianRasterizer)"""
     if index_maps is not None:
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), index_maps=index_maps)
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads, camera_model),
+                  index_maps=index_maps)
 
 
 def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=None):
@@ -47,10 +48,16 @@ def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=N
     return _RasterizeGaussiansFeatures.apply(features, *inputs)
 
 
-def camera_inputs(raster_settings, camera_grads):
-    """camera_grads=True: the three camera tensors of the settings, which the autograd Functions then take as three more inputs behind
-    their own; False: none.  Anything but a bool raises TypeError."""
-    if not _C.camera_flag(camera_grads):
+def camera_inputs(raster_settings, camera_grads, camera_model=None):
+    """What the autograd Functions take behind their own inputs.  camera_grads=True: the three camera tensors of the settings; a
+    camera model: the checked CameraModel alone (one input that is no tensor); neither: nothing, so a call without either is the call
+    it always was.  Anything but a bool raises TypeError; a bad camera model TypeError or ValueError (_C.camera_model); both together
+    NotImplementedError."""
+    cm = _C.camera_model(camera_model)
+    _C.camera_model_excludes(cm, _C.camera_flag(camera_grads))
+    if cm is not None:
+        return (cm,)
+    if not camera_grads:
         return ()
     return (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
 
@@ -63,7 +70,7 @@ def camera_grad_results(needs, grads, inputs):
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
                                     contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None, distortion=False,
-                                    median_depth=False, index_maps=None):
+                                    median_depth=False, index_maps=None, camera_model=None):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, distortion (1,H,W)]
     [, median_depth (1,H,W)][, feature_map])"""
     _C.aux_mode(depth_alpha)
@@ -73,8 +80,8 @@ def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacit
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads), distortion=distortion,
-                  median_depth=median_depth, index_maps=index_maps)
+                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads, camera_model),
+                  distortion=distortion, median_depth=median_depth, index_maps=index_maps)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -98,7 +105,11 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     Median depth and index maps (include/gsr_median.h): _RasterizeGaussiansMedian below runs this forward with _median and / or
     _index_maps: one launch after the render writes the caller's index tensors in place and, with _median=True, returns the
-    median-depth map behind the distortion map's place and saves its state behind the distortion state; the same holds for it."""
+    median-depth map behind the distortion map's place and saves its state behind the distortion state; the same holds for it.
+
+    Camera model (include/gsr_camera_model.h): a checked CameraModel as the ONE input behind the others (camera_inputs(); never
+    together with the three camera tensors) selects the camera-model kernels of the two per-Gaussian stages; the gradient tuple
+    grows by a None."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -140,6 +151,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         )
         # the screen-space filter (include/gsr_aa.h): a keyword of the binding, so the debug snapshot holds the same tuple
         kw = {"antialiasing": True} if antialiasing else {}
+        camera_model = camera[0] if len(camera) == 1 else None   # (include/gsr_camera_model.h): a keyword of the binding too
+        if camera_model is not None:
+            kw["camera_model"] = camera_model
         maps = ()
         if depth_alpha is not None:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *maps = \
@@ -195,6 +209,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.antialiasing = antialiasing
         ctx.depth_alpha = depth_alpha
         ctx.camera = len(camera) == 3
+        ctx.camera_model = camera_model
         ctx.absgrad = absgrad
         # after the reference's ten: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the
         # opacity input that the anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
@@ -218,7 +233,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, *extra) = ctx.saved_tensors
         off = ctx.lead
-        n_in = 15 + (3 if ctx.camera else 0)
+        n_in = 15 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0)
         fb = None
         if ctx.features:
             features, extra = extra[0], extra[1:]
@@ -247,6 +262,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             kw["features"] = fb
         if ctx.absgrad is not None:
             kw["absgrad"] = ctx.absgrad
+        if ctx.camera_model is not None:
+            kw["camera_model"] = ctx.camera_model
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
@@ -317,6 +334,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
             *cam_grads,
+            *((None,) if ctx.camera_model is not None else ()),
         )
 
 
@@ -377,6 +395,9 @@ class _RasterizeGaussiansMedian(torch.autograd.Function):
         grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, g[0] if g else None,
                                                                 grad_distortion, grad_median)
         return (grad_features, None, None, None, *rest)
+
+
+CameraModel = _C.CameraModel   # (model, fx, fy, cx, cy): the `camera_model` keyword, see GaussianRasterizer
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -473,10 +494,27 @@ class GaussianRasterizer(nn.Module):
     blends, and that weight with the forward's bits (0 there).  The per-pixel answer to the question contrib_stats answers per
     Gaussian: picking, lifting 2-D masks to Gaussians, keyframe bookkeeping.  The returned tuple is unchanged; no gradients.  Together
     with median_depth one launch serves both.  Anything but a 3-tuple raises TypeError, wrong tensors ValueError, before anything
-    runs.  Out of scope (NotImplementedError): the view-parallel paths."""
+    runs.  Out of scope (NotImplementedError): the view-parallel paths.
+
+    camera_model (extension, default None): a CameraModel(model, fx, fy, cx, cy), or the same five values as a plain tuple -- model
+    "pinhole" (intrinsics with an off-centre principal point, as COLMAP, TUM, Replica and ScanNet calibrations have) or "fisheye"
+    (equidistant, r = f theta, no distortion coefficients); fx, fy in pixels; cx, cy in pixels with the origin at the corner of the
+    first pixel and pixel centres at +0.5 (OpenCV / COLMAP).  The default camera is CameraModel("pinhole", W / (2 tanfovx),
+    H / (2 tanfovy), W / 2, H / 2).  With a model, viewmatrix, campos, bg, sh_degree, scale_modifier, image_width, image_height,
+    prefiltered and debug of the settings keep their meaning; projmatrix, tanfovx and tanfovy are IGNORED.  The near plane
+    (view z <= 0.2), the depth order, the depth values of depth_alpha and the SH direction are unchanged; the pinhole's EWA guard
+    band follows the principal point (t.x / t.z clamped to [-(cx / fx + 0.3 W / (2 fx)), (W - cx) / fx + 0.3 W / (2 fx)], the default
+    path's +-1.3 tanfov at the default intrinsics), the fisheye has the full 2x3 Jacobian and no band (include/gsr_camera_model.h).
+    radii, means2D.grad (same units, so densify_stats and absgrad thresholds carry over) and every optional output keep their
+    contracts.  No gradients w.r.t. the intrinsics.  Anything but a CameraModel / 5-tuple raises TypeError, an unknown model string
+    or a focal length that is not finite and positive ValueError.  Out of scope (NotImplementedError, before anything runs):
+    camera_grads=True (its terms differentiate projmatrix) and the view-parallel paths.  fused_geometry.depth_normals and
+    normal_consistency_loss still assume the centred pinhole of tanfovx / tanfovy.  With None every call is what it was without the
+    keyword, bit for bit."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
-                 contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None):
+                 contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None,
+                 camera_model=None):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
@@ -488,6 +526,9 @@ class GaussianRasterizer(nn.Module):
         self.index_maps = index_maps
         self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
         self.camera_grads = _C.camera_flag(camera_grads)   # the same
+        # TypeError for anything but a CameraModel / 5-tuple, ValueError for bad values, NotImplementedError with camera_grads
+        self.camera_model = _C.camera_model(camera_model)
+        _C.camera_model_excludes(self.camera_model, self.camera_grads)
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
         self.depth_alpha = depth_alpha
@@ -530,7 +571,9 @@ class GaussianRasterizer(nn.Module):
             return rasterize_gaussians_depth_alpha(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
                                                    self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
-                                                   self.absgrad, features, self.distortion, self.median_depth, self.index_maps)
+                                                   self.absgrad, features, self.distortion, self.median_depth, self.index_maps,
+                                                   self.camera_model)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
-                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad, features, self.index_maps)
+                                   self.contrib_pixel_weight, self.camera_grads, self.absgrad, features, self.index_maps,
+                                   self.camera_model)

@@ -30,7 +30,7 @@ class AdamGroup(ctypes.Structure):
                 ("lr", _d), ("row", ctypes.c_int32)]
 
 
-def _leaf_forward(mode, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing):
+def _leaf_forward(mode, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing, camera_model=None):
     st = raster_settings
     P = int(xyz.size(0))
     M = 1 + (int(features_rest.size(1)) if features_rest.numel() else 0)
@@ -41,7 +41,8 @@ def _leaf_forward(mode, xyz, features_dc, features_rest, opacity, scaling, rotat
         True, mode, antialiasing, st.bg,
         ((xyz, "xyz"), (features_dc, "features_dc"), (features_rest, "features_rest"), (opacity, "opacity"), (scaling, "scaling"),
          (rotation, "rotation"), (st.viewmatrix, "viewmatrix"), (st.projmatrix, "projmatrix"), (st.campos, "campos")),
-        st.sh_degree, M, st.image_width, st.image_height, st.scale_modifier, st.tanfovx, st.tanfovy, st.prefiltered, st.debug)
+        st.sh_degree, M, st.image_width, st.image_height, st.scale_modifier, st.tanfovx, st.tanfovy, st.prefiltered, st.debug,
+        _C.camera_model(camera_model))
     return (R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps)
 
 
@@ -97,7 +98,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             _C.absgrad_tensors(absgrad, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps = _leaf_forward(
             None if depth_alpha is None else _C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation,
-            raster_settings, antialiasing)
+            raster_settings, antialiasing, camera[0] if len(camera) == 1 else None)
         if contrib_stats is not None:   # the blend-weight statistics of this view (GaussianRasterizer): once per forward, never in backward
             _C.gaussian_contributions(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width, raster_settings.image_height,
                                       contrib_stats, contrib_pixel_weight, raster_settings.debug)
@@ -125,6 +126,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         ctx.antialiasing = antialiasing
         ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
+        ctx.camera_model = camera[0] if len(camera) == 1 else None   # or the one checked CameraModel (GaussianRasterizer, camera_model)
         # after the state: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the opacity logits
         # that the anti-aliased backward reads (the records hold sigmoid(logit) * rho), each saved on its path only
         ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
@@ -151,7 +153,8 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             if grad_features_map is not None and ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:]):
                 # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
                 return (_C.features_backward_only(geom, binning, img, R, int(xyz.size(0)), st.image_width, st.image_height, features,
-                                                  grad_features_map, st.debug), (None,) * (14 + (3 if ctx.camera else 0)))
+                                                  grad_features_map, st.debug),
+                        (None,) * (14 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0)))
             if grad_features_map is not None:   # (no gradient reached the map: the feature pass is skipped)
                 fb = _C.FeatureBackward(features, grad_features_map)
         if grad_color is None:
@@ -187,7 +190,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                     cam, outs = _C.camera_backward_args(P, dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
                                 absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb,
-                                distortion=db, median=mb)
+                                distortion=db, median=mb, camera_model=ctx.camera_model)
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
@@ -196,7 +199,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         if fb is not None:   # (no Gaussian: nothing ran)
             grad_features = fb.grad if fb.grad is not None else torch.zeros_like(fb.features)
         return grad_features, (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, None,
-                               *cam_grads)
+                               *cam_grads, *((None,) if ctx.camera_model is not None else ()))
 
 
 class _RasterizeLeafGaussiansFeatures(torch.autograd.Function):
@@ -252,7 +255,7 @@ class _RasterizeLeafGaussiansMedian(torch.autograd.Function):
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                              depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
-                             absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None):
+                             absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, camera_model=None):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -268,7 +271,9 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     (distortion=True): differentiable w.r.t. the leaves, xyz's depth included.
     median_depth: True (with depth_alpha) puts the median-depth map (1, H, W) behind alpha (and distortion), in front of the feature
     map, as GaussianRasterizer's (median_depth=True): differentiable w.r.t. xyz along the view z axis.
-    index_maps: (median_index, dominant_index, dominant_weight), overwritten in place by the forward, as GaussianRasterizer's."""
+    index_maps: (median_index, dominant_index, dominant_weight), overwritten in place by the forward, as GaussianRasterizer's.
+    camera_model: a CameraModel ("pinhole" with intrinsics or "fisheye"), as GaussianRasterizer's: the settings' projmatrix, tanfovx and
+    tanfovy are then ignored; not with camera_grads (NotImplementedError)."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
     distortion = _C.distortion_flag(distortion, depth_alpha)
@@ -276,7 +281,8 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     if index_maps is not None:
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     inputs = (xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats, depth_alpha,
-              _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads))
+              _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad,
+              *camera_inputs(raster_settings, camera_grads, camera_model))
     if features is not None:
         _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
     if median_depth or index_maps is not None:

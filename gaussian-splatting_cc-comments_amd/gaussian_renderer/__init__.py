@@ -83,7 +83,7 @@ def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
-           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False):
+           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False, camera_model=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -107,11 +107,20 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     normals (extension): True adds "normal" (3, H, W) to the dict, the blend sum_i n_i alpha_i T_i of the per-Gaussian view-space
     normals of fused_geometry.gaussian_normals(), differentiable (rotations through n_i, everything else through the weights): three
     more channels of the feature pass behind the caller's `features`, split off again -- "features" keeps exactly the caller's
-    channels; on both paths.  The input of fused_geometry.normal_consistency_loss()."""
+    channels; on both paths.  The input of fused_geometry.normal_consistency_loss().
+    camera_model (extension): a CameraModel ("pinhole" with intrinsics, or "fisheye") -- see GaussianRasterizer; None = the camera's own
+    `camera_model` attribute if it has one, else the centred pinhole of FoVx / FoVy.  With a model the camera's full_proj_transform,
+    FoVx and FoVy are ignored; on both paths; not with camera_grads.  The normal map of normals=True is the blend of per-Gaussian
+    normals and works with either model; fused_geometry.depth_normals() and normal_consistency_loss(), which the caller applies to the
+    result, still assume the centred pinhole."""
     from diff_gaussian_rasterization import _C
     _C.normals_flag(normals)   # a switch: anything but a bool is refused
+    if camera_model is None:
+        camera_model = getattr(viewpoint_camera, "camera_model", None)
     if camera_grads is None:
         camera_grads = getattr(pipe, "camera_grads", False)
+    camera_model = _C.camera_model(camera_model)   # refused before anything runs: a bad model, and a model with camera gradients
+    _C.camera_model_excludes(camera_model, camera_grads is True)
     if antialiasing is None:
         antialiasing = getattr(pipe, "antialiasing", False)
     xyz = pc.get_xyz
@@ -146,6 +155,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         extras["median_depth"] = median_depth
     if index_maps is not None:      # ... and the caller's index maps
         extras["index_maps"] = index_maps
+    if camera_model is not None:    # ... and the camera model (checked by either path before anything runs)
+        extras["camera_model"] = camera_model
 
     if leaf:
         from fused_params import rasterize_leaf_gaussians
