@@ -1018,8 +1018,11 @@ extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_a
 // aux: 0 or a GSR_AUX_* mode; aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h), NULL: the default ones
 // cam: NULL, or the camera gradients (include/gsr_cam.h; checked by the caller): the twin kernels, then the fold of their rows
 // cm: NULL, or a checked camera model (include/gsr_camera_model.h; never with cam): its twin kernels
+// camk: NULL, or the camera gradients under the model cm (include/gsr_cam_cm.h; checked by the caller, never with cam): the kernels
+//       that are both twins, then the fold of their rows
 static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities,
-                                       const gsr_cam_args* cam = nullptr, const gsr_camera_model* cm = nullptr)
+                                       const gsr_cam_args* cam = nullptr, const gsr_camera_model* cm = nullptr,
+                                       const gsr_cam_cm_args* camk = nullptr)
 {
 	g_err[0] = 0;
 	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
@@ -1030,13 +1033,16 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: bad range [%d, %d + %d) of %d Gaussians (first must be a multiple "
 		                "of 64, out_row0 must be 0 or first)", first, first, count, b.P);
 	hipStream_t s = (hipStream_t)b.stream;
-	if (cam && count == 0) {   // no Gaussian: the fold of no rows writes the 35 zeros
+	float* const cam_rows = cam ? (float*)cam->scratch : camk ? (float*)camk->scratch : nullptr;
+	auto fold = [&](int nrows) {   // the rows of the per-Gaussian pass into the outputs, structural zeros included
 		{
 			GsrProfScope p(s, "camera_grad");
-			gsr_launch_camera_grad_fold((const float*)cam->scratch, 0, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
+			if (cam) gsr_launch_camera_grad_fold(cam_rows, nrows, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
+			else gsr_launch_cam_cm_fold(cam_rows, nrows, camk->dL_dviewmatrix, camk->dL_dintrinsics, camk->dL_dcampos, s);
 		}
 		return gsr_stage_done(s, b.debug, "camera_grad");
-	}
+	};
+	if (cam_rows && count == 0) return fold(0);   // no Gaussian: the fold of no rows writes the zeros
 	if (count == 0) return GSR_OK;
 	GsrGaussianBackwardArgs a = {};
 	a.leaf = b.leaf; a.shs_rest = b.shs_rest; a.dL_dsh_rest = b.dL_dsh_rest;
@@ -1056,15 +1062,11 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
 	{
 		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam ? (float*)cam->scratch : nullptr, cm);
+		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam_rows, cm);
 	}
-	if (!cam) return gsr_stage_done(s, b.debug, "gaussian_backward");
+	if (!cam_rows) return gsr_stage_done(s, b.debug, "gaussian_backward");
 	if ((rc = gsr_stage_done(s, b.debug, "gaussian_backward"))) return rc;
-	{
-		GsrProfScope p(s, "camera_grad");
-		gsr_launch_camera_grad_fold((const float*)cam->scratch, (int)gsr_cam_rows(count), cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
-	}
-	return gsr_stage_done(s, b.debug, "camera_grad");
+	return fold((int)gsr_cam_rows(count));
 }
 
 extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
@@ -1127,6 +1129,34 @@ extern "C" int gsr_backward_gaussians_cam(const gsr_backward_args* args, int ant
 	if (args->P > 0 && args->shs && !args->cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
 	if (antialiasing && args->P > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
 	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, cam);
+}
+
+// ---- camera gradients under a camera model (include/gsr_cam_cm.h) ----
+extern "C" size_t gsr_cam_cm_bytes(int P) { return gsr_cam_bytes(P); }   // the same rows of 32 floats, one per wave
+
+extern "C" int gsr_backward_gaussians_cam_cm(const gsr_backward_args* args, const gsr_camera_model* model, int antialiasing,
+                                             const float* opacities, const gsr_aux_args* aux, const gsr_cam_cm_args* cam, int first, int count,
+                                             int out_row0)
+{
+	if (!cam) return gsr_backward_gaussians_cm(args, model, antialiasing, opacities, aux, first, count, out_row0);
+	const char* who = "gsr_backward_gaussians_cam_cm";
+	int rc;
+	if (!model) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the camera model is NULL (without one the camera gradients are gsr_backward_gaussians_cam's)", who);
+	if ((rc = gsr_camera_model_check(who, *model))) return rc;
+	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	if (args->P < 0 || args->num_rendered < 0 || args->width <= 0 || args->height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (!cam->dL_dviewmatrix || !cam->dL_dintrinsics || !cam->dL_dcampos)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dviewmatrix, dL_dintrinsics or dL_dcampos is NULL", who);
+	if (!cam->scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam is NULL", who);
+	if (!aligned16(cam->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam must be 16-byte aligned", who);
+	if (first != 0 || count != args->P)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera gradients need the whole scene in one call (first 0, count %d; got %d, %d): "
+		                "the part-by-part pipeline of view-parallel mode has no camera form", who, args->P, first, count);
+	if (args->P > 0 && !args->geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
+	if (args->P > 0 && args->shs && !args->cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
+	if (antialiasing && args->P > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, nullptr, model, cam);
 }
 
 static int gsr_backward_whole(const gsr_backward_args& a)

@@ -203,18 +203,22 @@ template <typename Base>
 struct GsrGaussianBackwardCam : Base {
 	float* cam_partials;   // [waves of the launch][GSR_CAM_ROW]
 };
-// CM: a camera model (include/gsr_camera_model.h; never together with CAM).  gsr_cm_cov2d recomputes the forward's values, the
+// CM: a camera model (include/gsr_camera_model.h).  gsr_cm_cov2d recomputes the forward's values, the
 // covariance chain also forms dL/dJ01 and dL/dJ10, and dL/dt -- from the six dL/dJ and from dL/dmean2D, which no longer goes through
 // the projection matrix -- comes from gsr_cm_backward (gsr_camera_model.h).  The arguments get the model behind them (GsrWithCameraModel).
+// CAM && CM: the camera gradients under a model (include/gsr_cam_cm.h).  There is no projection matrix: the view rows take dL/dt as
+// gsr_cm_backward returns it (J^T (dL/du, dL/dv) included) and dL/dW from the model's own J (gsr_cm_jacobian), and the projection
+// rows' place is taken by one group of four, the intrinsics' terms (gsr_cm_intrinsics_grad).  The wave's row, in the same stride:
+//   [4 i + k] and [4 i + 3] as above, i < 3;  [12 ..16) = sum dL/d(fx, fy, cx, cy);  [16 + k] = sum dL/dcampos[k], [19] = 0
+// gsr_camera_grad_fold_kernel<true> adds the rows.  The arguments are the model's with the row pointer behind them.
 #define GSR_GB_THREADS 64
 template <bool AA> using GsrGbArgs = typename std::conditional<AA, GsrGaussianBackwardArgsAA, GsrGaussianBackwardArgs>::type;
+template <bool AA, bool CM> using GsrGbModelArgs = typename std::conditional<CM, GsrWithCameraModel<GsrGbArgs<AA>>, GsrGbArgs<AA>>::type;
 template <bool LEAF, int AUX, bool AA, bool CAM, bool CM>
 __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
-	typename std::conditional<CAM, GsrGaussianBackwardCam<GsrGbArgs<AA>>,
-	                          typename std::conditional<CM, GsrWithCameraModel<GsrGbArgs<AA>>, GsrGbArgs<AA>>::type>::type a,
+	typename std::conditional<CAM, GsrGaussianBackwardCam<GsrGbModelArgs<AA, CM>>, GsrGbModelArgs<AA, CM>>::type a,
 	int sh_via_lds, int skip_dsh)
 {
-	static_assert(!(CAM && CM), "the camera gradients differentiate the projection matrix: no camera-model form");
 	// staging of the dL/dsh output block: rows of 13 float4; the packed layout goes out in two halves of 32 rows
 	// (6.6 KB per wave), the split leaf tensors as one linear 12 KB block
 	__shared__ float4 s_sh[GSR_GB_THREADS / 64][(LEAF ? 64 : 32) * GSR_SH_ROW4];
@@ -352,6 +356,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 	// row, the three row factors of dL/dprojmatrix, and dL/d(mean - campos)
 	float cam_dt[3] = {0.f, 0.f, 0.f}, cam_dW[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 	float cam_p[3] = {0.f, 0.f, 0.f}, cam_dm[3] = {0.f, 0.f, 0.f};
+	[[maybe_unused]] float cam_k[4] = {0.f, 0.f, 0.f, 0.f};   // CAM && CM: the terms of dL/d(fx, fy, cx, cy) in the projection rows' place
 
 	if (visible) {
 		// ---- computeCov2DCUDA, backward.cu:144-277 ----
@@ -434,6 +439,20 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 			// dL/dmean2D is in the units of the core camera's NDC chain: 0.5 W dL/du, 0.5 H dL/dv
 			float dt[3];
 			gsr_cm_backward(a.cm_model, h_x, h_y, c2, cm_e, dJ, dmean2D[0] / (0.5f * (float)a.W), dmean2D[1] / (0.5f * (float)a.H), dt);
+			if constexpr (CAM) {
+				// the other half of the product rules: t = V mean, T = W J with J as gsr_cm_cov2d formed it, and the model's own parameters
+				cam_dt[0] = dt[0]; cam_dt[1] = dt[1]; cam_dt[2] = dt[2];
+				if (AUX) {
+					const float dv = acc[NACC - 1];
+					cam_dt[2] += AUX == GSR_AUX_INVDEPTH ? -dv / (t.z * t.z) : dv;
+				}
+				float J[6];
+				gsr_cm_jacobian(a.cm_model, h_x, h_y, c2, cm_e, J);
+				cam_dW[0] = J[0] * dL_dT00 + J[3] * dL_dT10; cam_dW[1] = J[0] * dL_dT01 + J[3] * dL_dT11; cam_dW[2] = J[0] * dL_dT02 + J[3] * dL_dT12;
+				cam_dW[3] = J[1] * dL_dT00 + J[4] * dL_dT10; cam_dW[4] = J[1] * dL_dT01 + J[4] * dL_dT11; cam_dW[5] = J[1] * dL_dT02 + J[4] * dL_dT12;
+				cam_dW[6] = J[2] * dL_dT00 + J[5] * dL_dT10; cam_dW[7] = J[2] * dL_dT01 + J[5] * dL_dT11; cam_dW[8] = J[2] * dL_dT02 + J[5] * dL_dT12;
+				gsr_cm_intrinsics_grad(a.cm_model, c2, cm_e, dJ, dmean2D[0] / (0.5f * (float)a.W), dmean2D[1] / (0.5f * (float)a.H), cam_k);
+			}
 			dmean3D[0] = vm[0] * dt[0] + vm[1] * dt[1] + vm[2] * dt[2];
 			dmean3D[1] = vm[4] * dt[0] + vm[5] * dt[1] + vm[6] * dt[2];
 			dmean3D[2] = vm[8] * dt[0] + vm[9] * dt[1] + vm[10] * dt[2];
@@ -466,7 +485,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 			dmean3D[1] += dz * vm[6];
 			dmean3D[2] += dz * vm[10];
 		}
-		if constexpr (CAM) {
+		if constexpr (CAM && !CM) {
 			// the other half of the product rules above: t = V mean, T = W J (J's entries as gsr_cov2d forms them), p_hom = P mean
 			const float J00 = h_x / t.z, J11 = h_y / t.z;
 			const float J02 = -(h_x * t.x) / (t.z * t.z), J12 = -(h_y * t.y) / (t.z * t.z);
@@ -498,13 +517,21 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 			const float v3 = gsr_wave_sum_to_lane63(cam_dt[i]);
 			if (lane == 63) row[i] = make_float4(v0, v1, v2, v3);
 		}
+		if constexpr (CM) {   // the intrinsics (fx, fy, cx, cy)
+			const float v0 = gsr_wave_sum_to_lane63(cam_k[0]);
+			const float v1 = gsr_wave_sum_to_lane63(cam_k[1]);
+			const float v2 = gsr_wave_sum_to_lane63(cam_k[2]);
+			const float v3 = gsr_wave_sum_to_lane63(cam_k[3]);
+			if (lane == 63) row[3] = make_float4(v0, v1, v2, v3);
+		} else {
 #pragma unroll
-		for (int j = 0; j < 3; j++) {   // rows 0, 1 and 3 of the projection matrix
-			const float v0 = gsr_wave_sum_to_lane63(cam_p[j] * mx);
-			const float v1 = gsr_wave_sum_to_lane63(cam_p[j] * my);
-			const float v2 = gsr_wave_sum_to_lane63(cam_p[j] * mz);
-			const float v3 = gsr_wave_sum_to_lane63(cam_p[j]);
-			if (lane == 63) row[3 + j] = make_float4(v0, v1, v2, v3);
+			for (int j = 0; j < 3; j++) {   // rows 0, 1 and 3 of the projection matrix
+				const float v0 = gsr_wave_sum_to_lane63(cam_p[j] * mx);
+				const float v1 = gsr_wave_sum_to_lane63(cam_p[j] * my);
+				const float v2 = gsr_wave_sum_to_lane63(cam_p[j] * mz);
+				const float v3 = gsr_wave_sum_to_lane63(cam_p[j]);
+				if (lane == 63) row[3 + j] = make_float4(v0, v1, v2, v3);
+			}
 		}
 		if (visible) {   // (reopened: SH, covariance and leaf backward of the visible lanes)
 #include "gaussian_backward_tail.inc"
@@ -513,7 +540,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 			const float v0 = gsr_wave_sum_to_lane63(-cam_dm[0]);
 			const float v1 = gsr_wave_sum_to_lane63(-cam_dm[1]);
 			const float v2 = gsr_wave_sum_to_lane63(-cam_dm[2]);
-			if (lane == 63) row[6] = make_float4(v0, v1, v2, 0.f);
+			if (lane == 63) row[CM ? 4 : 6] = make_float4(v0, v1, v2, 0.f);
 		}
 	}
 
@@ -608,6 +635,14 @@ static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux
 	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
 	const dim3 grid((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS);
 	gsr_variant(a.leaf, aux, AA, [&](auto LEAF, auto AUX, auto) {
+		if (cam_partials && cm) {   // camera gradients under a model (include/gsr_cam_cm.h): the model's arguments with the row pointer behind them
+			GsrGaussianBackwardCam<GsrWithCameraModel<Args>> c;
+			static_cast<Args&>(c) = a;
+			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
+			c.cam_partials = cam_partials;
+			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
+			return;
+		}
 		if (cam_partials) {   // the camera-gradient twin (include/gsr_cam.h): the same arguments with the row pointer behind them
 			GsrGaussianBackwardCam<Args> c;
 			static_cast<Args&>(c) = a;
@@ -645,11 +680,15 @@ void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float*
 // as a balanced tree and writes the column's four outputs -- and, in the first workgroup of each matrix, that matrix's four exact zeros.
 #define GSR_CAM_FOLD_THREADS 1024
 #define GSR_CAM_FOLD_GROUPS 7
+#define GSR_CAM_CM_FOLD_GROUPS 5
 __device__ __forceinline__ float4 gsr_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
+// CM: the fold of the camera-model rows (include/gsr_cam_cm.h): the same summation with a second output map -- five columns, the
+// intrinsics (fx, fy, cx, cy) in the projection rows' place (dL_dmid), campos behind them.
+template <bool CM>
 __global__ void __launch_bounds__(GSR_CAM_FOLD_THREADS) gsr_camera_grad_fold_kernel(const float4* __restrict__ partials, int nrows,
                                                                                   float* __restrict__ dL_dviewmatrix,
-                                                                                  float* __restrict__ dL_dprojmatrix,
+                                                                                  float* __restrict__ dL_dmid,
                                                                                   float* __restrict__ dL_dcampos)
 {
 	__shared__ float4 s_wave[GSR_CAM_FOLD_THREADS / 64];
@@ -684,10 +723,16 @@ __global__ void __launch_bounds__(GSR_CAM_FOLD_THREADS) gsr_camera_grad_fold_ker
 	if (col < 3) {          // row `col` of the view matrix
 		dL_dviewmatrix[col] = v.x; dL_dviewmatrix[4 + col] = v.y; dL_dviewmatrix[8 + col] = v.z; dL_dviewmatrix[12 + col] = v.w;
 		if (col == 0) { dL_dviewmatrix[3] = 0.f; dL_dviewmatrix[7] = 0.f; dL_dviewmatrix[11] = 0.f; dL_dviewmatrix[15] = 0.f; }
+	} else if constexpr (CM) {
+		if (col == 3) {     // fx, fy, cx, cy
+			dL_dmid[0] = v.x; dL_dmid[1] = v.y; dL_dmid[2] = v.z; dL_dmid[3] = v.w;
+		} else {
+			dL_dcampos[0] = v.x; dL_dcampos[1] = v.y; dL_dcampos[2] = v.z;
+		}
 	} else if (col < 6) {   // rows 0, 1 and 3 of the projection matrix
 		const int rr = col == 5 ? 3 : col - 3;
-		dL_dprojmatrix[rr] = v.x; dL_dprojmatrix[4 + rr] = v.y; dL_dprojmatrix[8 + rr] = v.z; dL_dprojmatrix[12 + rr] = v.w;
-		if (col == 3) { dL_dprojmatrix[2] = 0.f; dL_dprojmatrix[6] = 0.f; dL_dprojmatrix[10] = 0.f; dL_dprojmatrix[14] = 0.f; }
+		dL_dmid[rr] = v.x; dL_dmid[4 + rr] = v.y; dL_dmid[8 + rr] = v.z; dL_dmid[12 + rr] = v.w;
+		if (col == 3) { dL_dmid[2] = 0.f; dL_dmid[6] = 0.f; dL_dmid[10] = 0.f; dL_dmid[14] = 0.f; }
 	} else {
 		dL_dcampos[0] = v.x; dL_dcampos[1] = v.y; dL_dcampos[2] = v.z;
 	}
@@ -697,8 +742,14 @@ size_t gsr_cam_rows(int P) { return ((size_t)(P > 0 ? P : 0) + 63) / 64; }
 
 void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s)
 {
-	gsr_launch(gsr_camera_grad_fold_kernel, dim3(GSR_CAM_FOLD_GROUPS), dim3(GSR_CAM_FOLD_THREADS), 0, s, nullptr, nullptr,
+	gsr_launch(gsr_camera_grad_fold_kernel<false>, dim3(GSR_CAM_FOLD_GROUPS), dim3(GSR_CAM_FOLD_THREADS), 0, s, nullptr, nullptr,
 	           reinterpret_cast<const float4*>(partials), nrows, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos);
+}
+
+void gsr_launch_cam_cm_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dintrinsics, float* dL_dcampos, hipStream_t s)
+{
+	gsr_launch(gsr_camera_grad_fold_kernel<true>, dim3(GSR_CAM_CM_FOLD_GROUPS), dim3(GSR_CAM_FOLD_THREADS), 0, s, nullptr, nullptr,
+	           reinterpret_cast<const float4*>(partials), nrows, dL_dviewmatrix, dL_dintrinsics, dL_dcampos);
 }
 
 // ---- view-parallel SH gradient (no reference counterpart) ------------------------------

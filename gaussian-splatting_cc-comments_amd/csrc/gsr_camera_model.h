@@ -172,3 +172,47 @@ __device__ __forceinline__ void gsr_cm_backward(int model, float fx, float fy, c
 		        ((fx * x) * tz2 * du + (fy * y) * tz2 * dv);
 	}
 }
+
+// ---- camera gradients under a model (include/gsr_cam_cm.h) ---------------------------------------------------------------------------
+// J[3 i + k] = d pixel_i / d t_k exactly as gsr_cm_cov2d formed it (the same expressions on the same values: the same bits), for the
+// rotation half of T = W J: dL/dW[i][k] = J[0][i] dL/dT0k + J[1][i] dL/dT1k.  Pinhole: J01 = J10 = 0, J02 / J12 from the clamped coordinate.
+__device__ __forceinline__ void gsr_cm_jacobian(int model, float fx, float fy, const GsrCov2D& c2, const GsrCmExtra& e, float* J)
+{
+	if (model == GSR_CAMERA_FISHEYE) {
+		const GsrFisheye& f = e.f;
+		const float x = e.traw.x, y = e.traw.y;
+		const float xyA = x * y * f.A;
+		J[0] = fx * (f.s + x * x * f.A); J[1] = fx * xyA; J[2] = -(fx * x) * f.id2;
+		J[3] = fy * xyA; J[4] = fy * (f.s + y * y * f.A); J[5] = -(fy * y) * f.id2;
+	} else {
+		const GsrVec3 t = c2.t;   // x and y clamped to the guard band
+		J[0] = fx / t.z; J[1] = 0.0f; J[2] = -(fx * t.x) / (t.z * t.z);
+		J[3] = 0.0f; J[4] = fy / t.z; J[5] = -(fy * t.y) / (t.z * t.z);
+	}
+}
+
+// dL/d(fx, fy, cx, cy) of one Gaussian from dL/dJ (dJ[3 i + k], as for gsr_cm_backward) and dL/d(u, v) in pixels.  Every entry of J's
+// row 0 is fx times a function of t alone, and u = fx (...) + cx - 0.5, so nothing is divided by fx:
+//   pinhole: dL/dfx = dJ00 / z - dJ02 x_c / z^2 + du x / z   (x_c the clamped coordinate, a constant; x the raw one; the band's limits
+//            carry no gradient with respect to fx and cx)
+//   fisheye: dL/dfx = dJ00 (s + x^2 A) + dJ01 x y A - dJ02 x / d2 + du s x   with the s, A, 1 / d2 gsr_cm_cov2d evaluated (the series
+//            near the axis serves here too)
+// fy likewise with row 1; dL/dcx = du, dL/dcy = dv.
+__device__ __forceinline__ void gsr_cm_intrinsics_grad(int model, const GsrCov2D& c2, const GsrCmExtra& e, const float* dJ, float du,
+                                                       float dv, float* dk)
+{
+	const float x = e.traw.x, y = e.traw.y, z = e.traw.z;
+	if (model == GSR_CAMERA_FISHEYE) {
+		const GsrFisheye& f = e.f;
+		const float xyA = x * y * f.A;
+		dk[0] = dJ[0] * (f.s + x * x * f.A) + dJ[1] * xyA - dJ[2] * x * f.id2 + du * (f.s * x);
+		dk[1] = dJ[3] * xyA + dJ[4] * (f.s + y * y * f.A) - dJ[5] * y * f.id2 + dv * (f.s * y);
+	} else {
+		const float tz = 1.f / z;
+		const float tz2 = tz * tz;
+		dk[0] = dJ[0] * tz - dJ[2] * c2.t.x * tz2 + du * (x * tz);
+		dk[1] = dJ[4] * tz - dJ[5] * c2.t.y * tz2 + dv * (y * tz);
+	}
+	dk[2] = du;
+	dk[3] = dv;
+}

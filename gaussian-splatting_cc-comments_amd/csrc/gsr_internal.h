@@ -12,6 +12,7 @@
 #include "../../include/gsr_cam.h"
 #include "../../include/gsr_absgrad.h"
 #include "../../include/gsr_camera_model.h"
+#include "../../include/gsr_cam_cm.h"
 #include "gsr_device.h"
 
 #define GSR_PREPROCESS_BLOCK 256  // Gaussians per workgroup of the binning kernels (granularity of their scans)
@@ -337,11 +338,13 @@ struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
 // dL/dcov3D and dL/dmean3D
 // cam_partials: NULL, or the camera-gradient kernels (include/gsr_cam.h), which also store one row of 32 floats per wave of 64
 // Gaussians there (gsr_cam_rows(count) rows; first must be 0); gsr_launch_camera_grad_fold adds the rows into the 35 outputs
-// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h; never with cam_partials), with a.focal_x / a.focal_y = fx, fy
+// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h), with a.focal_x / a.focal_y = fx, fy.  With cam_partials too: the
+// camera gradients under a model (include/gsr_cam_cm.h), whose rows gsr_launch_cam_cm_fold adds into the 16 + 4 + 3 outputs
 void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials = nullptr,
                                   const gsr_camera_model* cm = nullptr);
 size_t gsr_cam_rows(int P);
 void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s);
+void gsr_launch_cam_cm_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dintrinsics, float* dL_dcampos, hipStream_t s);
 void gsr_launch_sh_grad_from_views(int P, int D, int M, int V, const float* means3D, const float* cam_pos, const float* dL_dRGB,
                                    int64_t view_stride, float* dL_dsh, hipStream_t s);
 

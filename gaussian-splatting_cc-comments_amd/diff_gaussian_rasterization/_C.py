@@ -71,6 +71,11 @@ class CamArgs(ctypes.Structure):
     _fields_ = [("dL_dviewmatrix", _vp), ("dL_dprojmatrix", _vp), ("dL_dcampos", _vp), ("scratch", _vp)]
 
 
+class CamCmArgs(ctypes.Structure):
+    """include/gsr_cam_cm.h gsr_cam_cm_args"""
+    _fields_ = [("dL_dviewmatrix", _vp), ("dL_dintrinsics", _vp), ("dL_dcampos", _vp), ("scratch", _vp)]
+
+
 class AbsgradArgs(ctypes.Structure):
     """include/gsr_absgrad.h gsr_absgrad_args"""
     _fields_ = [("abs_dL_dmean2D", _vp), ("stat_abs_gradient_accum", _vp)]
@@ -94,6 +99,15 @@ class CameraModel(NamedTuple):
     fy: float
     cx: float
     cy: float
+
+    @classmethod
+    def from_tensor(cls, model, intrinsics):
+        """The CameraModel whose floats are the values of `intrinsics`, a (4,) tensor (fx, fy, cx, cy) -- the tensor that
+        `camera_model_grads=` takes as the autograd handle of the intrinsics.  One read-back from the device: the kernels take the
+        model's floats as arguments, so an optimiser step on the tensor is followed by this call."""
+        if not isinstance(intrinsics, torch.Tensor) or tuple(intrinsics.shape) != (4,):
+            raise ValueError(f"intrinsics must be a tensor of shape (4,) holding (fx, fy, cx, cy), got {intrinsics!r}")
+        return camera_model((model, *(float(v) for v in intrinsics.detach().to(torch.float32).cpu().tolist())))
 
 
 class AuxLayout(ctypes.Structure):
@@ -257,6 +271,12 @@ def lib():
                                ("gsr_backward_gaussians_cm", [pb, pm, _i, _vp, pa, _i, _i, _i])):
             getattr(L, name).restype = _i
             getattr(L, name).argtypes = argtypes
+    # include/gsr_cam_cm.h: camera gradients under a camera model (the same holds for an older library)
+    if hasattr(L, "gsr_backward_gaussians_cam_cm"):
+        L.gsr_cam_cm_bytes.restype = _sz
+        L.gsr_cam_cm_bytes.argtypes = [_i]
+        L.gsr_backward_gaussians_cam_cm.restype = _i
+        L.gsr_backward_gaussians_cam_cm.argtypes = [pb, ctypes.POINTER(CameraModelArgs), _i, _vp, pa, ctypes.POINTER(CamCmArgs), _i, _i, _i]
     _lib = L
     return L
 
@@ -352,7 +372,42 @@ def camera_model_excludes(cm, camera_grads=False, what=None):
         raise NotImplementedError(f"{what} has no camera_model form")
     if camera_grads is True:
         raise NotImplementedError("camera_grads=True has no camera_model form: the camera gradients differentiate projmatrix, "
-                                  "which a camera model ignores")
+                                  "which a camera model ignores; camera_model_grads=True gives dL/dviewmatrix, dL/dcampos and "
+                                  "dL/dintrinsics under a model")
+
+
+def camera_model_grads_arg(value, cm, device=None):
+    """Checks the `camera_model_grads` keyword against the checked CameraModel `cm` (or None) -> False, True, or the intrinsics tensor.
+    False: nothing.  True: the settings' viewmatrix and campos become autograd inputs behind the model (include/gsr_cam_cm.h).  A
+    float32 (4,) HIP tensor: as True, and the tensor is the autograd handle of (fx, fy, cx, cy): it receives dL/dintrinsics; its
+    values are not read (CameraModel.from_tensor builds the model from it).  Anything but a bool or a tensor raises TypeError; a
+    wrong dtype, shape or device, and True or a tensor without a camera model, ValueError.  No library is touched."""
+    if isinstance(value, bool):
+        if value and cm is None:
+            raise ValueError("camera_model_grads=True needs a camera_model (without one, camera_grads=True gives dL/dviewmatrix, "
+                             "dL/dprojmatrix and dL/dcampos)")
+        return value
+    if not isinstance(value, torch.Tensor):
+        raise TypeError(f"camera_model_grads must be True, False or a float32 (4,) tensor (fx, fy, cx, cy), got {value!r}")
+    if cm is None:
+        raise ValueError("camera_model_grads needs a camera_model: the tensor is the autograd handle of that model's intrinsics")
+    if value.dtype != torch.float32:
+        raise ValueError(f"camera_model_grads: the intrinsics tensor must be float32 (got {value.dtype})")
+    if tuple(value.shape) != (4,):
+        raise ValueError(f"camera_model_grads: the intrinsics tensor must have shape (4,) = (fx, fy, cx, cy), got {tuple(value.shape)}")
+    if not value.is_cuda or (device is not None and value.device != device):
+        raise ValueError(f"camera_model_grads: the intrinsics tensor must be on the render's HIP (cuda) device (got {value.device})")
+    return value
+
+
+def camera_model_matches(cm, intrinsics):
+    """settings.debug: the intrinsics tensor of `camera_model_grads` and the CameraModel the kernels read must hold the same float32
+    values (one read-back); ValueError otherwise."""
+    want = torch.tensor([cm.fx, cm.fy, cm.cx, cm.cy], dtype=torch.float32)
+    got = intrinsics.detach().to(torch.float32).cpu()
+    if not torch.equal(want, got):
+        raise ValueError(f"camera_model_grads: the intrinsics tensor {got.tolist()} differs from the camera_model's "
+                         f"(fx, fy, cx, cy) = {want.tolist()}; build the model with CameraModel.from_tensor(model, intrinsics)")
 
 
 def absgrad_tensors(absgrad, P, device=None):
@@ -399,6 +454,19 @@ def camera_backward_args(P, device):
     return c, outs
 
 
+def camera_cm_backward_args(P, device):
+    """CamCmArgs of a backward with camera gradients under a camera model (include/gsr_cam_cm.h) -> (struct, (dL_dviewmatrix (4,4),
+    dL_dintrinsics (4,), dL_dcampos (3,))), as camera_backward_args()."""
+    f32 = dict(dtype=torch.float32, device=device)
+    outs = (torch.empty((4, 4), **f32), torch.empty((4,), **f32), torch.empty((3,), **f32))
+    scratch = torch.empty((lib().gsr_cam_cm_bytes(int(P)),), dtype=torch.uint8, device=device)
+    c = CamCmArgs()
+    c.dL_dviewmatrix, c.dL_dintrinsics, c.dL_dcampos = (t.data_ptr() for t in outs)
+    c.scratch = scratch.data_ptr()
+    c._keep = outs + (scratch,)
+    return c, outs
+
+
 # ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
 def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, absgrad=False, cm=None):
     """-> (function of L, the arguments that precede the default entry point's own).  stage: "preprocess" | "render" (the two forward
@@ -406,19 +474,22 @@ def _entry(L, stage, leaf=False, x=None, aa=False, opacities=None, cam=None, abs
     inputs are the optimiser's leaves (fused_params.py); x: the AuxArgs of a call with depth and alpha maps, or None; aa: the
     screen-space filter, whose per-Gaussian backward reads the forward's opacity input at address `opacities`.  The *_aa entry
     points take (antialiasing, aux or NULL, ...) and cover every other one; the older names stay in use where they suffice.
-    cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None.
+    cam: the CamArgs of a per-Gaussian backward that also produces the camera gradients (include/gsr_cam.h), or None; with cm, the
+    CamCmArgs of the camera gradients under that model (include/gsr_cam_cm.h).
     absgrad: the blend that also leaves the sums of per-pixel moduli in the slots (include/gsr_absgrad.h).
     cm: the CameraModelArgs of a call with a camera model (include/gsr_camera_model.h), or None: the *_cm entry points take the model in
     front of the *_aa arguments; the stages that only read the splat records have none."""
     xr = None if x is None else ctypes.byref(x)
-    if cm is not None and cam is not None:
-        raise NotImplementedError("camera gradients have no camera_model form")
+    if cm is not None and cam is not None and not isinstance(cam, CamCmArgs):
+        raise NotImplementedError("the camera gradients of include/gsr_cam.h have no camera_model form (include/gsr_cam_cm.h has)")
     if stage == "preprocess" and cm is not None:
         name = "gsr_forward_preprocess_leaf_cm" if leaf else "gsr_forward_preprocess_cm"
         lead = (ctypes.byref(cm), int(aa), xr)
     elif stage == "preprocess":
         name = "gsr_forward_preprocess_leaf" if leaf else "gsr_forward_preprocess"
         name, lead = (name + "_aa", (1, xr)) if aa else (name + "_aux", (xr,)) if x is not None else (name, ())
+    elif stage == "gaussians" and cm is not None and cam is not None:
+        name, lead = "gsr_backward_gaussians_cam_cm", (ctypes.byref(cm), int(aa), opacities if aa else None, xr, ctypes.byref(cam))
     elif stage == "gaussians" and cm is not None:
         name, lead = "gsr_backward_gaussians_cm", (ctypes.byref(cm), int(aa), opacities if aa else None, xr)
     elif stage == "gaussians" and cam is not None:
@@ -556,7 +627,8 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
     logits in leaf mode) when the screen-space filter was on, else None; before_part(k) / after_part(k): called around part k's pass
     (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_backward_args()) when
-    the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`.
+    the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`.  With
+    camera_model it is the CamCmArgs (camera_cm_backward_args()) of the camera gradients under that model.
     absgrad: AbsgradArgs (absgrad_tensors()) when the blend shall keep the per-pixel moduli of dL/dmean2D and a fold pass behind it
     shall overwrite abs_mean2D and add into abs_gradient_accum (include/gsr_absgrad.h); not with `parts` either.
     features: FeatureBackward (include/gsr_features.h) when a feature map took part in the loss: its pass runs between the blend (and
@@ -568,7 +640,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     kernels write and chain word 9.
     median: MedianBackward (include/gsr_median.h) when the median-depth map took part in the loss: its pass runs at the same place and
     adds into the slots' word 9 alone; x is required as for distortion.
-    camera_model: the checked CameraModel of the forward (include/gsr_camera_model.h), or None; not with cam."""
+    camera_model: the checked CameraModel of the forward (include/gsr_camera_model.h), or None."""
     if distortion is not None and x is None:
         raise RuntimeError("run_backward: the distortion map's backward needs the depth-and-alpha kernels (x is None)")
     if median is not None and x is None:
@@ -603,7 +675,7 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
 
 
 def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads=False, absgrad=None,
-                    features=None, distortion=None, median=None, cm=None):
+                    features=None, distortion=None, median=None, cm=None, camera_model_grads=False):
     """rasterize_gaussians_backward() / rasterize_gaussians_backward_depth_alpha(): args are the reference's 21 (rasterize_points.cu:
     132-153), aux is None or (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha)."""
     (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -613,6 +685,9 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
         raise RuntimeError(f"{who}: antialiasing=True needs the forward's opacities")
     cm = camera_model(cm)
     camera_model_excludes(cm, camera_flag(camera_grads))
+    if not isinstance(camera_model_grads, bool):
+        raise TypeError(f"{who}: camera_model_grads must be True or False here, got {camera_model_grads!r}")
+    cm_grads = camera_model_grads_arg(camera_model_grads, cm)
     cam, cam_grads = None, ()
     L = lib()
     dev = means3D.device
@@ -644,6 +719,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
             scratch = backward_scratch(P, R, dev)
             if camera_flag(camera_grads):
                 cam, cam_grads = camera_backward_args(P, dev)
+            elif cm_grads:
+                cam, cam_grads = camera_cm_backward_args(P, dev)
             ab = None if absgrad is None else absgrad_tensors(absgrad, P, dev)
             if stats is None and not aa and aux is None and cam is None and ab is None and features is None and cm is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
@@ -669,6 +746,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                              absgrad=ab, features=features, distortion=distortion, median=median, camera_model=cm)
         elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
             cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
+        elif cm_grads:
+            cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4,), **f32), torch.zeros((3,), **f32))
     if debug_out is not None:
         debug_out["dL_dconic"] = dL_dconic
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations) + tuple(cam_grads)
@@ -678,7 +757,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree,
                                  campos, geomBuffer, R, binningBuffer, imageBuffer, debug, *, lean=False, skip_sh=False,
                                  debug_out=None, stats=None, antialiasing=False, opacities=None, camera_grads=False, absgrad=None,
-                                 features=None, camera_model=None):
+                                 features=None, camera_model=None, camera_model_grads=False):
     """-> (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
 
     The 21 positional arguments and the tuple are the reference extension's.  Keyword-only extras (all per call,
@@ -698,12 +777,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 (include/gsr_absgrad.h)
       features  FeatureBackward(features, dL_dfeature_map): the feature map of features_forward() took part in the loss; its share
                 of the geometry gradients is in the eight results, dL/dfeatures is left in features.grad (include/gsr_features.h)
-      camera_model  the CameraModel of the forward (include/gsr_camera_model.h); not with camera_grads"""
+      camera_model  the CameraModel of the forward (include/gsr_camera_model.h); not with camera_grads (camera_model_grads below)
+      camera_model_grads  True (with camera_model): three more results behind the eight, dL_dviewmatrix (4,4), dL_dintrinsics (4,)
+                    = dL/d(fx, fy, cx, cy) and dL_dcampos (3,) (include/gsr_cam_cm.h)"""
     return _backward_plain("rasterize_gaussians_backward", None,
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), lean, skip_sh, debug_out, stats, antialiasing, opacities, camera_grads, absgrad,
-                           features, cm=camera_model)
+                           features, cm=camera_model, camera_model_grads=camera_model_grads)
 
 
 def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -711,19 +792,19 @@ def rasterize_gaussians_backward_depth_alpha(depth_alpha, background, means3D, r
                                              degree, campos, geomBuffer, R, binningBuffer, imageBuffer, auxBuffer, dL_ddepth,
                                              dL_dalpha, debug, *, stats=None, antialiasing=False, opacities=None,
                                              camera_grads=False, absgrad=None, features=None, distortion=None, median=None,
-                                             camera_model=None):
+                                             camera_model=None, camera_model_grads=False):
     """rasterize_gaussians_backward() of a rasterize_gaussians_depth_alpha() forward, with dL/dD and dL/dA (1,H,W) or None on
     top of dL/dpix -> the same eight gradients (the lean set: dL_dcolors only for precomputed colours, dL_dcov3D only for
     precomputed covariances, as rasterize_gaussians_backward(lean=True)).  antialiasing / opacities / camera_grads / absgrad /
     features: as there.  distortion: DistortionBackward(state, dL_ddistortion) when the map of distortion_forward() took part in
     the loss; its share is in the eight results, dL/dv chained to dL_dmeans3D (include/gsr_distortion.h).  median:
     MedianBackward(state, dL_dmedian_depth) when the median-depth map of median_forward() did; its dL/dv is chained the same way
-    (include/gsr_median.h).  camera_model: as there."""
+    (include/gsr_median.h).  camera_model, camera_model_grads: as there."""
     return _backward_plain("rasterize_gaussians_backward_depth_alpha", (depth_alpha, auxBuffer, dL_ddepth, dL_dalpha),
                            (background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                             projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos, geomBuffer, R, binningBuffer,
                             imageBuffer, debug), True, False, None, stats, antialiasing, opacities, camera_grads, absgrad, features,
-                           distortion, median, camera_model)
+                           distortion, median, camera_model, camera_model_grads)
 
 
 # ---- blend-weight statistics of a forward's state (include/gsr_contrib.h) -----------------------------------------------------------

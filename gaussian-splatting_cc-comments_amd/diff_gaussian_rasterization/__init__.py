@@ -22,16 +22,17 @@ def cpu_deep_copy_tuple(input_tuple):
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, densify_stats=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None,
-                        camera_grads=False, absgrad=None, features=None, index_maps=None, camera_model=None):
+                        camera_grads=False, absgrad=None, features=None, index_maps=None, camera_model=None,
+                        camera_model_grads=False):
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
-    statistics, the camera gradients, the absolute gradients, the feature channels, the per-pixel index maps and the camera model,
-    see GaussianRasterizer)"""
+    statistics, the camera gradients, the absolute gradients, the feature channels, the per-pixel index maps, the camera model and
+    the camera gradients under it, see GaussianRasterizer)"""
     if index_maps is not None:
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads, camera_model),
-                  index_maps=index_maps)
+                  contrib_stats, contrib_pixel_weight, absgrad,
+                  *camera_inputs(raster_settings, camera_grads, camera_model, camera_model_grads), index_maps=index_maps)
 
 
 def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=None):
@@ -48,13 +49,17 @@ def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=N
     return _RasterizeGaussiansFeatures.apply(features, *inputs)
 
 
-def camera_inputs(raster_settings, camera_grads, camera_model=None):
+def camera_inputs(raster_settings, camera_grads, camera_model=None, camera_model_grads=False):
     """What the autograd Functions take behind their own inputs.  camera_grads=True: the three camera tensors of the settings; a
     camera model: the checked CameraModel alone (one input that is no tensor); neither: nothing, so a call without either is the call
     it always was.  Anything but a bool raises TypeError; a bad camera model TypeError or ValueError (_C.camera_model); both together
-    NotImplementedError."""
+    NotImplementedError.  A camera model with camera_model_grads (True or the intrinsics tensor, _C.camera_model_grads_arg): four
+    inputs, the model, the settings' viewmatrix and campos, and the intrinsics tensor or None."""
     cm = _C.camera_model(camera_model)
     _C.camera_model_excludes(cm, _C.camera_flag(camera_grads))
+    cmg = _C.camera_model_grads_arg(camera_model_grads, cm)
+    if cmg is not False:
+        return (cm, raster_settings.viewmatrix, raster_settings.campos, None if cmg is True else cmg)
     if cm is not None:
         return (cm,)
     if not camera_grads:
@@ -67,10 +72,18 @@ def camera_grad_results(needs, grads, inputs):
     return tuple(g.reshape(t.shape) if n else None for n, g, t in zip(needs, grads, inputs))
 
 
+def camera_model_grad_results(needs, grads, raster_settings):
+    """The gradients of the inputs (viewmatrix, campos, intrinsics) behind a CameraModel from a backward's (dL_dviewmatrix,
+    dL_dintrinsics, dL_dcampos), None where the input does not require one."""
+    dV, dK, dC = grads
+    return (dV.reshape(raster_settings.viewmatrix.shape) if needs[0] else None,
+            dC.reshape(raster_settings.campos.shape) if needs[1] else None, dK if needs[2] else None)
+
+
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                     raster_settings, depth_alpha, densify_stats=None, antialiasing=False, contrib_stats=None,
                                     contrib_pixel_weight=None, camera_grads=False, absgrad=None, features=None, distortion=False,
-                                    median_depth=False, index_maps=None, camera_model=None):
+                                    median_depth=False, index_maps=None, camera_model=None, camera_model_grads=False):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, distortion (1,H,W)]
     [, median_depth (1,H,W)][, feature_map])"""
     _C.aux_mode(depth_alpha)
@@ -80,7 +93,8 @@ def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacit
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                   cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                  contrib_stats, contrib_pixel_weight, absgrad, *camera_inputs(raster_settings, camera_grads, camera_model),
+                  contrib_stats, contrib_pixel_weight, absgrad,
+                  *camera_inputs(raster_settings, camera_grads, camera_model, camera_model_grads),
                   distortion=distortion, median_depth=median_depth, index_maps=index_maps)
 
 
@@ -109,7 +123,12 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     Camera model (include/gsr_camera_model.h): a checked CameraModel as the ONE input behind the others (camera_inputs(); never
     together with the three camera tensors) selects the camera-model kernels of the two per-Gaussian stages; the gradient tuple
-    grows by a None."""
+    grows by a None.
+
+    Camera gradients under a model (include/gsr_cam_cm.h): FOUR inputs behind the others -- the CameraModel, the settings'
+    viewmatrix and campos, and the intrinsics tensor (fx, fy, cx, cy) or None -- make the backward return dL/dviewmatrix, dL/dcampos
+    and dL/dintrinsics behind the model's None; the camera variant of the camera-model kernels runs when at least one of the three
+    requires a gradient, the plain camera-model kernels otherwise.  The kernels read the settings' tensors and the model's floats."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -151,9 +170,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         )
         # the screen-space filter (include/gsr_aa.h): a keyword of the binding, so the debug snapshot holds the same tuple
         kw = {"antialiasing": True} if antialiasing else {}
-        camera_model = camera[0] if len(camera) == 1 else None   # (include/gsr_camera_model.h): a keyword of the binding too
+        camera_model = camera[0] if len(camera) in (1, 4) else None   # (include/gsr_camera_model.h): a keyword of the binding too
         if camera_model is not None:
             kw["camera_model"] = camera_model
+        if len(camera) == 4 and camera[3] is not None and raster_settings.debug:   # the handle of the intrinsics and the model agree
+            _C.camera_model_matches(camera_model, camera[3])
         maps = ()
         if depth_alpha is not None:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *maps = \
@@ -210,6 +231,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.depth_alpha = depth_alpha
         ctx.camera = len(camera) == 3
         ctx.camera_model = camera_model
+        ctx.camera_cm = len(camera) == 4   # viewmatrix, campos and the intrinsics (or None) behind the model (include/gsr_cam_cm.h)
         ctx.absgrad = absgrad
         # after the reference's ten: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the
         # opacity input that the anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
@@ -233,7 +255,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer, *extra) = ctx.saved_tensors
         off = ctx.lead
-        n_in = 15 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0)
+        n_in = 15 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0) + (3 if ctx.camera_cm else 0)
         fb = None
         if ctx.features:
             features, extra = extra[0], extra[1:]
@@ -258,6 +280,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         cam_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera else ()
         if any(cam_needs):
             kw["camera_grads"] = True
+        cm_needs = tuple(ctx.needs_input_grad[16 + off:19 + off]) if ctx.camera_cm else ()
+        if any(cm_needs):
+            kw["camera_model_grads"] = True
         if fb is not None:
             kw["features"] = fb
         if ctx.absgrad is not None:
@@ -294,7 +319,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
             grads = _C.rasterize_gaussians_backward_depth_alpha(ctx.depth_alpha, *args[:-1], extra[0], hw(grad_depth), hw(grad_alpha),
                                                                 raster_settings.debug, stats=ctx.densify_stats, **kw, **kw_dist)
-        elif raster_settings.debug and ctx.depth_alpha is None and not any(cam_needs):  # reference __init__.py:141-148
+        elif raster_settings.debug and ctx.depth_alpha is None and not any(cam_needs) and not any(cm_needs):  # reference __init__.py:141-148
             cpu_args = cpu_deep_copy_tuple(args)
             try:
                 grads = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
@@ -312,6 +337,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         if ctx.camera:
             cam_grads = camera_grad_results(cam_needs, grads[8:], (raster_settings.viewmatrix, raster_settings.projmatrix,
                                                                    raster_settings.campos)) if any(cam_needs) else (None, None, None)
+        if ctx.camera_cm:
+            cam_grads = camera_model_grad_results(cm_needs, grads[8:], raster_settings) if any(cm_needs) else (None, None, None)
 
         # gradient order: reference __init__.py:154-164
         grad_features = None
@@ -333,8 +360,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
             None,
-            *cam_grads,
+            *(cam_grads if ctx.camera else ()),
             *((None,) if ctx.camera_model is not None else ()),
+            *(cam_grads if ctx.camera_cm else ()),
         )
 
 
@@ -506,15 +534,27 @@ class GaussianRasterizer(nn.Module):
     band follows the principal point (t.x / t.z clamped to [-(cx / fx + 0.3 W / (2 fx)), (W - cx) / fx + 0.3 W / (2 fx)], the default
     path's +-1.3 tanfov at the default intrinsics), the fisheye has the full 2x3 Jacobian and no band (include/gsr_camera_model.h).
     radii, means2D.grad (same units, so densify_stats and absgrad thresholds carry over) and every optional output keep their
-    contracts.  No gradients w.r.t. the intrinsics.  Anything but a CameraModel / 5-tuple raises TypeError, an unknown model string
-    or a focal length that is not finite and positive ValueError.  Out of scope (NotImplementedError, before anything runs):
-    camera_grads=True (its terms differentiate projmatrix) and the view-parallel paths.  fused_geometry.depth_normals and
-    normal_consistency_loss still assume the centred pinhole of tanfovx / tanfovy.  With None every call is what it was without the
-    keyword, bit for bit."""
+    contracts.  Gradients w.r.t. the pose and the intrinsics: camera_model_grads.  Anything but a CameraModel / 5-tuple raises
+    TypeError, an unknown model string or a focal length that is not finite and positive ValueError.  Out of scope
+    (NotImplementedError, before anything runs): camera_grads=True (its terms differentiate projmatrix; camera_model_grads is the
+    form for a model) and the view-parallel paths.  fused_geometry.depth_normals and normal_consistency_loss still assume the
+    centred pinhole of tanfovx / tanfovy.  With None every call is what it was without the keyword, bit for bit.
+
+    camera_model_grads (extension, default False; needs camera_model): True makes the settings' viewmatrix and campos autograd
+    inputs behind the model, as camera_grads does for the default camera: pose refinement, tracking and bundle adjustment on
+    calibrated and fisheye cameras (include/gsr_cam_cm.h).  A float32 (4,) tensor on the render's device does the same and is, in
+    addition, the autograd handle of (fx, fy, cx, cy): it receives dL/dintrinsics (self-calibration).  Its VALUES are not read --
+    the kernels take the CameraModel's floats; CameraModel.from_tensor(model, intrinsics) builds the model from the tensor (one
+    read-back per step), and with settings.debug the forward compares the two and raises ValueError on a mismatch.  The gradients
+    are those of the function the camera-model backward differentiates (straight-through 0.99 clamp; the pinhole's guard-band clamp
+    a constant, its limits without a gradient w.r.t. the intrinsics; culling, radii, tile membership and depth order carry none);
+    projmatrix has none, a model ignores it.  An input that requires no gradient gets None, and when none of the three does the
+    plain camera-model kernels run.  Without a camera_model ValueError; anything but a bool or a tensor TypeError; a wrong dtype,
+    shape or device ValueError; the view-parallel paths NotImplementedError.  With False every call is the call it was."""
 
     def __init__(self, raster_settings, densify_stats=None, depth_alpha=None, antialiasing=False, contrib_stats=None,
                  contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None,
-                 camera_model=None):
+                 camera_model=None, camera_model_grads=False):
         super().__init__()
         if depth_alpha is not None:
             _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
@@ -529,6 +569,8 @@ class GaussianRasterizer(nn.Module):
         # TypeError for anything but a CameraModel / 5-tuple, ValueError for bad values, NotImplementedError with camera_grads
         self.camera_model = _C.camera_model(camera_model)
         _C.camera_model_excludes(self.camera_model, self.camera_grads)
+        # ValueError without a model or for a wrong tensor, TypeError for anything but a bool or a tensor
+        self.camera_model_grads = _C.camera_model_grads_arg(camera_model_grads, self.camera_model)
         self.raster_settings = raster_settings
         self.densify_stats = densify_stats
         self.depth_alpha = depth_alpha
@@ -572,8 +614,8 @@ class GaussianRasterizer(nn.Module):
                                                    cov3D_precomp, raster_settings, self.depth_alpha, self.densify_stats,
                                                    self.antialiasing, self.contrib_stats, self.contrib_pixel_weight, self.camera_grads,
                                                    self.absgrad, features, self.distortion, self.median_depth, self.index_maps,
-                                                   self.camera_model)
+                                                   self.camera_model, self.camera_model_grads)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                    cov3D_precomp, raster_settings, self.densify_stats, self.antialiasing, self.contrib_stats,
                                    self.contrib_pixel_weight, self.camera_grads, self.absgrad, features, self.index_maps,
-                                   self.camera_model)
+                                   self.camera_model, self.camera_model_grads)

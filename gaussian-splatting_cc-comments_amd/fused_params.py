@@ -18,7 +18,7 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C, camera_grad_results, camera_inputs
+from diff_gaussian_rasterization import _C, camera_grad_results, camera_inputs, camera_model_grad_results
 
 _vp, _i64, _d = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
 ADAM_MAX_GROUPS = 8
@@ -98,7 +98,9 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
             _C.absgrad_tensors(absgrad, int(xyz.size(0)), xyz.device if xyz.is_cuda else None)
         R, color, radii, geom, binning, img, M, (xyz, features_dc, features_rest, scaling, rotation), *maps = _leaf_forward(
             None if depth_alpha is None else _C.aux_mode(depth_alpha), xyz, features_dc, features_rest, opacity, scaling, rotation,
-            raster_settings, antialiasing, camera[0] if len(camera) == 1 else None)
+            raster_settings, antialiasing, camera[0] if len(camera) in (1, 4) else None)
+        if len(camera) == 4 and camera[3] is not None and raster_settings.debug:   # the handle of the intrinsics and the model agree
+            _C.camera_model_matches(_C.camera_model(camera[0]), camera[3])
         if contrib_stats is not None:   # the blend-weight statistics of this view (GaussianRasterizer): once per forward, never in backward
             _C.gaussian_contributions(geom, binning, img, R, int(xyz.size(0)), raster_settings.image_width, raster_settings.image_height,
                                       contrib_stats, contrib_pixel_weight, raster_settings.debug)
@@ -126,7 +128,8 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         ctx.antialiasing = antialiasing
         ctx.absgrad = absgrad
         ctx.camera = len(camera) == 3   # the settings' viewmatrix, projmatrix, campos as inputs (GaussianRasterizer, camera_grads)
-        ctx.camera_model = camera[0] if len(camera) == 1 else None   # or the one checked CameraModel (GaussianRasterizer, camera_model)
+        ctx.camera_model = camera[0] if len(camera) in (1, 4) else None   # or the one checked CameraModel (GaussianRasterizer, camera_model)
+        ctx.camera_cm = len(camera) == 4   # ... with the settings' viewmatrix, campos and the intrinsics tensor (or None) behind it (camera_model_grads)
         # after the state: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the opacity logits
         # that the anti-aliased backward reads (the records hold sigmoid(logit) * rho), each saved on its path only
         ctx.save_for_backward(xyz, features_dc, features_rest, scaling, rotation, radii, geom, binning, img,
@@ -154,7 +157,7 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                 # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
                 return (_C.features_backward_only(geom, binning, img, R, int(xyz.size(0)), st.image_width, st.image_height, features,
                                                   grad_features_map, st.debug),
-                        (None,) * (14 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0)))
+                        (None,) * (14 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0) + (3 if ctx.camera_cm else 0)))
             if grad_features_map is not None:   # (no gradient reached the map: the feature pass is skipped)
                 fb = _C.FeatureBackward(features, grad_features_map)
         if grad_color is None:
@@ -163,6 +166,8 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         cam_needs = tuple(ctx.needs_input_grad[14 + off:17 + off]) if ctx.camera else ()
         cam, cam_grads = None, (None, None, None) if ctx.camera else ()
+        cm_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera_cm else ()
+        cm_grads = (None, None, None) if ctx.camera_cm else ()
         with torch.cuda.device(dev):
             alloc = torch.zeros if P == 0 else torch.empty
             d_means2D, d_xyz = alloc((P, 3), **f32), alloc((P, 3), **f32)
@@ -188,18 +193,24 @@ class _RasterizeLeafGaussians(torch.autograd.Function):
                     x = _C.aux_backward_args(ctx.depth_alpha, extra[0], hw(grad_depth), hw(grad_alpha), dev)
                 if any(cam_needs):
                     cam, outs = _C.camera_backward_args(P, dev)
+                elif any(cm_needs):   # the camera gradients under the model (include/gsr_cam_cm.h)
+                    cam, outs = _C.camera_cm_backward_args(P, dev)
                 _C.run_backward(a, scratch, dev, x, extra[-1] if ctx.antialiasing else None, cam=cam,
                                 absgrad=None if ctx.absgrad is None else _C.absgrad_tensors(ctx.absgrad, P, dev), features=fb,
                                 distortion=db, median=mb, camera_model=ctx.camera_model)
             elif any(cam_needs):
                 outs = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
+            elif any(cm_needs):
+                outs = (torch.zeros((4, 4), **f32), torch.zeros((4,), **f32), torch.zeros((3,), **f32))
             if any(cam_needs):
                 cam_grads = camera_grad_results(cam_needs, outs, (st.viewmatrix, st.projmatrix, st.campos))
+            if any(cm_needs):
+                cm_grads = camera_model_grad_results(cm_needs, outs, st)
         grad_features = None
         if fb is not None:   # (no Gaussian: nothing ran)
             grad_features = fb.grad if fb.grad is not None else torch.zeros_like(fb.features)
         return grad_features, (d_xyz, d_means2D, d_dc, d_rest, d_opacity, d_scaling, d_rotation, None, None, None, None, None, None, None,
-                               *cam_grads, *((None,) if ctx.camera_model is not None else ()))
+                               *cam_grads, *((None,) if ctx.camera_model is not None else ()), *cm_grads)
 
 
 class _RasterizeLeafGaussiansFeatures(torch.autograd.Function):
@@ -255,7 +266,8 @@ class _RasterizeLeafGaussiansMedian(torch.autograd.Function):
 
 def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats=None,
                              depth_alpha=None, antialiasing=False, contrib_stats=None, contrib_pixel_weight=None, camera_grads=False,
-                             absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, camera_model=None):
+                             absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, camera_model=None,
+                             camera_model_grads=False):
     """Equivalent to
         GaussianRasterizer(raster_settings)(means3D=xyz, means2D=means2D, shs=cat(features_dc, features_rest, 1),
             opacities=sigmoid(opacity), scales=exp(scaling), rotations=normalize(rotation))
@@ -273,7 +285,9 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
     map, as GaussianRasterizer's (median_depth=True): differentiable w.r.t. xyz along the view z axis.
     index_maps: (median_index, dominant_index, dominant_weight), overwritten in place by the forward, as GaussianRasterizer's.
     camera_model: a CameraModel ("pinhole" with intrinsics or "fisheye"), as GaussianRasterizer's: the settings' projmatrix, tanfovx and
-    tanfovy are then ignored; not with camera_grads (NotImplementedError)."""
+    tanfovy are then ignored; not with camera_grads (NotImplementedError): camera_model_grads is its form for a model.
+    camera_model_grads: True or the float32 (4,) intrinsics tensor (with camera_model), as GaussianRasterizer's: the settings'
+    viewmatrix and campos, and the tensor, take part in autograd behind the model."""
     if depth_alpha is not None:
         _C.aux_mode(depth_alpha)
     distortion = _C.distortion_flag(distortion, depth_alpha)
@@ -282,7 +296,7 @@ def rasterize_leaf_gaussians(xyz, means2D, features_dc, features_rest, opacity, 
         _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
     inputs = (xyz, means2D, features_dc, features_rest, opacity, scaling, rotation, raster_settings, stats, depth_alpha,
               _C.aa_flag(antialiasing), contrib_stats, contrib_pixel_weight, absgrad,
-              *camera_inputs(raster_settings, camera_grads, camera_model))
+              *camera_inputs(raster_settings, camera_grads, camera_model, camera_model_grads))
     if features is not None:
         _C.feature_tensor(features, int(xyz.size(0)))   # refused before anything runs
     if median_depth or index_maps is not None:

@@ -83,7 +83,8 @@ def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
-           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False, camera_model=None):
+           absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False, camera_model=None,
+           camera_model_grads=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -110,9 +111,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     channels; on both paths.  The input of fused_geometry.normal_consistency_loss().
     camera_model (extension): a CameraModel ("pinhole" with intrinsics, or "fisheye") -- see GaussianRasterizer; None = the camera's own
     `camera_model` attribute if it has one, else the centred pinhole of FoVx / FoVy.  With a model the camera's full_proj_transform,
-    FoVx and FoVy are ignored; on both paths; not with camera_grads.  The normal map of normals=True is the blend of per-Gaussian
+    FoVx and FoVy are ignored; on both paths; not with camera_grads (camera_model_grads is its form for a model).  The normal map of normals=True is the blend of per-Gaussian
     normals and works with either model; fused_geometry.depth_normals() and normal_consistency_loss(), which the caller applies to the
-    result, still assume the centred pinhole."""
+    result, still assume the centred pinhole.
+    camera_model_grads (extension): True, or the float32 (4,) tensor (fx, fy, cx, cy) that is the autograd handle of the model's
+    intrinsics -- the camera's world_view_transform and camera_center (and the tensor) take part in autograd behind the camera
+    model (see GaussianRasterizer): pose refinement and self-calibration on calibrated and fisheye cameras; None =
+    getattr(pipe, "camera_model_grads", False); on both paths."""
     from diff_gaussian_rasterization import _C
     _C.normals_flag(normals)   # a switch: anything but a bool is refused
     if camera_model is None:
@@ -121,6 +126,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         camera_grads = getattr(pipe, "camera_grads", False)
     camera_model = _C.camera_model(camera_model)   # refused before anything runs: a bad model, and a model with camera gradients
     _C.camera_model_excludes(camera_model, camera_grads is True)
+    if camera_model_grads is None:
+        camera_model_grads = getattr(pipe, "camera_model_grads", False)
+    camera_model_grads = _C.camera_model_grads_arg(camera_model_grads, camera_model)   # refused before anything runs too
     if antialiasing is None:
         antialiasing = getattr(pipe, "antialiasing", False)
     xyz = pc.get_xyz
@@ -142,7 +150,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh
     user_channels = None
     if normals:   # three more feature channels behind the caller's own
-        n = _gaussian_normals(viewpoint_camera, pc, leaf, camera_grads is True)
+        n = _gaussian_normals(viewpoint_camera, pc, leaf, camera_grads is True or camera_model_grads is not False)
         if features is None:
             user_channels, features = 0, n
         else:
@@ -157,6 +165,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         extras["index_maps"] = index_maps
     if camera_model is not None:    # ... and the camera model (checked by either path before anything runs)
         extras["camera_model"] = camera_model
+    if camera_model_grads is not False:   # ... with the camera gradients under it
+        extras["camera_model_grads"] = camera_model_grads
 
     if leaf:
         from fused_params import rasterize_leaf_gaussians

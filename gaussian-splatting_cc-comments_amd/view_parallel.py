@@ -240,7 +240,7 @@ class _RasterizeViewParallel(torch.autograd.Function):
 
 def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations, raster_settings, exchange, stats=None,
                             antialiasing=False, camera_grads=False, absgrad=None, features=None, distortion=False,
-                            median_depth=False, index_maps=None, camera_model=None):
+                            median_depth=False, index_maps=None, camera_model=None, camera_model_grads=False):
     """GaussianRasterizer(raster_settings)(means3D=..., means2D=..., shs=..., opacities=..., scales=..., rotations=...)
     for ONE view of a view-parallel step: same (color, radii); after backward the parameter gradients are the
     sums over all ranks' views (exchange: GradientExchange; stats: optional densification tensors, see
@@ -264,6 +264,9 @@ def rasterize_view_parallel(means3D, means2D, shs, opacities, scales, rotations,
     if index_maps is not None:
         raise NotImplementedError("rasterize_view_parallel: the per-pixel index maps (index_maps=) have no view-parallel form "
                                   "(include/gsr_median.h); render them with GaussianRasterizer view by view")
+    if camera_model_grads is not False:
+        raise NotImplementedError("rasterize_view_parallel: camera gradients under a camera model (camera_model_grads=) need the "
+                                  "whole scene in one per-Gaussian pass: no view-parallel form (include/gsr_cam_cm.h)")
     if camera_model is not None:
         raise NotImplementedError("rasterize_view_parallel: camera models (camera_model=) have no view-parallel form "
                                   "(include/gsr_camera_model.h); render such views with GaussianRasterizer")
@@ -385,13 +388,13 @@ class ViewsInFlight:
         self.staggered = staggered
 
     def forward_backward(self, render_fns, upstream_grads, features=None, distortion=False, median_depth=False, index_maps=None,
-                         camera_model=None):
+                         camera_model=None, camera_model_grads=False):
         """Forward and backward of every view, `in_flight` at a time; returns the images (detached).  Work issued before the call on
         the current stream is waited for by the side streams, and the current stream waits for them at the end.
         features: not supported (NotImplementedError) -- a render_fn returns its image alone, and a feature map's gradient has no
         place in upstream_grads; render feature maps with GaussianRasterizer (features=) view by view.
         distortion, median_depth, index_maps: not supported either (NotImplementedError), for the same reason.
-        camera_model: not supported (NotImplementedError): the view-parallel render has no camera-model form."""
+        camera_model, camera_model_grads: not supported (NotImplementedError): the view-parallel render has no camera-model form."""
         if features is not None:
             raise NotImplementedError("ViewsInFlight: feature channels (features=) are not supported: a view's feature map and its "
                                       "gradient have no place in render_fns / upstream_grads (include/gsr_features.h)")
@@ -404,6 +407,9 @@ class ViewsInFlight:
         if index_maps is not None:
             raise NotImplementedError("ViewsInFlight: the per-pixel index maps (index_maps=) are not supported: a render_fn returns its "
                                       "image alone (include/gsr_median.h)")
+        if camera_model_grads is not False:
+            raise NotImplementedError("ViewsInFlight: camera gradients under a camera model (camera_model_grads=) are not supported: "
+                                      "rasterize_view_parallel has no such form (include/gsr_cam_cm.h)")
         if camera_model is not None:
             raise NotImplementedError("ViewsInFlight: camera models (camera_model=) are not supported: rasterize_view_parallel has no "
                                       "camera_model form (include/gsr_camera_model.h)")
