@@ -77,9 +77,8 @@ __global__ void __launch_bounds__(GSR_ABS_THREADS) gsr_absgrad_fold_kernel(
 	if (stat_abs_gradient_accum && visible) stat_abs_gradient_accum[idx] += hypotf(ax, ay);   // (no underflow of the squares: a barely visible Gaussian's sums are tiny)
 }
 
-void gsr_launch_absgrad_fold(int first, int count, GsrGeometry g, const int* radii, const GsrGradSlot* slots, const uint8_t* slot_valid,
-                             float* abs_dL_dmean2D, float* stat_abs_gradient_accum, hipStream_t s)
+void gsr_launch_absgrad_fold(const GsrFrame& f, int first, int count, const int* radii, float* abs_dL_dmean2D, float* stat_abs_gradient_accum)
 {
-	gsr_launch(gsr_absgrad_fold_kernel, dim3((count + GSR_ABS_THREADS - 1) / GSR_ABS_THREADS), dim3(GSR_ABS_THREADS), 0, s, nullptr, nullptr,
-	           first, count, g.tiles_touched, g.slot_base, radii, slots, slot_valid, abs_dL_dmean2D, stat_abs_gradient_accum);
+	gsr_launch(gsr_absgrad_fold_kernel, dim3((count + GSR_ABS_THREADS - 1) / GSR_ABS_THREADS), dim3(GSR_ABS_THREADS), 0, f.s, nullptr, nullptr,
+	           first, count, f.g.tiles_touched, f.g.slot_base, radii, f.slots, f.slot_valid, abs_dL_dmean2D, stat_abs_gradient_accum);
 }

@@ -312,9 +312,10 @@ static const GsrAuxBlend* gsr_aux_view(const gsr_aux_args* x, int64_t R, int W, 
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-// The one validity check of the option arguments (include/gsr_aux.h, include/gsr_aa.h), called once by every *_aux / *_aa entry
-// point.  antialiasing: 0 or 1 (the *_aux calls pass 0).  aux: NULL only where `optional` (the *_aa calls); its mode is always
-// checked, and beyond that what the calling stage needs of it.  live: the call has work to launch, so what it needs must be there.
+// The validity check of the option arguments (include/gsr_aux.h, include/gsr_aa.h): called by gsr_gaussian_options for the per-Gaussian
+// passes, and by the blend's *_aux / *_abs entry points themselves.  antialiasing: 0 or 1 (the *_aux calls pass 0).  aux: NULL only
+// where `optional` (the *_aa calls); its mode is always checked, and beyond that what the calling stage needs of it.  live: the call
+// has work to launch, so what it needs must be there.
 enum GsrAuxNeeds {
 	GSR_AUX_NEEDS_MODE,      // stage 1: reads nothing else
 	GSR_AUX_NEEDS_SCRATCH,   // the backward: an aligned scratch (the blend reads it; the per-Gaussian pass takes the same arguments)
@@ -332,7 +333,7 @@ static int gsr_option_check(const char* who, int antialiasing, const gsr_aux_arg
 	return GSR_OK;
 }
 
-// The one validity check of a camera model (include/gsr_camera_model.h), called once by every *_cm entry point with a model
+// The validity check of a camera model (include/gsr_camera_model.h), called by gsr_gaussian_options
 static int gsr_camera_model_check(const char* who, const gsr_camera_model& m)
 {
 	if (m.model != GSR_CAMERA_PINHOLE && m.model != GSR_CAMERA_FISHEYE)
@@ -342,6 +343,112 @@ static int gsr_camera_model_check(const char* who, const gsr_camera_model& m)
 	if (!std::isfinite(m.cx) || !std::isfinite(m.cy))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cx and cy must be finite, got %g, %g", who, (double)m.cx, (double)m.cy);
 	return GSR_OK;
+}
+
+// ---- the options of the per-Gaussian passes (GsrGaussianOptions) -----------------------------------
+// The one check of what the *_aux, *_aa, *_cm, *_cam and *_cam_cm entry points of stage 1 and of the per-Gaussian backward add to the
+// plain call, under the caller's name `who`, and the record the pass then runs with.  aux_required: the *_aux calls (elsewhere NULL =
+// no maps).  needs: what the stage reads of aux -- GSR_AUX_NEEDS_MODE is stage 1, whose own arguments gsr_forward_preprocess_impl
+// checks; else the backward with its args, opacity input and range.  model, cam: NULL = not offered by the caller or not asked for.
+static int gsr_gaussian_options(GsrGaussianOptions* o, const char* who, bool aux_required, GsrAuxNeeds needs, const gsr_aux_args* aux,
+                                int antialiasing, const float* opacities, const gsr_camera_model* model, const GsrCamTarget* cam,
+                                const gsr_backward_args* args, int first, int count)
+{
+	int rc;
+	if (model && (rc = gsr_camera_model_check(who, *model))) return rc;
+	if ((rc = gsr_option_check(who, antialiasing, aux, !aux_required, needs, false))) return rc;
+	*o = GsrGaussianOptions{};
+	o->aux = aux ? aux->mode : 0;
+	o->aa = antialiasing;
+	o->cm = model;
+	if (needs == GSR_AUX_NEEDS_MODE) return GSR_OK;
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	const gsr_backward_args& a = *args;
+	// (under a model the sizes and the geometry buffer are refused under this call's name; without one, by the pass itself)
+	if (model && (a.P < 0 || a.num_rendered < 0 || a.width <= 0 || a.height <= 0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	if (cam) {
+		if (!cam->dL_dviewmatrix || !cam->dL_dmid || !cam->dL_dcampos)
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dviewmatrix, %s or dL_dcampos is NULL", who, model ? "dL_dintrinsics" : "dL_dprojmatrix");
+		if (!cam->rows) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam is NULL", who);
+		if (!aligned16(cam->rows)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam must be 16-byte aligned", who);
+		if (first != 0 || count != a.P)
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera gradients need the whole scene in one call (first 0, count %d; got %d, %d): "
+			                "the part-by-part pipeline of view-parallel mode has no camera form", who, a.P, first, count);
+		o->cam = *cam;
+	}
+	if (model && a.P > 0 && !a.geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
+	if (cam && a.P > 0 && a.shs && !a.cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
+	if (antialiasing && a.P > 0 && count > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
+	o->aa_opacities = antialiasing ? opacities : nullptr;
+	return GSR_OK;
+}
+
+// ---- stages --------------------------------------------------------------------------------------
+// One stage of a call: `launch` -- its kernels, and the fills that belong to them -- inside the stage's profiling scope, then
+// gsr_stage_done.  launch returns nothing, or a GSR code that ends the call unless it is GSR_OK.  record = false: no scope, because the
+// stage is ONE kernel whose own dispatch packet takes the timestamps (gsr_prof_kernel_events).  `launch` is a template parameter, not a
+// std::function: the stages are the launch path.
+template <typename F>
+static int gsr_stage(hipStream_t s, int debug, const char* name, F&& launch, bool record = true)
+{
+	{
+		GsrProfScope p(s, record ? name : nullptr);
+		if constexpr (std::is_void<decltype(launch())>::value) launch();
+		else if (int rc = launch()) return rc;
+	}
+	return gsr_stage_done(s, debug, name);
+}
+
+// ---- the state of a forward (GsrFrame) -------------------------------------------------------------
+// Every call after stage 1 opens the state it reads here, in two steps around its own checks, so that refusals keep one order:
+// gsr_frame_sizes (which also clears the last error); the call's option checks; P == 0 is GSR_OK; the call's own pointers;
+// gsr_frame_open -- NULL state, alignment, the limit on R; then the call's R == 0 shortcut.
+enum : unsigned {
+	GSR_FRAME_IMAGE = 1,   // the call reads the image buffer
+	GSR_FRAME_SLOTS = 2,   // ... and the gradient slots: like binning, required when R > 0
+	GSR_FRAME_R32 = 4      // the call refuses R beyond 32 bits (the blend's and the per-Gaussian backward never have)
+};
+
+static int gsr_frame_sizes(const char* who, int P, int64_t R, int W, int H)
+{
+	g_err[0] = 0;
+	if (P < 0 || R < 0 || W <= 0 || H <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	return GSR_OK;
+}
+
+// own_aligned: the call's own buffers that must be 16-byte aligned are (they are refused with the state buffers)
+static int gsr_frame_open(GsrFrame* f, const char* who, unsigned needs, int P, int64_t R, int W, int H, const void* geometry, const void* binning,
+                          const void* image, void* slots, void* stream, int debug, bool own_aligned)
+{
+	const bool img = needs & GSR_FRAME_IMAGE, sl = needs & GSR_FRAME_SLOTS;
+	if (!geometry || (img && !image) || (R > 0 && (!binning || (sl && !slots))))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(geometry) || (img && !aligned16(image)) || !aligned16(binning) || (sl && !aligned16(slots)) || !own_aligned)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
+	if ((needs & GSR_FRAME_R32) && R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
+	*f = GsrFrame{};
+	f->P = P; f->W = W; f->H = H; f->R = R;
+	f->g = gsr_geometry_view((void*)geometry, P);
+	if (img) f->img = gsr_image_view((void*)image, W, H);
+	if (R > 0) {
+		f->bin = gsr_binning_view((void*)binning, P, R, W, H);
+		f->slot_valid = (uint8_t*)f->bin.tile_keys_alt;
+	}
+	if (sl) f->slots = (GsrGradSlot*)slots;
+	f->s = (hipStream_t)stream; f->debug = debug; f->cull = !(debug & GSR_DEBUG_NO_CULL);
+	return GSR_OK;
+}
+
+// the calls that take their state in gsr_backward_args
+static int gsr_frame_sizes(const char* who, const gsr_backward_args* a)
+{
+	g_err[0] = 0;
+	if (!a) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	return gsr_frame_sizes(who, a->P, a->num_rendered, a->width, a->height);
+}
+static int gsr_frame_open(GsrFrame* f, const char* who, unsigned needs, const gsr_backward_args& a, bool own_aligned)
+{
+	return gsr_frame_open(f, who, needs, a.P, a.num_rendered, a.width, a.height, a.geometry, a.binning, a.image, a.scratch, a.stream, a.debug, own_aligned);
 }
 
 GsrGeometry gsr_geometry_view(void* blob, int P)
@@ -506,10 +613,10 @@ static thread_local GsrLastStage1 g_last_stage1;
 
 // ---- forward, stage 1 --------------------------------------------------------------------------
 // `in`: the caller's inputs (gsr_preprocess_inputs / gsr_preprocess_leaves); what stage 1 derives itself (focal lengths, trim, the
-// geometry view) is filled in here.  aux: 0 or a GSR_AUX_* mode; aa: the screen-space filter.  Both stay outside the struct, which
-// is the kernels' argument.  cm: NULL, or a checked camera model (include/gsr_camera_model.h): projmatrix and the tangents are not read.
+// geometry view) is filled in here.  o: the checked options, which stay outside the struct (it is the kernels' argument); under a
+// camera model projmatrix and the tangents are not read.
 static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geometry, int64_t* num_rendered_host, void* stream, int debug,
-                                       int aux, int aa, const gsr_camera_model* cm = nullptr)
+                                       const GsrGaussianOptions& o)
 {
 	g_err[0] = 0;
 	hipStream_t s = (hipStream_t)stream;
@@ -519,7 +626,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	*num_rendered_host = 0;
 	if (P < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "bad P / image size");
 	if (P == 0) return GSR_OK;  // rasterize_points.cu:94: nothing is launched for an empty scene
-	if (!a.means3D || !a.opacities || !a.viewmatrix || (!a.projmatrix && !cm) || !geometry)  // radii is optional (rasterizer.h:52)
+	if (!a.means3D || !a.opacities || !a.viewmatrix || (!a.projmatrix && !o.cm) || !geometry)  // radii is optional (rasterizer.h:52)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_preprocess: required pointer is NULL");
 	if (!a.colors_precomp && !a.shs)  // rasterizer_impl.cu:281-284
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "For non-RGB, provide precomputed Gaussian colors!");
@@ -535,7 +642,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	if (a.leaf && a.M > 16) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "leaf mode: at most 16 SH coefficients (degree 3), M = %d", a.M);
 	a.focal_y = height / (2.0f * a.tan_fovy);  // rasterizer_impl.cu:251-252
 	a.focal_x = width / (2.0f * a.tan_fovx);
-	if (cm) { a.focal_x = cm->fx; a.focal_y = cm->fy; }
+	if (o.cm) { a.focal_x = o.cm->fx; a.focal_y = o.cm->fy; }
 	a.g = gsr_geometry_view(geometry, P);
 
 	int rc;
@@ -572,7 +679,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	gsr_launch_zero_status(a.g.status, s, beside ? td.aux_fork : nullptr);
 	if (beside) {
 		if ((rc = gsr_check_hip(hipStreamWaitEvent(td.aux_stream, td.aux_fork, 0), "hipStreamWaitEvent(fork)"))) return rc;
-		gsr_launch_preprocess_color(a, td.aux_stream, P <= GSR_COLOR_BESIDE_MAX_P ? GSR_COLOR_BESIDE_WGS : 0, aux);
+		gsr_launch_preprocess_color(a, td.aux_stream, P <= GSR_COLOR_BESIDE_MAX_P ? GSR_COLOR_BESIDE_WGS : 0, o.aux);
 		if (hipEventRecord(td.aux_join, td.aux_stream) != hipSuccess) {
 			(void)hipStreamSynchronize(td.aux_stream);  // no event to wait for: wait on the host instead, then report
 			return gsr_fail(GSR_ERR_HIP, "hipEventRecord(join) failed");
@@ -586,16 +693,8 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	// GSR_DEBUG_SERIAL, when every stage is being timed, or when the stream cannot be had.
 	const bool copy_beside = !(debug & (GSR_DEBUG_SYNC | GSR_DEBUG_SERIAL)) && !gsr_prof_records_all(s) &&
 	                         gsr_helper_stream(&td.copy_stream, &td.copy_fork, nullptr);
-	{
-		GsrProfScope p(s, "preprocess");
-		gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, aux, aa, cm);
-	}
-	if ((rc = gsr_stage_done(s, debug, "preprocess"))) return rc;
-	if (color && !beside) {
-		GsrProfScope p(s, "preprocess_color");
-		gsr_launch_preprocess_color(a, s, 0, aux);
-	}
-	if ((rc = gsr_stage_done(s, debug, "preprocess_color"))) return rc;
+	if ((rc = gsr_stage(s, debug, "preprocess", [&] { gsr_launch_preprocess(a, s, copy_beside ? td.copy_fork : nullptr, o); }))) return rc;
+	if (color && !beside && (rc = gsr_stage(s, debug, "preprocess_color", [&] { gsr_launch_preprocess_color(a, s, 0, o.aux); }))) return rc;
 
 	// read num_rendered back; the per-Gaussian half of the sort is enqueued behind the copy and keeps
 	// the GPU busy while the host waits on the event, allocates the binning buffer and launches stage 2
@@ -618,8 +717,7 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	// words, reduced by every sort workgroup).  Its first three 8-bit passes are always needed and are enqueued at once;
 	// whether bits 24..31 of max - min are populated is known once the status block has landed on the host.
 	const uint32_t* bias = a.g.status + GSR_STATUS_NEGMIN;
-	{
-		GsrProfScope p(s, "depth_sort");
+	rc = gsr_stage(s, debug, "depth_sort", [&] {
 		if (bucket) {
 			gsr_launch_depth_bucket_sort(a.g, P, col_pairs ? gsr_tilebin_seg(a.g, P) : nullptr, s);
 			if (col_pairs) gsr_launch_tilebin_col_hist(a.g, P, 0, s, true);
@@ -636,8 +734,8 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 			// kernel, which streams the SH rows: 48 MB took 0.10-0.125 ms there at 6 M Gaussians, 0.025 alone.
 			gsr_launch_slot_base_finish(a.g.slot_base, a.g.block_tiles, a.g.status, (size_t)P, s);
 		}
-	}
-	if ((rc = gsr_stage_done(s, debug, "depth_sort"))) return rc;
+	});
+	if (rc) return rc;
 	if ((rc = gsr_check_hip(hipEventSynchronize(ev), "hipEventSynchronize(num_rendered)"))) return rc;
 	drain.disarm();   // (the copy has landed)
 	g_last_stage1.geometry = geometry;
@@ -657,18 +755,18 @@ static int gsr_forward_preprocess_impl(const GsrPreprocessArgs& in, void* geomet
 	const int fourth = !bucket && ((culled_value >> 24) != 0u || (kmax >= kmin && kmax - kmin == 0xFFFFFFFFu));
 	// join: everything the caller enqueues after this call comes after the colour kernel too
 	if ((rc = join.now())) return rc;
-	if (fourth) {
-		GsrProfScope p(s, "depth_sort");
+	if (!fourth) return gsr_stage_done(s, debug, "depth_sort");
+	return gsr_stage(s, debug, "depth_sort", [&] {
 		gsr_radix_sort_passes(a.g.depth_keys, a.g.perm, a.g.depth_keys_alt, a.g.perm_alt, (size_t)P, 32, 4, 3, 1, a.g.sort_table, bias, 4, s);
 		// three passes leave the order in (depth_keys_alt, perm_alt), four in (depth_keys, perm): recorded in status[2]
 		if (col_pairs) {   // the histogram's chunk sums were added to by the run over the three-pass order
-			if ((rc = gsr_check_hip(hipMemsetAsync(a.g.col_table, 0, gsr_tilebin_col_clear_words((size_t)P) * 4, s), "hipMemsetAsync(col_table)"))) return rc;
+			if (int e = gsr_check_hip(hipMemsetAsync(a.g.col_table, 0, gsr_tilebin_col_clear_words((size_t)P) * 4, s), "hipMemsetAsync(col_table)")) return e;
 			gsr_launch_tilebin_col_hist(a.g, P, 0, s);
 		} else {
 			gsr_launch_sorted_block_sums(a.g, P, 0, s);   // (their prefix sums are taken by the key emission itself)
 		}
-	}
-	return gsr_stage_done(s, debug, "depth_sort");
+		return (int)GSR_OK;
+	});
 }
 
 // the inputs of the calls that take activated tensors, and of the calls that take the optimiser's leaves (activated inside the kernels)
@@ -700,6 +798,19 @@ static GsrPreprocessArgs gsr_preprocess_leaves(int P, int D, int M, int width, i
 	return a;
 }
 
+// Every stage-1 entry point: the one check of its options under its own name, then the stage.  Under a model the sizes and the geometry
+// buffer are refused under that name as well.
+static int gsr_forward_preprocess_opt(const char* who, bool aux_required, const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux,
+                                      const GsrPreprocessArgs& a, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
+{
+	GsrGaussianOptions o;
+	int rc;
+	if ((rc = gsr_gaussian_options(&o, who, aux_required, GSR_AUX_NEEDS_MODE, aux, antialiasing, nullptr, model, nullptr, nullptr, 0, 0))) return rc;
+	if (model && (a.P < 0 || a.W <= 0 || a.H <= 0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad P / image size", who);
+	if (model && a.P > 0 && !geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, o);
+}
+
 extern "C" int gsr_forward_preprocess(int P, int D, int M, int width, int height, const float* means3D,
                                       const float* shs, const float* colors_precomp, const float* opacities,
                                       const float* scales, float scale_modifier, const float* rotations,
@@ -709,7 +820,7 @@ extern "C" int gsr_forward_preprocess(int P, int D, int M, int width, int height
 {
 	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
 	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, 0, 0);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, GsrGaussianOptions{});
 }
 
 extern "C" int gsr_forward_preprocess_leaf(int P, int D, int M, int width, int height, const float* xyz,
@@ -722,7 +833,7 @@ extern "C" int gsr_forward_preprocess_leaf(int P, int D, int M, int width, int h
 {
 	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
 	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, 0, 0);
+	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, GsrGaussianOptions{});
 }
 
 extern "C" int gsr_forward_preprocess_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* means3D,
@@ -732,11 +843,9 @@ extern "C" int gsr_forward_preprocess_aux(const gsr_aux_args* aux, int P, int D,
                                           const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                                           int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	int rc;
-	if ((rc = gsr_option_check("gsr_forward_preprocess_aux", 0, aux, false, GSR_AUX_NEEDS_MODE, false))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
 	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux->mode, 0);
+	return gsr_forward_preprocess_opt("gsr_forward_preprocess_aux", true, nullptr, 0, aux, a, geometry, num_rendered_host, stream, debug);
 }
 
 extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, int D, int M, int width, int height, const float* xyz,
@@ -747,11 +856,9 @@ extern "C" int gsr_forward_preprocess_leaf_aux(const gsr_aux_args* aux, int P, i
                                                int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                                int debug)
 {
-	int rc;
-	if ((rc = gsr_option_check("gsr_forward_preprocess_leaf_aux", 0, aux, false, GSR_AUX_NEEDS_MODE, false))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
 	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux->mode, 0);
+	return gsr_forward_preprocess_opt("gsr_forward_preprocess_leaf_aux", true, nullptr, 0, aux, a, geometry, num_rendered_host, stream, debug);
 }
 
 // the anti-aliased path (include/gsr_aa.h): aux NULL or a known mode; antialiasing 0 or 1
@@ -762,11 +869,9 @@ extern "C" int gsr_forward_preprocess_aa(int antialiasing, const gsr_aux_args* a
                                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered,
                                          int* radii, void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	int rc;
-	if ((rc = gsr_option_check("gsr_forward_preprocess_aa", antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
 	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing);
+	return gsr_forward_preprocess_opt("gsr_forward_preprocess_aa", false, nullptr, antialiasing, aux, a, geometry, num_rendered_host, stream, debug);
 }
 
 extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_args* aux, int P, int D, int M, int width, int height,
@@ -777,26 +882,12 @@ extern "C" int gsr_forward_preprocess_leaf_aa(int antialiasing, const gsr_aux_ar
                                               int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                               int debug)
 {
-	int rc;
-	if ((rc = gsr_option_check("gsr_forward_preprocess_leaf_aa", antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
 	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing);
+	return gsr_forward_preprocess_opt("gsr_forward_preprocess_leaf_aa", false, nullptr, antialiasing, aux, a, geometry, num_rendered_host, stream, debug);
 }
 
-// a camera model (include/gsr_camera_model.h): model NULL = the *_aa call; else the model, the sizes and the geometry buffer are
-// checked first, under this call's name
-static int gsr_forward_cm_check(const char* who, const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int width,
-                                int height, const void* geometry)
-{
-	int rc;
-	if ((rc = gsr_camera_model_check(who, *model))) return rc;
-	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_MODE, false))) return rc;
-	if (P < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad P / image size", who);
-	if (P > 0 && !geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
-	return GSR_OK;
-}
-
+// a camera model (include/gsr_camera_model.h): model NULL = the *_aa call
 extern "C" int gsr_forward_preprocess_cm(const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int D, int M,
                                          int width, int height, const float* means3D, const float* shs, const float* colors_precomp,
                                          const float* opacities, const float* scales, float scale_modifier, const float* rotations,
@@ -804,15 +895,10 @@ extern "C" int gsr_forward_preprocess_cm(const gsr_camera_model* model, int anti
                                          const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, int* radii,
                                          void* geometry, int64_t* num_rendered_host, void* stream, int debug)
 {
-	if (!model)
-		return gsr_forward_preprocess_aa(antialiasing, aux, P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
-		                                 rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii,
-		                                 geometry, num_rendered_host, stream, debug);
-	int rc;
-	if ((rc = gsr_forward_cm_check("gsr_forward_preprocess_cm", model, antialiasing, aux, P, width, height, geometry))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_inputs(P, D, M, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
 	                                                    cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing, model);
+	return gsr_forward_preprocess_opt(model ? "gsr_forward_preprocess_cm" : "gsr_forward_preprocess_aa", false, model, antialiasing, aux, a, geometry,
+	                                  num_rendered_host, stream, debug);
 }
 
 extern "C" int gsr_forward_preprocess_leaf_cm(const gsr_camera_model* model, int antialiasing, const gsr_aux_args* aux, int P, int D, int M,
@@ -823,64 +909,41 @@ extern "C" int gsr_forward_preprocess_leaf_cm(const gsr_camera_model* model, int
                                               int prefiltered, int* radii, void* geometry, int64_t* num_rendered_host, void* stream,
                                               int debug)
 {
-	if (!model)
-		return gsr_forward_preprocess_leaf_aa(antialiasing, aux, P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales,
-		                                      scale_modifier, raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
-		                                      radii, geometry, num_rendered_host, stream, debug);
-	int rc;
-	if ((rc = gsr_forward_cm_check("gsr_forward_preprocess_leaf_cm", model, antialiasing, aux, P, width, height, geometry))) return rc;
 	const GsrPreprocessArgs a = gsr_preprocess_leaves(P, D, M, width, height, xyz, features_dc, features_rest, opacity_logits, log_scales, scale_modifier,
 	                                                    raw_rotations, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, radii);
-	return gsr_forward_preprocess_impl(a, geometry, num_rendered_host, stream, debug, aux ? aux->mode : 0, antialiasing, model);
+	return gsr_forward_preprocess_opt(model ? "gsr_forward_preprocess_leaf_cm" : "gsr_forward_preprocess_leaf_aa", false, model, antialiasing, aux, a,
+	                                  geometry, num_rendered_host, stream, debug);
 }
 
 // ---- forward, stage 2 --------------------------------------------------------------------------
-static int gsr_forward_render_impl(int P, int64_t R, int width, int height, const float* background,
-                                   const int* radii, void* geometry, void* binning, void* image, float* out_color,
-                                   void* stream, int debug, const gsr_aux_args* aux)
+static int gsr_forward_render_impl(int P, int64_t R, int width, int height, const float* background, void* geometry, void* binning, void* image,
+                                   float* out_color, void* stream, int debug, const gsr_aux_args* aux)
 {
-	g_err[0] = 0;
-	hipStream_t s = (hipStream_t)stream;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "bad sizes");
+	const char* who = "gsr_forward_render";
+	int rc;
+	if ((rc = gsr_frame_sizes(who, P, R, width, height))) return rc;
 	if (P == 0) return GSR_OK;  // image stays as allocated by the caller (zero-filled in the reference)
-	if (!background || !geometry || !image || !out_color || (R > 0 && !binning))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render: required pointer is NULL");
-	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "state buffers must be 16-byte aligned");
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered exceeds 32-bit offsets");
+	if (!background || !out_color) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32, P, R, width, height, geometry, binning, image, nullptr, stream, debug, true))) return rc;
 	if ((int64_t)gsr_grid_x(width) * gsr_grid_y(height) >= (1 << 28))  // dispatch-list entries keep the tile id in 28 bits
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "image too large: more than 2^28 tiles");
 
-	GsrGeometry g = gsr_geometry_view(geometry, P);
-	GsrImage im = gsr_image_view(image, width, height);
+	const GsrGeometry& g = f.g;
+	const GsrBinning& b = f.bin;
+	hipStream_t s = f.s;
 	const int ntiles = gsr_grid_x(width) * gsr_grid_y(height);
-	int rc;
 	int key_bytes = 4;
-	GsrBinning b;
-	memset(&b, 0, sizeof b);
 	const bool col_pairs = gsr_tilebin_applies(width, height) && !(debug & GSR_DEBUG_TILE_SORT);   // (as stage 1 decided)
 	if (g_last_stage1.geometry == geometry && g_last_stage1.col_pairs != col_pairs)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_forward_render: GSR_DEBUG_TILE_SORT must be passed to both forward calls or to neither "
 		                "(gsr_forward_preprocess on this thread prepared this geometry buffer for the other binning)");
-	if (R > 0) b = gsr_binning_view(binning, P, R, width, height);
 	if (R > 0 && col_pairs) {
 		// column pairs by tile column, their instances by tile row (tilebin.hip): point_list, ranges and the cleared validity
 		// bytes come out of the second pass; no per-instance key is ever stored
-		{
-			GsrProfScope p(s, "col_scatter");
-			gsr_launch_tilebin_col_scatter(g, P, b, R, s);
-		}
-		if ((rc = gsr_stage_done(s, debug, "col_scatter"))) return rc;
-		{
-			GsrProfScope p(s, "row_hist");
-			gsr_launch_tilebin_row_hist(g, P, b, R, s);
-		}
-		if ((rc = gsr_stage_done(s, debug, "row_hist"))) return rc;
-		{
-			GsrProfScope p(s, "row_scatter");
-			gsr_launch_tilebin_row_scatter(g, P, b, R, im.ranges, width, height, s);
-		}
-		if ((rc = gsr_stage_done(s, debug, "row_scatter"))) return rc;
+		if ((rc = gsr_stage(s, debug, "col_scatter", [&] { gsr_launch_tilebin_col_scatter(g, P, b, R, s); }))) return rc;
+		if ((rc = gsr_stage(s, debug, "row_hist", [&] { gsr_launch_tilebin_row_hist(g, P, b, R, s); }))) return rc;
+		if ((rc = gsr_stage(s, debug, "row_scatter", [&] { gsr_launch_tilebin_row_scatter(g, P, b, R, f.img.ranges, width, height, s); }))) return rc;
 	} else {
 		if (R > 0) {
 			const int bit = (int)gsr_get_higher_msb((uint32_t)ntiles);  // key bits above the depth word, rasterizer_impl.cu:355
@@ -889,43 +952,33 @@ static int gsr_forward_render_impl(int P, int64_t R, int width, int height, cons
 			uint32_t *k0 = even ? b.tile_keys : b.tile_keys_alt, *v0 = even ? b.point_list : b.point_list_alt;
 			uint32_t *k1 = even ? b.tile_keys_alt : b.tile_keys, *v1 = even ? b.point_list_alt : b.point_list;
 			key_bytes = gsr_tile_key_bytes(ntiles, (size_t)R);  // 16-bit tile ids whenever they fit: a quarter less traffic in emission, sort, ranges
-			{
-				GsrProfScope p(s, "duplicate_keys");
+			rc = gsr_stage(s, debug, "duplicate_keys", [&] {
 				gsr_launch_duplicate_keys(g, P, width, k0, key_bytes, v0, (uint32_t*)b.sort_table, gsr_radix_clear_words((size_t)R), s);
-			}
-			if ((rc = gsr_stage_done(s, debug, "duplicate_keys"))) return rc;
-			{
-				GsrProfScope p(s, "sort");
+			});
+			if (rc) return rc;
+			rc = gsr_stage(s, debug, "sort", [&] {
 				int in_first = 1;
 				gsr_radix_sort_u32(k0, v0, k1, v1, (size_t)R, bit, b.sort_table, &in_first, 0, key_bytes, s);  // chunk sums zeroed by duplicate_keys
-			}
-			if ((rc = gsr_stage_done(s, debug, "sort"))) return rc;
+			});
+			if (rc) return rc;
 		}
-		{
-			GsrProfScope p(s, "tile_ranges");
-			gsr_launch_tile_ranges(b.tile_keys, key_bytes, R, im.ranges, ntiles, b.tile_keys_alt, s);
-		}
-		if ((rc = gsr_stage_done(s, debug, "tile_ranges"))) return rc;
+		if ((rc = gsr_stage(s, debug, "tile_ranges", [&] { gsr_launch_tile_ranges(b.tile_keys, key_bytes, R, f.img.ranges, ntiles, b.tile_keys_alt, s); })))
+			return rc;
 	}
-	if (R > 0) {  // (measured at C3: the forward's own order is worth 33 us of blend time for ~12 us of this kernel and its launch)
-		GsrProfScope p(s, "tile_order");
-		gsr_launch_tile_order(im, ntiles, false, R, !(debug & GSR_DEBUG_NO_SPLIT), s, col_pairs);
-	}
-	if ((rc = gsr_stage_done(s, debug, "tile_order"))) return rc;
-	{
-		GsrProfScope p(s, "render_forward");
+	// (measured at C3: the forward's own order is worth 33 us of blend time for ~12 us of this kernel and its launch)
+	if (R > 0 && (rc = gsr_stage(s, debug, "tile_order", [&] { gsr_launch_tile_order(f.img, ntiles, false, R, !(debug & GSR_DEBUG_NO_SPLIT), s, col_pairs); })))
+		return rc;
+	return gsr_stage(s, debug, "render_forward", [&] {
 		GsrAuxBlend x;
-		gsr_launch_render_forward(width, height, im, b.point_list, g.splat, b.checkpoints, background, out_color, R > 0, !(debug & GSR_DEBUG_NO_CULL), s,
-		                          gsr_aux_view(aux, R, width, height, &x));
-	}
-	return gsr_stage_done(s, debug, "render_forward");
+		gsr_launch_render_forward(f, background, out_color, R > 0, gsr_aux_view(aux, R, width, height, &x));
+	});
 }
 
 extern "C" int gsr_forward_render(int P, int64_t R, int width, int height, const float* background,
                                   const int* radii, void* geometry, void* binning, void* image, float* out_color,
                                   void* stream, int debug)
 {
-	return gsr_forward_render_impl(P, R, width, height, background, radii, geometry, binning, image, out_color, stream, debug, nullptr);
+	return gsr_forward_render_impl(P, R, width, height, background, geometry, binning, image, out_color, stream, debug, nullptr);
 }
 
 extern "C" int gsr_forward_render_aux(const gsr_aux_args* aux, int P, int64_t R, int width, int height, const float* background,
@@ -934,18 +987,21 @@ extern "C" int gsr_forward_render_aux(const gsr_aux_args* aux, int P, int64_t R,
 {
 	int rc;
 	if ((rc = gsr_option_check("gsr_forward_render_aux", 0, aux, false, GSR_AUX_NEEDS_OUTPUTS, P > 0))) return rc;
-	return gsr_forward_render_impl(P, R, width, height, background, radii, geometry, binning, image, out_color, stream, debug, aux);
+	return gsr_forward_render_impl(P, R, width, height, background, geometry, binning, image, out_color, stream, debug, aux);
 }
 
 // ---- backward ----------------------------------------------------------------------------------
+// The checks that the two stages of the backward make of their gsr_backward_args, then the frame.  P == 0: GSR_OK, *f is not opened.
 // has_model: a camera model stands in for projmatrix (include/gsr_camera_model.h)
-static int gsr_backward_check(const gsr_backward_args& a, const char* who, bool has_model = false)
+static int gsr_backward_open(GsrFrame* f, const gsr_backward_args* args, const char* who, bool has_model)
 {
-	if (a.P < 0 || a.num_rendered < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, args))) return rc;
+	const gsr_backward_args& a = *args;
 	if (a.P == 0) return GSR_OK;
-	if (!a.background || !a.means3D || !a.viewmatrix || (!a.projmatrix && !has_model) || !a.geometry || !a.image || !a.dL_dpix ||
-	    !a.dL_dmean2D || !a.dL_dopacity || !a.dL_dmean3D || !a.dL_dscale || !a.dL_drot || (a.num_rendered > 0 && (!a.binning || !a.scratch)))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: required pointer is NULL");
+	if (!a.background || !a.means3D || !a.viewmatrix || (!a.projmatrix && !has_model) || !a.dL_dpix || !a.dL_dmean2D || !a.dL_dopacity ||
+	    !a.dL_dmean3D || !a.dL_dscale || !a.dL_drot)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
 	// dL_dconic is an intermediate; dL_dcolor / dL_dcov3D are only results when the colours / covariances were
 	// inputs (or, dL_dcolor, in view-parallel mode): NULL = not written
 	if (!a.leaf && ((a.colors_precomp && !a.dL_dcolor) || (a.cov3D_precomp && !a.dL_dcov3D) || (a.shs && !a.dL_dsh && !a.dL_dcolor)))
@@ -961,88 +1017,56 @@ static int gsr_backward_check(const gsr_backward_args& a, const char* who, bool 
 	}
 	if (a.stat_max_radii2D && !a.radii)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward: stat_max_radii2D needs radii");
-	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(a.scratch))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "state buffers must be 16-byte aligned");
-	return GSR_OK;
-}
-
-// Validity bytes of the gradient slots: the tile sort's dead ping-pong buffer, cleared at the end of the forward.
-// Which slots get written depends on the forward alone (not on dL_dpix), so a second backward over the
-// same forward state (retain_graph) finds exactly the bytes it would set itself.
-static uint8_t* gsr_slot_valid_of(const gsr_backward_args& a)
-{
-	if (a.num_rendered <= 0) return nullptr;
-	return (uint8_t*)gsr_binning_view(a.binning, a.P, a.num_rendered, a.width, a.height).tile_keys_alt;
+	return gsr_frame_open(f, who, GSR_FRAME_IMAGE | GSR_FRAME_SLOTS, a, true);   // (the backward has never limited R)
 }
 
 // absgrad: the ABS variant of the blend kernel (include/gsr_absgrad.h)
-static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_args* aux, bool absgrad = false)
+static int gsr_backward_blend_impl(const gsr_backward_args* args, const gsr_aux_args* aux, bool absgrad)
 {
-	g_err[0] = 0;
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_blend: args is NULL");
-	const gsr_backward_args& a = *args;
+	GsrFrame f;
 	int rc;
-	if ((rc = gsr_backward_check(a, "gsr_backward_blend"))) return rc;
-	if (a.P == 0 || a.num_rendered == 0) return GSR_OK;
-	hipStream_t s = (hipStream_t)a.stream;
-	GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
-	GsrImage im = gsr_image_view(a.image, a.width, a.height);
-	GsrBinning b = gsr_binning_view(a.binning, a.P, a.num_rendered, a.width, a.height);
-	{
-		GsrProfScope p(s, "tile_order");
-		gsr_launch_tile_order(im, gsr_grid_x(a.width) * gsr_grid_y(a.height), true, a.num_rendered, !(a.debug & GSR_DEBUG_NO_SPLIT), s);
-	}
-	if ((rc = gsr_stage_done(s, a.debug, "tile_order"))) return rc;
-	{
-		// (recorded alone -- bench.py's timed region -- the kernel's dispatch packet takes the timestamps itself)
-		hipEvent_t t0 = nullptr, t1 = nullptr;
-		const bool own = gsr_prof_kernel_events(s, "render_backward", &t0, &t1);
-		GsrProfScope p(s, own ? nullptr : "render_backward");
+	if ((rc = gsr_backward_open(&f, args, "gsr_backward_blend", false))) return rc;
+	if (args->P == 0 || args->num_rendered == 0) return GSR_OK;
+	rc = gsr_stage(f.s, f.debug, "tile_order", [&] {
+		gsr_launch_tile_order(f.img, gsr_grid_x(f.W) * gsr_grid_y(f.H), true, f.R, !(f.debug & GSR_DEBUG_NO_SPLIT), f.s);
+	});
+	if (rc) return rc;
+	// (recorded alone -- bench.py's timed region -- the kernel's dispatch packet takes the timestamps itself)
+	hipEvent_t t0 = nullptr, t1 = nullptr;
+	const bool own = gsr_prof_kernel_events(f.s, "render_backward", &t0, &t1);
+	return gsr_stage(f.s, f.debug, "render_backward", [&] {
 		GsrAuxBlend x;
-		gsr_launch_render_backward(a.width, a.height, im, b.point_list, g.splat, b.checkpoints, g.slot_base, a.background, a.dL_dpix,
-		                           (GsrGradSlot*)a.scratch, (uint8_t*)b.tile_keys_alt, !(a.debug & GSR_DEBUG_NO_CULL), s, t0, t1,
-		                           gsr_aux_view(aux, a.num_rendered, a.width, a.height, &x), absgrad);
-	}
-	return gsr_stage_done(s, a.debug, "render_backward");
+		gsr_launch_render_backward(f, args->background, args->dL_dpix, t0, t1, gsr_aux_view(aux, f.R, f.W, f.H, &x), absgrad);
+	}, !own);
 }
 
-extern "C" int gsr_backward_blend(const gsr_backward_args* args) { return gsr_backward_blend_impl(args, nullptr); }
+extern "C" int gsr_backward_blend(const gsr_backward_args* args) { return gsr_backward_blend_impl(args, nullptr, false); }
 
 extern "C" int gsr_backward_blend_aux(const gsr_backward_args* args, const gsr_aux_args* aux)
 {
 	int rc;
 	if ((rc = gsr_option_check("gsr_backward_blend_aux", 0, aux, false, GSR_AUX_NEEDS_SCRATCH, args && args->P > 0 && args->num_rendered > 0))) return rc;
-	return gsr_backward_blend_impl(args, aux);
+	return gsr_backward_blend_impl(args, aux, false);
 }
 
-// aux: 0 or a GSR_AUX_* mode; aa_opacities: the anti-aliased kernels with this opacity input (include/gsr_aa.h), NULL: the default ones
-// cam: NULL, or the camera gradients (include/gsr_cam.h; checked by the caller): the twin kernels, then the fold of their rows
-// cm: NULL, or a checked camera model (include/gsr_camera_model.h; never with cam): its twin kernels
-// camk: NULL, or the camera gradients under the model cm (include/gsr_cam_cm.h; checked by the caller, never with cam): the kernels
-//       that are both twins, then the fold of their rows
-static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, int aux, const float* aa_opacities,
-                                       const gsr_cam_args* cam = nullptr, const gsr_camera_model* cm = nullptr,
-                                       const gsr_cam_cm_args* camk = nullptr)
+// o.cam.rows: the twin kernels that also store the camera rows, then the fold of those rows
+static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first, int count, int out_row0, const GsrGaussianOptions& o)
 {
-	g_err[0] = 0;
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: args is NULL");
-	const gsr_backward_args& b = *args;
+	GsrFrame f;
 	int rc;
-	if ((rc = gsr_backward_check(b, "gsr_backward_gaussians", cm != nullptr))) return rc;
+	if ((rc = gsr_backward_open(&f, args, "gsr_backward_gaussians", o.cm != nullptr))) return rc;
+	const gsr_backward_args& b = *args;
 	if (first < 0 || count < 0 || (int64_t)first + count > b.P || (first & 63) || (out_row0 != 0 && out_row0 != first))
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians: bad range [%d, %d + %d) of %d Gaussians (first must be a multiple "
 		                "of 64, out_row0 must be 0 or first)", first, first, count, b.P);
 	hipStream_t s = (hipStream_t)b.stream;
-	float* const cam_rows = cam ? (float*)cam->scratch : camk ? (float*)camk->scratch : nullptr;
 	auto fold = [&](int nrows) {   // the rows of the per-Gaussian pass into the outputs, structural zeros included
-		{
-			GsrProfScope p(s, "camera_grad");
-			if (cam) gsr_launch_camera_grad_fold(cam_rows, nrows, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos, s);
-			else gsr_launch_cam_cm_fold(cam_rows, nrows, camk->dL_dviewmatrix, camk->dL_dintrinsics, camk->dL_dcampos, s);
-		}
-		return gsr_stage_done(s, b.debug, "camera_grad");
+		return gsr_stage(s, b.debug, "camera_grad", [&] {
+			if (o.cm) gsr_launch_cam_cm_fold(o.cam.rows, nrows, o.cam.dL_dviewmatrix, o.cam.dL_dmid, o.cam.dL_dcampos, s);
+			else gsr_launch_camera_grad_fold(o.cam.rows, nrows, o.cam.dL_dviewmatrix, o.cam.dL_dmid, o.cam.dL_dcampos, s);
+		});
 	};
-	if (cam_rows && count == 0) return fold(0);   // no Gaussian: the fold of no rows writes the zeros
+	if (o.cam.rows && count == 0) return fold(0);   // no Gaussian: the fold of no rows writes the zeros
 	if (count == 0) return GSR_OK;
 	GsrGaussianBackwardArgs a = {};
 	a.leaf = b.leaf; a.shs_rest = b.shs_rest; a.dL_dsh_rest = b.dL_dsh_rest;
@@ -1054,42 +1078,42 @@ static int gsr_backward_gaussians_impl(const gsr_backward_args* args, int first,
 	a.tan_fovx = b.tan_fovx; a.tan_fovy = b.tan_fovy;
 	a.focal_y = b.height / (2.0f * b.tan_fovy);
 	a.focal_x = b.width / (2.0f * b.tan_fovx);
-	if (cm) { a.focal_x = cm->fx; a.focal_y = cm->fy; }
-	a.radii = b.radii; a.g = gsr_geometry_view(b.geometry, b.P);
-	a.slots = (const GsrGradSlot*)b.scratch; a.slot_valid = gsr_slot_valid_of(b);
+	if (o.cm) { a.focal_x = o.cm->fx; a.focal_y = o.cm->fy; }
+	a.radii = b.radii; a.g = f.g;
+	a.slots = f.slots; a.slot_valid = f.slot_valid;
 	a.dL_dmean2D = b.dL_dmean2D; a.dL_dconic = b.dL_dconic; a.dL_dopacity = b.dL_dopacity; a.dL_dcolor = b.dL_dcolor;
 	a.dL_dmean3D = b.dL_dmean3D; a.dL_dcov3D = b.dL_dcov3D; a.dL_dsh = b.dL_dsh; a.dL_dscale = b.dL_dscale; a.dL_drot = b.dL_drot;
 	a.stat_xyz_gradient_accum = b.stat_xyz_gradient_accum; a.stat_denom = b.stat_denom; a.stat_max_radii2D = b.stat_max_radii2D;
-	{
-		GsrProfScope p(s, "gaussian_backward");
-		gsr_launch_gaussian_backward(a, aa_opacities, s, aux, cam_rows, cm);
-	}
-	if (!cam_rows) return gsr_stage_done(s, b.debug, "gaussian_backward");
-	if ((rc = gsr_stage_done(s, b.debug, "gaussian_backward"))) return rc;
+	rc = gsr_stage(s, b.debug, "gaussian_backward", [&] { gsr_launch_gaussian_backward(a, s, o); });
+	if (rc || !o.cam.rows) return rc;
 	return fold((int)gsr_cam_rows(count));
 }
 
 extern "C" int gsr_backward_gaussians(const gsr_backward_args* args, int first, int count, int out_row0)
 {
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, 0, nullptr);
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, GsrGaussianOptions{});
+}
+
+// the option entry points: the one check under the caller's name, then the pass
+static int gsr_backward_gaussians_opt(const char* who, bool aux_required, const gsr_backward_args* args, const gsr_camera_model* model, int antialiasing,
+                                      const float* opacities, const gsr_aux_args* aux, const GsrCamTarget* cam, int first, int count, int out_row0)
+{
+	GsrGaussianOptions o;
+	int rc;
+	// (the per-Gaussian pass reads the mode of aux alone; the scratch's alignment is checked as the blend's call does)
+	if ((rc = gsr_gaussian_options(&o, who, aux_required, GSR_AUX_NEEDS_SCRATCH, aux, antialiasing, opacities, model, cam, args, first, count))) return rc;
+	return gsr_backward_gaussians_impl(args, first, count, out_row0, o);
 }
 
 extern "C" int gsr_backward_gaussians_aux(const gsr_backward_args* args, const gsr_aux_args* aux, int first, int count, int out_row0)
 {
-	int rc;
-	// (the per-Gaussian pass reads the mode alone; the scratch's alignment is checked as the blend's call does)
-	if ((rc = gsr_option_check("gsr_backward_gaussians_aux", 0, aux, false, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux->mode, nullptr);
+	return gsr_backward_gaussians_opt("gsr_backward_gaussians_aux", true, args, nullptr, 0, nullptr, aux, nullptr, first, count, out_row0);
 }
 
 extern "C" int gsr_backward_gaussians_aa(const gsr_backward_args* args, int antialiasing, const float* opacities, const gsr_aux_args* aux,
                                          int first, int count, int out_row0)
 {
-	int rc;
-	if ((rc = gsr_option_check("gsr_backward_gaussians_aa", antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
-	if (antialiasing && args && args->P > 0 && count > 0 && !opacities)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_backward_gaussians_aa: the opacity input is NULL");
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr);
+	return gsr_backward_gaussians_opt("gsr_backward_gaussians_aa", false, args, nullptr, antialiasing, opacities, aux, nullptr, first, count, out_row0);
 }
 
 // a camera model (include/gsr_camera_model.h): model NULL = gsr_backward_gaussians_aa
@@ -1097,15 +1121,7 @@ extern "C" int gsr_backward_gaussians_cm(const gsr_backward_args* args, const gs
                                          const gsr_aux_args* aux, int first, int count, int out_row0)
 {
 	if (!model) return gsr_backward_gaussians_aa(args, antialiasing, opacities, aux, first, count, out_row0);
-	const char* who = "gsr_backward_gaussians_cm";
-	int rc;
-	if ((rc = gsr_camera_model_check(who, *model))) return rc;
-	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
-	if (args->P < 0 || args->num_rendered < 0 || args->width <= 0 || args->height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-	if (args->P > 0 && !args->geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
-	if (antialiasing && args->P > 0 && count > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, nullptr, model);
+	return gsr_backward_gaussians_opt("gsr_backward_gaussians_cm", false, args, model, antialiasing, opacities, aux, nullptr, first, count, out_row0);
 }
 
 // ---- camera gradients (include/gsr_cam.h) ----
@@ -1115,20 +1131,8 @@ extern "C" int gsr_backward_gaussians_cam(const gsr_backward_args* args, int ant
                                           const gsr_cam_args* cam, int first, int count, int out_row0)
 {
 	if (!cam) return gsr_backward_gaussians_aa(args, antialiasing, opacities, aux, first, count, out_row0);
-	const char* who = "gsr_backward_gaussians_cam";
-	int rc;
-	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
-	if (!cam->dL_dviewmatrix || !cam->dL_dprojmatrix || !cam->dL_dcampos)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dviewmatrix, dL_dprojmatrix or dL_dcampos is NULL", who);
-	if (!cam->scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam is NULL", who);
-	if (!aligned16(cam->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam must be 16-byte aligned", who);
-	if (first != 0 || count != args->P)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera gradients need the whole scene in one call (first 0, count %d; got %d, %d): "
-		                "the part-by-part pipeline of view-parallel mode has no camera form", who, args->P, first, count);
-	if (args->P > 0 && args->shs && !args->cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
-	if (antialiasing && args->P > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, cam);
+	const GsrCamTarget t = {(float*)cam->scratch, cam->dL_dviewmatrix, cam->dL_dprojmatrix, cam->dL_dcampos};
+	return gsr_backward_gaussians_opt("gsr_backward_gaussians_cam", false, args, nullptr, antialiasing, opacities, aux, &t, first, count, out_row0);
 }
 
 // ---- camera gradients under a camera model (include/gsr_cam_cm.h) ----
@@ -1140,23 +1144,9 @@ extern "C" int gsr_backward_gaussians_cam_cm(const gsr_backward_args* args, cons
 {
 	if (!cam) return gsr_backward_gaussians_cm(args, model, antialiasing, opacities, aux, first, count, out_row0);
 	const char* who = "gsr_backward_gaussians_cam_cm";
-	int rc;
 	if (!model) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the camera model is NULL (without one the camera gradients are gsr_backward_gaussians_cam's)", who);
-	if ((rc = gsr_camera_model_check(who, *model))) return rc;
-	if ((rc = gsr_option_check(who, antialiasing, aux, true, GSR_AUX_NEEDS_SCRATCH, false))) return rc;
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
-	if (args->P < 0 || args->num_rendered < 0 || args->width <= 0 || args->height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-	if (!cam->dL_dviewmatrix || !cam->dL_dintrinsics || !cam->dL_dcampos)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dviewmatrix, dL_dintrinsics or dL_dcampos is NULL", who);
-	if (!cam->scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam is NULL", who);
-	if (!aligned16(cam->scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scratch of cam must be 16-byte aligned", who);
-	if (first != 0 || count != args->P)
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera gradients need the whole scene in one call (first 0, count %d; got %d, %d): "
-		                "the part-by-part pipeline of view-parallel mode has no camera form", who, args->P, first, count);
-	if (args->P > 0 && !args->geometry) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: geometry is NULL", who);
-	if (args->P > 0 && args->shs && !args->cam_pos) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cam_pos is NULL", who);
-	if (antialiasing && args->P > 0 && !opacities) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity input is NULL", who);
-	return gsr_backward_gaussians_impl(args, first, count, out_row0, aux ? aux->mode : 0, antialiasing ? opacities : nullptr, nullptr, model, cam);
+	const GsrCamTarget t = {(float*)cam->scratch, cam->dL_dviewmatrix, cam->dL_dintrinsics, cam->dL_dcampos};
+	return gsr_backward_gaussians_opt(who, false, args, model, antialiasing, opacities, aux, &t, first, count, out_row0);
 }
 
 static int gsr_backward_whole(const gsr_backward_args& a)
@@ -1220,26 +1210,20 @@ extern "C" int gsr_backward_blend_abs(const gsr_backward_args* args, const gsr_a
 
 extern "C" int gsr_absgrad_fold(const gsr_backward_args* args, const gsr_absgrad_args* abs, int first, int count)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_absgrad_fold";
 	if (!args || !abs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args or abs is NULL", who);
 	const gsr_backward_args& a = *args;
-	if (a.P < 0 || a.num_rendered < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, args))) return rc;
 	if (first < 0 || count < 0 || (int64_t)first + count > a.P)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad range [%d, %d + %d) of %d Gaussians", who, first, first, count, a.P);
 	if (!abs->abs_dL_dmean2D && !abs->stat_abs_gradient_accum)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: abs_dL_dmean2D and stat_abs_gradient_accum are both NULL", who);
 	if (count == 0) return GSR_OK;
-	if (!a.geometry || (a.num_rendered > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(a.geometry) || !aligned16(a.binning) || !aligned16(a.scratch))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
-	hipStream_t s = (hipStream_t)a.stream;
-	{
-		GsrProfScope p(s, "absgrad_fold");
-		gsr_launch_absgrad_fold(first, count, gsr_geometry_view(a.geometry, a.P), a.radii, (const GsrGradSlot*)a.scratch, gsr_slot_valid_of(a),
-		                        abs->abs_dL_dmean2D, abs->stat_abs_gradient_accum, s);
-	}
-	return gsr_stage_done(s, a.debug, "absgrad_fold");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_SLOTS, a, true))) return rc;
+	return gsr_stage(f.s, f.debug, "absgrad_fold",
+	                 [&] { gsr_launch_absgrad_fold(f, first, count, a.radii, abs->abs_dL_dmean2D, abs->stat_abs_gradient_accum); });
 }
 
 // ---- blend-weight statistics (include/gsr_contrib.h) --------------------------------------------
@@ -1254,32 +1238,24 @@ extern "C" int gsr_contributions(int P, int64_t R, int width, int height, const 
                                  const float* pixel_weight, float* weight_sum, float* weight_max, int32_t* pixel_count, void* scratch,
                                  void* stream, int debug)
 {
-	g_err[0] = 0;
-	hipStream_t s = (hipStream_t)stream;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: bad sizes");
-	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
-	if (!weight_sum && !weight_max && !pixel_count) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: all three outputs are NULL");
-	if (!geometry || !image || (R > 0 && (!binning || !scratch)))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_contributions: required pointer is NULL");
-	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(scratch))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "state buffers and scratch must be 16-byte aligned");
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "num_rendered exceeds 32-bit offsets");
-	if (R == 0) return GSR_OK;   // nothing blended: every Gaussian is left untouched
-	GsrGeometry g = gsr_geometry_view((void*)geometry, P);
-	GsrImage im = gsr_image_view((void*)image, width, height);
-	GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
+	const char* who = "gsr_contributions";
 	int rc;
-	{
-		GsrProfScope p(s, "contrib_tiles");   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
-		if ((rc = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_contrib_valid_offset(R), 0, (size_t)R, s), "hipMemsetAsync(contrib validity)"))) return rc;
-		gsr_launch_contrib_tiles(width, height, im, b.point_list, g.splat, g.slot_base, pixel_weight, scratch, R, !(debug & GSR_DEBUG_NO_CULL), s);
-	}
-	if ((rc = gsr_stage_done(s, debug, "contrib_tiles"))) return rc;
-	{
-		GsrProfScope p(s, "contrib_gaussians");
-		gsr_launch_contrib_gaussians(P, g, scratch, R, weight_sum, weight_max, pixel_count, s);
-	}
-	return gsr_stage_done(s, debug, "contrib_gaussians");
+	if ((rc = gsr_frame_sizes(who, P, R, width, height))) return rc;
+	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
+	if (!weight_sum && !weight_max && !pixel_count) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: all three outputs are NULL", who);
+	if (R > 0 && !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32, P, R, width, height, geometry, binning, image, nullptr, stream, debug,
+	                         aligned16(scratch))))
+		return rc;
+	if (R == 0) return GSR_OK;   // nothing blended: every Gaussian is left untouched
+	rc = gsr_stage(f.s, debug, "contrib_tiles", [&] {   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
+		const int e = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_contrib_valid_offset(R), 0, (size_t)R, f.s), "hipMemsetAsync(contrib validity)");
+		if (!e) gsr_launch_contrib_tiles(f, pixel_weight, scratch);
+		return e;
+	});
+	if (rc) return rc;
+	return gsr_stage(f.s, debug, "contrib_gaussians", [&] { gsr_launch_contrib_gaussians(f, scratch, weight_sum, weight_max, pixel_count); });
 }
 
 // ---- blended feature channels (include/gsr_features.h) ---------------------------------------------
@@ -1295,74 +1271,48 @@ extern "C" size_t gsr_features_scratch_bytes(int P, int64_t R, int K)
 extern "C" int gsr_features_forward(int P, int64_t R, int width, int height, int K, const void* geometry, const void* binning, const void* image,
                                     const float* features, float* out, void* stream, int debug)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_features_forward";
-	hipStream_t s = (hipStream_t)stream;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, P, R, width, height))) return rc;
 	if (K < 1 || K > GSR_FEATURES_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must be in [1, %d], got %d", who, GSR_FEATURES_MAX_K, K);
 	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
 	if (!features || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: features or out is NULL", who);
-	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	int rc;
-	{
-		GsrProfScope p(s, "features_forward");
-		if (R == 0) {   // nothing blended: the map is zeros
-			if ((rc = gsr_check_hip(hipMemsetAsync(out, 0, (size_t)K * height * width * sizeof(float), s), "hipMemsetAsync(feature map)"))) return rc;
-		} else {
-			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
-			GsrImage im = gsr_image_view((void*)image, width, height);
-			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
-			gsr_launch_features_forward(width, height, K, im, b.point_list, g.splat, features, out, !(debug & GSR_DEBUG_NO_CULL), s);
-		}
-	}
-	return gsr_stage_done(s, debug, "features_forward");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32, P, R, width, height, geometry, binning, image, nullptr, stream, debug, true))) return rc;
+	return gsr_stage(f.s, debug, "features_forward", [&] {
+		if (R == 0)   // nothing blended: the map is zeros
+			return gsr_check_hip(hipMemsetAsync(out, 0, (size_t)K * height * width * sizeof(float), f.s), "hipMemsetAsync(feature map)");
+		gsr_launch_features_forward(f, K, features, out);
+		return (int)GSR_OK;
+	});
 }
 
 extern "C" int gsr_features_backward(const gsr_backward_args* args, int K, const float* features, const float* dL_dout, float* dL_dfeatures,
                                      void* scratch, int into_slots)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_features_backward";
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, args))) return rc;
 	const gsr_backward_args& a = *args;
 	const int64_t R = a.num_rendered;
-	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
 	if (K < 1 || K > GSR_FEATURES_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must be in [1, %d], got %d", who, GSR_FEATURES_MAX_K, K);
 	if (into_slots != 0 && into_slots != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: into_slots must be 0 or 1, got %d", who, into_slots);
 	if (a.P == 0) return GSR_OK;
 	if (!features || !dL_dout || !dL_dfeatures) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: features, dL_dout or dL_dfeatures is NULL", who);
-	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !scratch || (into_slots && !a.scratch))))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(scratch) || (into_slots && !aligned16(a.scratch)))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	hipStream_t s = (hipStream_t)a.stream;
-	int rc;
-	if (R == 0) {   // nothing blended: every gradient is zero
-		{
-			GsrProfScope p(s, "features_backward_fold");
-			if ((rc = gsr_check_hip(hipMemsetAsync(dL_dfeatures, 0, (size_t)a.P * K * sizeof(float), s), "hipMemsetAsync(dL_dfeatures)"))) return rc;
-		}
-		return gsr_stage_done(s, a.debug, "features_backward_fold");
-	}
-	GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
-	GsrImage im = gsr_image_view(a.image, a.width, a.height);
-	GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
-	{
-		GsrProfScope p(s, "features_backward_tiles");   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
-		if ((rc = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_features_valid_offset(R, K), 0, (size_t)R, s), "hipMemsetAsync(features validity)"))) return rc;
-		gsr_launch_features_backward_tiles(a.width, a.height, K, R, im, b.point_list, g.splat, g.slot_base, features, dL_dout, scratch,
-		                                   into_slots ? (GsrGradSlot*)a.scratch : nullptr, !(a.debug & GSR_DEBUG_NO_CULL), s);
-	}
-	if ((rc = gsr_stage_done(s, a.debug, "features_backward_tiles"))) return rc;
-	{
-		GsrProfScope p(s, "features_backward_fold");
-		gsr_launch_features_fold(a.P, K, R, g, scratch, dL_dfeatures, s);
-	}
-	return gsr_stage_done(s, a.debug, "features_backward_fold");
+	if (R > 0 && !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	GsrFrame f;   // (into_slots = 0: the slots are neither needed nor passed on)
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32 | (into_slots ? GSR_FRAME_SLOTS : 0), a, aligned16(scratch)))) return rc;
+	if (R == 0)   // nothing blended: every gradient is zero
+		return gsr_stage(f.s, f.debug, "features_backward_fold", [&] {
+			return gsr_check_hip(hipMemsetAsync(dL_dfeatures, 0, (size_t)a.P * K * sizeof(float), f.s), "hipMemsetAsync(dL_dfeatures)");
+		});
+	rc = gsr_stage(f.s, f.debug, "features_backward_tiles", [&] {   // (with the clearing of the validity bytes: the caller's scratch may be uninitialised)
+		const int e = gsr_check_hip(hipMemsetAsync((uint8_t*)scratch + gsr_features_valid_offset(R, K), 0, (size_t)R, f.s), "hipMemsetAsync(features validity)");
+		if (!e) gsr_launch_features_backward_tiles(f, K, features, dL_dout, scratch);
+		return e;
+	});
+	if (rc) return rc;
+	return gsr_stage(f.s, f.debug, "features_backward_fold", [&] { gsr_launch_features_fold(f, K, scratch, dL_dfeatures); });
 }
 
 // ---- depth-distortion map (include/gsr_distortion.h) ------------------------------------------------
@@ -1375,58 +1325,37 @@ extern "C" size_t gsr_distortion_state_bytes(int width, int height)
 extern "C" int gsr_distortion_forward(int P, int64_t R, int width, int height, const void* geometry, const void* binning, const void* image,
                                       float* out_dist, void* state, void* stream, int debug)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_distortion_forward";
-	hipStream_t s = (hipStream_t)stream;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, P, R, width, height))) return rc;
 	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
 	if (!out_dist || !state) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: out_dist or state is NULL", who);
-	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(state))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	int rc;
-	{
-		GsrProfScope p(s, "distortion_forward");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32, P, R, width, height, geometry, binning, image, nullptr, stream, debug,
+	                         aligned16(state))))
+		return rc;
+	return gsr_stage(f.s, debug, "distortion_forward", [&] {
 		if (R == 0) {   // nothing blended: the map and the state are zeros
 			const size_t plane = (size_t)height * width * sizeof(float);
-			if ((rc = gsr_check_hip(hipMemsetAsync(out_dist, 0, plane, s), "hipMemsetAsync(distortion map)"))) return rc;
-			if ((rc = gsr_check_hip(hipMemsetAsync(state, 0, 3 * plane, s), "hipMemsetAsync(distortion state)"))) return rc;
-		} else {
-			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
-			GsrImage im = gsr_image_view((void*)image, width, height);
-			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
-			gsr_launch_distortion_forward(width, height, im, b.point_list, g.splat, out_dist, (float*)state, !(debug & GSR_DEBUG_NO_CULL), s);
+			if (int e = gsr_check_hip(hipMemsetAsync(out_dist, 0, plane, f.s), "hipMemsetAsync(distortion map)")) return e;
+			return gsr_check_hip(hipMemsetAsync(state, 0, 3 * plane, f.s), "hipMemsetAsync(distortion state)");
 		}
-	}
-	return gsr_stage_done(s, debug, "distortion_forward");
+		gsr_launch_distortion_forward(f, out_dist, (float*)state);
+		return (int)GSR_OK;
+	});
 }
 
 extern "C" int gsr_distortion_backward(const gsr_backward_args* args, const void* state, const float* dL_ddist)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_distortion_backward";
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
-	const gsr_backward_args& a = *args;
-	const int64_t R = a.num_rendered;
-	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-	if (a.P == 0) return GSR_OK;
+	int rc;
+	if ((rc = gsr_frame_sizes(who, args))) return rc;
+	if (args->P == 0) return GSR_OK;
 	if (!state || !dL_ddist) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state or dL_ddist is NULL", who);
-	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(a.scratch) || !aligned16(state))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	if (R == 0) return GSR_OK;   // nothing blended: no slot to add into
-	hipStream_t s = (hipStream_t)a.stream;
-	{
-		GsrProfScope p(s, "distortion_backward");
-		GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
-		GsrImage im = gsr_image_view(a.image, a.width, a.height);
-		GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
-		gsr_launch_distortion_backward(a.width, a.height, im, b.point_list, g.splat, g.slot_base, (const float*)state, dL_ddist,
-		                               (GsrGradSlot*)a.scratch, !(a.debug & GSR_DEBUG_NO_CULL), s);
-	}
-	return gsr_stage_done(s, a.debug, "distortion_backward");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_SLOTS | GSR_FRAME_R32, *args, aligned16(state)))) return rc;
+	if (f.R == 0) return GSR_OK;   // nothing blended: no slot to add into
+	return gsr_stage(f.s, f.debug, "distortion_backward", [&] { gsr_launch_distortion_backward(f, (const float*)state, dL_ddist); });
 }
 
 // ---- median-depth and per-pixel index maps (include/gsr_median.h) -----------------------------------
@@ -1440,62 +1369,43 @@ extern "C" int gsr_median_forward(int P, int64_t R, int width, int height, const
                                   float* out_median_depth, int32_t* out_median_index, int32_t* out_dominant_index, float* out_dominant_weight,
                                   void* state, void* stream, int debug)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_median_forward";
-	hipStream_t s = (hipStream_t)stream;
-	if (P < 0 || R < 0 || width <= 0 || height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
+	int rc;
+	if ((rc = gsr_frame_sizes(who, P, R, width, height))) return rc;
 	if (P == 0) return GSR_OK;   // (no Gaussian: an empty array's address means nothing)
 	if (!out_median_depth && !out_median_index && !out_dominant_index && !out_dominant_weight)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every output is NULL", who);
 	if (out_median_depth && !state) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: out_median_depth needs state", who);
-	if (!geometry || !image || (R > 0 && !binning)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(geometry) || !aligned16(image) || !aligned16(binning) || !aligned16(state))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	int rc;
-	{
-		GsrProfScope p(s, "median_forward");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_R32, P, R, width, height, geometry, binning, image, nullptr, stream, debug,
+	                         aligned16(state))))
+		return rc;
+	return gsr_stage(f.s, debug, "median_forward", [&] {
 		if (R == 0) {   // nothing blended: depth and weight 0, indices -1, no position in the state
 			const size_t plane = (size_t)height * width * 4;
 			void* const outs[5] = {out_median_depth, out_dominant_weight, out_median_index, out_dominant_index, state};
 			for (int i = 0; i < 5; i++)
-				if (outs[i] && (rc = gsr_check_hip(hipMemsetAsync(outs[i], i < 2 ? 0 : 0xFF, plane, s), "hipMemsetAsync(median maps)"))) return rc;
-		} else {
-			GsrGeometry g = gsr_geometry_view((void*)geometry, P);
-			GsrImage im = gsr_image_view((void*)image, width, height);
-			GsrBinning b = gsr_binning_view((void*)binning, P, R, width, height);
-			gsr_launch_median_forward(width, height, im, b.point_list, g.splat, out_median_depth, out_median_index, out_dominant_index,
-			                          out_dominant_weight, (uint32_t*)state, !(debug & GSR_DEBUG_NO_CULL), (debug & GSR_DEBUG_MEDIAN_FULL_WALK) != 0, s);
+				if (outs[i])
+					if (int e = gsr_check_hip(hipMemsetAsync(outs[i], i < 2 ? 0 : 0xFF, plane, f.s), "hipMemsetAsync(median maps)")) return e;
+			return (int)GSR_OK;
 		}
-	}
-	return gsr_stage_done(s, debug, "median_forward");
+		gsr_launch_median_forward(f, out_median_depth, out_median_index, out_dominant_index, out_dominant_weight, (uint32_t*)state,
+		                          (debug & GSR_DEBUG_MEDIAN_FULL_WALK) != 0);
+		return (int)GSR_OK;
+	});
 }
 
 extern "C" int gsr_median_backward(const gsr_backward_args* args, const void* state, const float* dL_dmedian)
 {
-	g_err[0] = 0;
 	const char* who = "gsr_median_backward";
-	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: args is NULL", who);
-	const gsr_backward_args& a = *args;
-	const int64_t R = a.num_rendered;
-	if (a.P < 0 || R < 0 || a.width <= 0 || a.height <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad sizes", who);
-	if (a.P == 0) return GSR_OK;
+	int rc;
+	if ((rc = gsr_frame_sizes(who, args))) return rc;
+	if (args->P == 0) return GSR_OK;
 	if (!state || !dL_dmedian) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state or dL_dmedian is NULL", who);
-	if (!a.geometry || !a.image || (R > 0 && (!a.binning || !a.scratch))) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
-	if (!aligned16(a.geometry) || !aligned16(a.image) || !aligned16(a.binning) || !aligned16(a.scratch) || !aligned16(state))
-		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: state buffers and scratch must be 16-byte aligned", who);
-	if (R > 0xffffffffLL) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: num_rendered exceeds 32-bit offsets", who);
-	if (R == 0) return GSR_OK;   // nothing blended: no slot to add into
-	hipStream_t s = (hipStream_t)a.stream;
-	{
-		GsrProfScope p(s, "median_backward");
-		GsrGeometry g = gsr_geometry_view(a.geometry, a.P);
-		GsrImage im = gsr_image_view(a.image, a.width, a.height);
-		GsrBinning b = gsr_binning_view(a.binning, a.P, R, a.width, a.height);
-		gsr_launch_median_backward(a.width, a.height, im, b.point_list, g.splat, g.slot_base, (const uint32_t*)state, dL_dmedian,
-		                           (GsrGradSlot*)a.scratch, s);
-	}
-	return gsr_stage_done(s, a.debug, "median_backward");
+	GsrFrame f;
+	if ((rc = gsr_frame_open(&f, who, GSR_FRAME_IMAGE | GSR_FRAME_SLOTS | GSR_FRAME_R32, *args, aligned16(state)))) return rc;
+	if (f.R == 0) return GSR_OK;   // nothing blended: no slot to add into
+	return gsr_stage(f.s, f.debug, "median_backward", [&] { gsr_launch_median_backward(f, (const uint32_t*)state, dL_dmedian); });
 }
 
 // ---- per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h) ----

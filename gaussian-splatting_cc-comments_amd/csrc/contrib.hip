@@ -155,18 +155,16 @@ __global__ void __launch_bounds__(256) gsr_contrib_gaussians_kernel(int P, const
 
 size_t gsr_contrib_valid_offset(int64_t R) { return gsr_align_up((size_t)R * sizeof(GsrContribSlot)); }
 
-void gsr_launch_contrib_tiles(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                              const float* pixel_weight, void* scratch, int64_t R, bool cull, hipStream_t s)
+void gsr_launch_contrib_tiles(const GsrFrame& f, const float* pixel_weight, void* scratch)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H);
-	uint8_t* valid = (uint8_t*)scratch + gsr_contrib_valid_offset(R);
-	gsr_launch(gsr_contrib_tiles_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
-	           slot_base, img.n_contrib, img.tile_max_contrib, pixel_weight, (GsrContribSlot*)scratch, valid, cull ? 1 : 0);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
+	uint8_t* valid = (uint8_t*)scratch + gsr_contrib_valid_offset(f.R);
+	gsr_launch(gsr_contrib_tiles_kernel, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, f.img.ranges, f.bin.point_list, f.g.splat,
+	           f.g.slot_base, f.img.n_contrib, f.img.tile_max_contrib, pixel_weight, (GsrContribSlot*)scratch, valid, f.cull ? 1 : 0);
 }
 
-void gsr_launch_contrib_gaussians(int P, GsrGeometry g, const void* scratch, int64_t R, float* weight_sum, float* weight_max, int32_t* pixel_count,
-                                  hipStream_t s)
+void gsr_launch_contrib_gaussians(const GsrFrame& f, const void* scratch, float* weight_sum, float* weight_max, int32_t* pixel_count)
 {
-	gsr_launch(gsr_contrib_gaussians_kernel, dim3((P + 255) / 256), dim3(256), 0, s, nullptr, nullptr, P, g.tiles_touched, g.slot_base,
-	           (const GsrContribSlot*)scratch, (const uint8_t*)scratch + gsr_contrib_valid_offset(R), weight_sum, weight_max, pixel_count);
+	gsr_launch(gsr_contrib_gaussians_kernel, dim3((f.P + 255) / 256), dim3(256), 0, f.s, nullptr, nullptr, f.P, f.g.tiles_touched, f.g.slot_base,
+	           (const GsrContribSlot*)scratch, (const uint8_t*)scratch + gsr_contrib_valid_offset(f.R), weight_sum, weight_max, pixel_count);
 }

@@ -162,18 +162,16 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_distortion_backward
 	GSR_REPLAY(true, true, w, s_batch[w.wave], splat, slot_base, cull, pass);
 }
 
-void gsr_launch_distortion_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out, float* state,
-                                   bool cull, hipStream_t s)
+void gsr_launch_distortion_forward(const GsrFrame& f, float* out, float* state)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H);
-	gsr_launch(gsr_distortion_forward_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
-	           img.n_contrib, img.tile_max_contrib, out, state, cull ? 1 : 0);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
+	gsr_launch(gsr_distortion_forward_kernel, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, f.img.ranges, f.bin.point_list,
+	           f.g.splat, f.img.n_contrib, f.img.tile_max_contrib, out, state, f.cull ? 1 : 0);
 }
 
-void gsr_launch_distortion_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                                    const float* state, const float* dL_ddist, GsrGradSlot* slots, bool cull, hipStream_t s)
+void gsr_launch_distortion_backward(const GsrFrame& f, const float* state, const float* dL_ddist)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H);
-	gsr_launch(gsr_distortion_backward_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
-	           slot_base, img.final_T, img.n_contrib, img.tile_max_contrib, state, dL_ddist, slots, cull ? 1 : 0);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
+	gsr_launch(gsr_distortion_backward_kernel, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, f.img.ranges, f.bin.point_list,
+	           f.g.splat, f.g.slot_base, f.img.final_T, f.img.n_contrib, f.img.tile_max_contrib, state, dL_ddist, f.slots, f.cull ? 1 : 0);
 }

@@ -234,37 +234,35 @@ __global__ void __launch_bounds__(256) gsr_features_fold_kernel(int P, int K, ui
 int gsr_features_chunks(int K) { return (K + GSR_FEAT_CH - 1) / GSR_FEAT_CH; }
 size_t gsr_features_valid_offset(int64_t R, int K) { return gsr_align_up((size_t)gsr_features_chunks(K) * (size_t)R * sizeof(float4)); }
 
-void gsr_launch_features_forward(int W, int H, int K, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float* features,
-                                 float* out, bool cull, hipStream_t s)
+void gsr_launch_features_forward(const GsrFrame& f, int K, const float* features, float* out)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H, gsr_features_chunks(K));
-	gsr_launch(gsr_features_forward_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, K, img.ranges, point_list, splat,
-	           img.n_contrib, img.tile_max_contrib, features, out, cull ? 1 : 0);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H, gsr_features_chunks(K));
+	gsr_launch(gsr_features_forward_kernel, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, K, f.img.ranges, f.bin.point_list,
+	           f.g.splat, f.img.n_contrib, f.img.tile_max_contrib, features, out, f.cull ? 1 : 0);
 }
 
-void gsr_launch_features_backward_tiles(int W, int H, int K, int64_t R, GsrImage img, const uint32_t* point_list, const GsrSplat* splat,
-                                        const uint32_t* slot_base, const float* features, const float* dL_dout, void* scratch,
-                                        GsrGradSlot* slots, bool cull, hipStream_t s)
+void gsr_launch_features_backward_tiles(const GsrFrame& f, int K, const float* features, const float* dL_dout, void* scratch)
 {
 	const int nchunks = gsr_features_chunks(K);
-	const GsrTileGrid t = gsr_tile_grid(W, H);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
+	const GsrImage& img = f.img;
 	float4* frec = (float4*)scratch;
-	uint8_t* fvalid = (uint8_t*)scratch + gsr_features_valid_offset(R, K);
-	if (slots) {
+	uint8_t* fvalid = (uint8_t*)scratch + gsr_features_valid_offset(f.R, K);
+	if (f.slots) {
 		// one chunk per launch: the chunks' additions into the slots happen in launch order
 		for (int c = 0; c < nchunks; c++)
-			gsr_launch(gsr_features_backward_kernel<true>, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, K, c, (uint32_t)R, img.ranges,
-			           point_list, splat, slot_base, img.final_T, img.n_contrib, img.tile_max_contrib, features, dL_dout, frec, fvalid, slots,
-			           cull ? 1 : 0);
+			gsr_launch(gsr_features_backward_kernel<true>, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, K, c, (uint32_t)f.R, img.ranges,
+			           f.bin.point_list, f.g.splat, f.g.slot_base, img.final_T, img.n_contrib, img.tile_max_contrib, features, dL_dout, frec, fvalid,
+			           f.slots, f.cull ? 1 : 0);
 	} else {
-		gsr_launch(gsr_features_backward_kernel<false>, dim3(t.grid.x, nchunks), t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, K, 0, (uint32_t)R,
-		           img.ranges, point_list, splat, slot_base, img.final_T, img.n_contrib, img.tile_max_contrib, features, dL_dout, frec, fvalid,
-		           (GsrGradSlot*)nullptr, cull ? 1 : 0);
+		gsr_launch(gsr_features_backward_kernel<false>, dim3(t.grid.x, nchunks), t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, K, 0,
+		           (uint32_t)f.R, img.ranges, f.bin.point_list, f.g.splat, f.g.slot_base, img.final_T, img.n_contrib, img.tile_max_contrib, features, dL_dout,
+		           frec, fvalid, (GsrGradSlot*)nullptr, f.cull ? 1 : 0);
 	}
 }
 
-void gsr_launch_features_fold(int P, int K, int64_t R, GsrGeometry g, const void* scratch, float* dL_dfeatures, hipStream_t s)
+void gsr_launch_features_fold(const GsrFrame& f, int K, const void* scratch, float* dL_dfeatures)
 {
-	gsr_launch(gsr_features_fold_kernel, dim3((P + 255) / 256), dim3(256), 0, s, nullptr, nullptr, P, K, (uint32_t)R, g.tiles_touched, g.slot_base,
-	           (const float4*)scratch, (const uint8_t*)scratch + gsr_features_valid_offset(R, K), dL_dfeatures);
+	gsr_launch(gsr_features_fold_kernel, dim3((f.P + 255) / 256), dim3(256), 0, f.s, nullptr, nullptr, f.P, K, (uint32_t)f.R, f.g.tiles_touched,
+	           f.g.slot_base, (const float4*)scratch, (const uint8_t*)scratch + gsr_features_valid_offset(f.R, K), dL_dfeatures);
 }

@@ -626,7 +626,7 @@ __global__ void __launch_bounds__(GSR_GB_THREADS) gsr_gaussian_backward_kernel(
 
 // one instantiation per (LEAF, depth-and-alpha mode, AA): the AA ones are those that receive the struct with the opacity input
 template <typename Args>
-static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux, float* cam_partials, const gsr_camera_model* cm)
+static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, const GsrGaussianOptions& o)
 {
 	constexpr bool AA = std::is_same<Args, GsrGaussianBackwardArgsAA>::value;
 	// LDS-transposed SH path: the flagship layout (16 coefficients) with 16-byte aligned tensors
@@ -634,26 +634,26 @@ static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux
 	int sh_via_lds = (a.shs && a.M == 16 && ((uintptr_t)a.shs & 15u) == 0 && (skip_dsh || ((uintptr_t)a.dL_dsh & 15u) == 0)) ? 1 : 0;
 	if (a.leaf && (((uintptr_t)a.shs_rest & 15u) != 0 || (!skip_dsh && ((uintptr_t)a.dL_dsh_rest & 15u) != 0))) sh_via_lds = 0;
 	const dim3 grid((a.count + GSR_GB_THREADS - 1) / GSR_GB_THREADS);
-	gsr_variant(a.leaf, aux, AA, [&](auto LEAF, auto AUX, auto) {
-		if (cam_partials && cm) {   // camera gradients under a model (include/gsr_cam_cm.h): the model's arguments with the row pointer behind them
+	gsr_variant(a.leaf, o.aux, AA, [&](auto LEAF, auto AUX, auto) {
+		if (o.cam.rows && o.cm) {   // camera gradients under a model (include/gsr_cam_cm.h): the model's arguments with the row pointer behind them
 			GsrGaussianBackwardCam<GsrWithCameraModel<Args>> c;
 			static_cast<Args&>(c) = a;
-			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
-			c.cam_partials = cam_partials;
+			c.cm_model = o.cm->model; c.cm_cx = o.cm->cx; c.cm_cy = o.cm->cy;
+			c.cam_partials = o.cam.rows;
 			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
 			return;
 		}
-		if (cam_partials) {   // the camera-gradient twin (include/gsr_cam.h): the same arguments with the row pointer behind them
+		if (o.cam.rows) {   // the camera-gradient twin (include/gsr_cam.h): the same arguments with the row pointer behind them
 			GsrGaussianBackwardCam<Args> c;
 			static_cast<Args&>(c) = a;
-			c.cam_partials = cam_partials;
+			c.cam_partials = o.cam.rows;
 			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, true, false>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
 			return;
 		}
-		if (cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
+		if (o.cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
 			GsrWithCameraModel<Args> c;
 			static_cast<Args&>(c) = a;
-			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
+			c.cm_model = o.cm->model; c.cm_cx = o.cm->cx; c.cm_cy = o.cm->cy;
 			gsr_launch(gsr_gaussian_backward_kernel<LEAF(), AUX(), AA, false, true>, grid, dim3(GSR_GB_THREADS), 0, s, nullptr, nullptr, c, sh_via_lds, skip_dsh);
 			return;
 		}
@@ -662,14 +662,13 @@ static void gsr_launch_gaussian_backward_t(const Args& a, hipStream_t s, int aux
 	});
 }
 
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials,
-                                  const gsr_camera_model* cm)
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, const GsrGaussianOptions& o)
 {
-	if (!aa_opacities) return gsr_launch_gaussian_backward_t(a, s, aux, cam_partials, cm);
+	if (!o.aa_opacities) return gsr_launch_gaussian_backward_t(a, s, o);
 	GsrGaussianBackwardArgsAA x;
 	static_cast<GsrGaussianBackwardArgs&>(x) = a;
-	x.opacities = aa_opacities;
-	gsr_launch_gaussian_backward_t(x, s, aux, cam_partials, cm);
+	x.opacities = o.aa_opacities;
+	gsr_launch_gaussian_backward_t(x, s, o);
 }
 
 // ---- fold of the camera partials (include/gsr_cam.h) ---------------------------------------------------------------------------

@@ -108,6 +108,45 @@ GsrGeometry gsr_geometry_view(void* blob, int P);
 GsrImage gsr_image_view(void* blob, int W, int H);
 GsrBinning gsr_binning_view(void* blob, int P, int64_t R, int W, int H);
 
+// The state of one forward as every call after stage 1 sees it, checked and opened in one place (api.hip, gsr_frame_open).  img is
+// zero when the call reads no image, bin and slot_valid when nothing was rendered (R == 0), slots when the call takes none.
+struct GsrFrame {
+	int P, W, H;
+	int64_t R;
+	GsrGeometry g;
+	GsrImage img;
+	GsrBinning bin;
+	GsrGradSlot* slots;
+	// Validity bytes of the gradient slots: the tile sort's dead ping-pong buffer, cleared at the end of the forward.
+	// Which slots get written depends on the forward alone (not on dL_dpix), so a second backward over the
+	// same forward state (retain_graph) finds exactly the bytes it would set itself.
+	uint8_t* slot_valid;
+	hipStream_t s;
+	int debug;
+	bool cull;   // !GSR_DEBUG_NO_CULL
+};
+
+// The camera-gradient target of the per-Gaussian backward: the kernels also store one row of 32 floats per wave of 64 Gaussians in
+// `rows` (gsr_cam_rows(count) rows; first must be 0), and a fold adds the rows into the outputs -- without a camera model the 35 of
+// include/gsr_cam.h (dL_dmid = dL_dprojmatrix), under one the 16 + 4 + 3 of include/gsr_cam_cm.h (dL_dmid = dL_dintrinsics)
+struct GsrCamTarget {
+	float* rows;
+	float* dL_dviewmatrix;
+	float* dL_dmid;
+	float* dL_dcampos;
+};
+
+// What the per-Gaussian passes (stage 1 and the per-Gaussian backward) run with beyond their arguments, checked and built in one place
+// (api.hip, gsr_gaussian_options).
+struct GsrGaussianOptions {
+	int aux = 0;                             // 0, or the depth-and-alpha mode (GSR_AUX_*): stage 1 also stores the depth value v in the splat record's last
+	                                         // word; the backward sums the slots' tenth word (dL/dv) and chains it into dL/dmean3D
+	int aa = 0;                              // the anti-aliased path (include/gsr_aa.h): the record's opacity is opacity * rho (gsr_aa.h) ...
+	const float* aa_opacities = nullptr;     // ... and the backward's opacity input: dL/dopacity = dL/dopacity_record * rho, and dL/drho into dL/dcov3D and dL/dmean3D
+	const gsr_camera_model* cm = nullptr;    // NULL, or the camera-model kernels (include/gsr_camera_model.h), with focal_x / focal_y = fx, fy
+	GsrCamTarget cam = {};                   // rows == NULL: no camera gradients
+};
+
 // error plumbing (api.hip)
 int gsr_fail(int code, const char* fmt, ...);
 int gsr_check_hip(hipError_t e, const char* what);
@@ -183,11 +222,8 @@ struct GsrPreprocessArgs {
 };
 
 // preprocess.hip
-// aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the kernels then also store the depth value v in the splat record's last word
-// aa: the anti-aliased path (include/gsr_aa.h): the record's opacity is opacity * rho (gsr_aa.h); the colour kernel has no such variant
-// done: NULL, or an event signalled when the kernel has finished (gsr_launch)
-// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h; checked by the caller), with a.focal_x / a.focal_y = fx, fy
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa, const gsr_camera_model* cm = nullptr);
+// done: NULL, or an event signalled when the kernel has finished (gsr_launch); the colour kernel has no anti-aliased variant
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, const GsrGaussianOptions& o);
 void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done);
 bool gsr_preprocess_needs_color(const GsrPreprocessArgs& a);
 void gsr_launch_preprocess_color(const GsrPreprocessArgs& a, hipStream_t s, int wgs_per_cu, int aux);
@@ -237,56 +273,44 @@ void gsr_launch_depth_bucket_sort(GsrGeometry g, int P, uint4* seg, hipStream_t 
 int gsr_tile_key_bytes(int ntiles, size_t num_rendered);
 
 // render_forward.hip
-void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float4* checkpoints,
-                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s,
-                               const GsrAuxBlend* aux);   // ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries; aux: NULL, or the depth-and-alpha variant
+// ordered: tile_order holds ntiles + 3 * gsr_tile_order_max_split(ntiles) entries; aux: NULL, or the depth-and-alpha variant
+void gsr_launch_render_forward(const GsrFrame& f, const float* bg, float* out_color, bool ordered, const GsrAuxBlend* aux);
 
 // render_backward.hip
-void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
-                                const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop,
-                                const GsrAuxBlend* aux, bool absgrad = false);   // t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
-                                                                                 // absgrad: the ABS variant, which also fills the slots' words 10 and 11 (include/gsr_absgrad.h)
+// t_*: NULL, or taken by the kernel's own dispatch packet (gsr_launch); aux: NULL, or the depth-and-alpha variant
+// absgrad: the ABS variant, which also fills the slots' words 10 and 11 (include/gsr_absgrad.h)
+void gsr_launch_render_backward(const GsrFrame& f, const float* bg, const float* dL_dpix, hipEvent_t t_start, hipEvent_t t_stop,
+                                const GsrAuxBlend* aux, bool absgrad);
 
 // absgrad.hip: per-Gaussian fold of the slots' words 10 and 11 (include/gsr_absgrad.h) for the Gaussians [first, first + count).
-// radii: NULL = visibility from tiles_touched; slots / slot_valid: NULL when nothing was rendered (every Gaussian then gets zeros)
-void gsr_launch_absgrad_fold(int first, int count, GsrGeometry g, const int* radii, const GsrGradSlot* slots, const uint8_t* slot_valid,
-                             float* abs_dL_dmean2D, float* stat_abs_gradient_accum, hipStream_t s);
+// radii: NULL = visibility from tiles_touched; the frame's slot_valid: NULL when nothing was rendered (every Gaussian then gets zeros)
+void gsr_launch_absgrad_fold(const GsrFrame& f, int first, int count, const int* radii, float* abs_dL_dmean2D, float* stat_abs_gradient_accum);
 
 // contrib.hip: blend-weight statistics (include/gsr_contrib.h).  scratch: R 16-byte records, then (at gsr_contrib_valid_offset) R validity
 // bytes, which gsr_contributions clears on the stream before the tile pass
 size_t gsr_contrib_valid_offset(int64_t R);
-void gsr_launch_contrib_tiles(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                              const float* pixel_weight, void* scratch, int64_t R, bool cull, hipStream_t s);
-void gsr_launch_contrib_gaussians(int P, GsrGeometry g, const void* scratch, int64_t R, float* weight_sum, float* weight_max, int32_t* pixel_count,
-                                  hipStream_t s);
+void gsr_launch_contrib_tiles(const GsrFrame& f, const float* pixel_weight, void* scratch);
+void gsr_launch_contrib_gaussians(const GsrFrame& f, const void* scratch, float* weight_sum, float* weight_max, int32_t* pixel_count);
 
 // features.hip: K blended feature channels and their gradients (include/gsr_features.h).  scratch: gsr_features_chunks(K) x R 16-byte
 // records, then (at gsr_features_valid_offset) R validity bytes, which gsr_features_backward clears on the stream before the tile pass.
-// slots: NULL (into_slots = 0), or the gradient slots whose words 0..5 the tile pass adds into
+// the frame's slots: NULL (into_slots = 0), or the gradient slots whose words 0..5 the tile pass adds into
 int gsr_features_chunks(int K);
 size_t gsr_features_valid_offset(int64_t R, int K);
-void gsr_launch_features_forward(int W, int H, int K, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float* features,
-                                 float* out, bool cull, hipStream_t s);
-void gsr_launch_features_backward_tiles(int W, int H, int K, int64_t R, GsrImage img, const uint32_t* point_list, const GsrSplat* splat,
-                                        const uint32_t* slot_base, const float* features, const float* dL_dout, void* scratch,
-                                        GsrGradSlot* slots, bool cull, hipStream_t s);
-void gsr_launch_features_fold(int P, int K, int64_t R, GsrGeometry g, const void* scratch, float* dL_dfeatures, hipStream_t s);
+void gsr_launch_features_forward(const GsrFrame& f, int K, const float* features, float* out);
+void gsr_launch_features_backward_tiles(const GsrFrame& f, int K, const float* features, const float* dL_dout, void* scratch);
+void gsr_launch_features_fold(const GsrFrame& f, int K, const void* scratch, float* dL_dfeatures);
 
 // distortion.hip: the depth-distortion map of an aux-mode forward and its gradient (include/gsr_distortion.h).  state: the planes A, mu,
-// S [3][H][W]; slots: the gradient slots whose words 0..5 and 9 the backward adds into
-void gsr_launch_distortion_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out, float* state,
-                                   bool cull, hipStream_t s);
-void gsr_launch_distortion_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                                    const float* state, const float* dL_ddist, GsrGradSlot* slots, bool cull, hipStream_t s);
+// S [3][H][W]; the backward adds into words 0..5 and 9 of the frame's gradient slots
+void gsr_launch_distortion_forward(const GsrFrame& f, float* out, float* state);
+void gsr_launch_distortion_backward(const GsrFrame& f, const float* state, const float* dL_ddist);
 
 // median.hip: the median-depth map, the per-pixel index maps and the median depth's gradient (include/gsr_median.h).  Outputs: NULL =
-// not wanted; state: the median's list position per pixel [H][W]; slots: the gradient slots whose word 9 the backward adds into
-void gsr_launch_median_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out_depth,
-                               int32_t* out_median, int32_t* out_dominant, float* out_weight, uint32_t* state, bool cull, bool full_walk,
-                               hipStream_t s);
-void gsr_launch_median_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                                const uint32_t* state, const float* dL_dmedian, GsrGradSlot* slots, hipStream_t s);
+// not wanted; state: the median's list position per pixel [H][W]; the backward adds into word 9 of the frame's gradient slots
+void gsr_launch_median_forward(const GsrFrame& f, float* out_depth, int32_t* out_median, int32_t* out_dominant, float* out_weight,
+                               uint32_t* state, bool full_walk);
+void gsr_launch_median_backward(const GsrFrame& f, const uint32_t* state, const float* dL_dmedian);
 
 // gaussian_backward.hip
 struct GsrGaussianBackwardArgs {
@@ -333,15 +357,7 @@ struct GsrGaussianBackwardArgs {
 struct GsrGaussianBackwardArgsAA : GsrGaussianBackwardArgs {
 	const float* opacities;
 };
-// aux: 0, or the depth-and-alpha mode (GSR_AUX_*): the slots' tenth word (dL/dv) is summed and chained into dL/dmean3D
-// aa_opacities: NULL, or the anti-aliased kernels with this opacity input: dL/dopacity = dL/dopacity_record * rho, and dL/drho into
-// dL/dcov3D and dL/dmean3D
-// cam_partials: NULL, or the camera-gradient kernels (include/gsr_cam.h), which also store one row of 32 floats per wave of 64
-// Gaussians there (gsr_cam_rows(count) rows; first must be 0); gsr_launch_camera_grad_fold adds the rows into the 35 outputs
-// cm: NULL, or the camera-model kernels (include/gsr_camera_model.h), with a.focal_x / a.focal_y = fx, fy.  With cam_partials too: the
-// camera gradients under a model (include/gsr_cam_cm.h), whose rows gsr_launch_cam_cm_fold adds into the 16 + 4 + 3 outputs
-void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, const float* aa_opacities, hipStream_t s, int aux, float* cam_partials = nullptr,
-                                  const gsr_camera_model* cm = nullptr);
+void gsr_launch_gaussian_backward(const GsrGaussianBackwardArgs& a, hipStream_t s, const GsrGaussianOptions& o);
 size_t gsr_cam_rows(int P);
 void gsr_launch_camera_grad_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, hipStream_t s);
 void gsr_launch_cam_cm_fold(const float* partials, int nrows, float* dL_dviewmatrix, float* dL_dintrinsics, float* dL_dcampos, hipStream_t s);

@@ -174,23 +174,21 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) gsr_median_backward_ker
 	}
 }
 
-void gsr_launch_median_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float* out_depth,
-                               int32_t* out_median, int32_t* out_dominant, float* out_weight, uint32_t* state, bool cull, bool full_walk,
-                               hipStream_t s)
+void gsr_launch_median_forward(const GsrFrame& f, float* out_depth, int32_t* out_median, int32_t* out_dominant, float* out_weight,
+                               uint32_t* state, bool full_walk)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
 	if (full_walk)
-		gsr_launch(gsr_median_forward_kernel<false>, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
-		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
+		gsr_launch(gsr_median_forward_kernel<false>, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, f.img.ranges, f.bin.point_list,
+		           f.g.splat, f.img.n_contrib, f.img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, f.cull ? 1 : 0);
 	else
-		gsr_launch(gsr_median_forward_kernel<true>, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles, img.ranges, point_list, splat,
-		           img.n_contrib, img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, cull ? 1 : 0);
+		gsr_launch(gsr_median_forward_kernel<true>, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles, f.img.ranges, f.bin.point_list,
+		           f.g.splat, f.img.n_contrib, f.img.tile_max_contrib, out_depth, out_median, out_dominant, out_weight, state, f.cull ? 1 : 0);
 }
 
-void gsr_launch_median_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const uint32_t* slot_base,
-                                const uint32_t* state, const float* dL_dmedian, GsrGradSlot* slots, hipStream_t s)
+void gsr_launch_median_backward(const GsrFrame& f, const uint32_t* state, const float* dL_dmedian)
 {
-	const GsrTileGrid t = gsr_tile_grid(W, H);
-	gsr_launch(gsr_median_backward_kernel, t.grid, t.block, 0, s, nullptr, nullptr, W, H, t.gx, t.ntiles,
-	           img.ranges, point_list, splat, slot_base, state, dL_dmedian, slots);
+	const GsrTileGrid t = gsr_tile_grid(f.W, f.H);
+	gsr_launch(gsr_median_backward_kernel, t.grid, t.block, 0, f.s, nullptr, nullptr, f.W, f.H, t.gx, t.ntiles,
+	           f.img.ranges, f.bin.point_list, f.g.splat, f.g.slot_base, state, dL_dmedian, f.slots);
 }

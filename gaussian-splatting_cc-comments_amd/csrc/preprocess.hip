@@ -315,18 +315,18 @@ void gsr_launch_zero_status(uint32_t* status, hipStream_t s, hipEvent_t done)
 
 // one instantiation per (LEAF, depth-and-alpha mode, AA) and, with a camera model, one more each; done: the event the count's
 // read-back waits for (api.hip)
-void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, int aux, int aa, const gsr_camera_model* cm)
+void gsr_launch_preprocess(const GsrPreprocessArgs& a, hipStream_t s, hipEvent_t done, const GsrGaussianOptions& o)
 {
 	const int nb = (a.P + GSR_PREPROCESS_BLOCK - 1) / GSR_PREPROCESS_BLOCK;
 	uint32_t* clear = (uint32_t*)a.g.sort_table;
 	const size_t clear_words = gsr_radix_clear_words((size_t)a.P);
 	uint32_t* clear2 = (uint32_t*)a.g.col_table;
 	const size_t clear2_words = gsr_tilebin_col_clear_words((size_t)a.P);
-	gsr_variant(a.leaf, aux, aa, [&](auto LEAF, auto AUX, auto AA) {
-		if (cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
+	gsr_variant(a.leaf, o.aux, o.aa, [&](auto LEAF, auto AUX, auto AA) {
+		if (o.cm) {   // the camera-model twin (include/gsr_camera_model.h): the same arguments with the model behind them
 			GsrWithCameraModel<GsrPreprocessArgs> c;
 			static_cast<GsrPreprocessArgs&>(c) = a;
-			c.cm_model = cm->model; c.cm_cx = cm->cx; c.cm_cy = cm->cy;
+			c.cm_model = o.cm->model; c.cm_cx = o.cm->cx; c.cm_cy = o.cm->cy;
 			gsr_launch(gsr_preprocess_kernel<LEAF(), AUX(), AA(), true>, dim3(nb), dim3(GSR_PREPROCESS_BLOCK), 0, s, nullptr, done,
 			           c, clear, clear_words, clear2, clear2_words);
 			return;

@@ -445,19 +445,19 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	GSR_TILE_CLOCK_STOP(gsr_backward_tile_clock, slot_id, lane, st_staged | (st_pairs << 20) | (st_pairs_hit << 42), st_reductions | (st_lanes_hit << 24));   // one record per dispatch entry
 }
 
-void gsr_launch_render_backward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, const float4* checkpoints,
-                                const uint32_t* slot_base, const float* bg, const float* dL_dpix, GsrGradSlot* slots,
-                                uint8_t* slot_valid, bool cull, hipStream_t s, hipEvent_t t_start, hipEvent_t t_stop, const GsrAuxBlend* aux, bool absgrad)
+void gsr_launch_render_backward(const GsrFrame& f, const float* bg, const float* dL_dpix, hipEvent_t t_start, hipEvent_t t_stop,
+                                const GsrAuxBlend* aux, bool absgrad)
 {
-	const int gx = gsr_grid_x(W), gy = gsr_grid_y(H);
+	const GsrImage& img = f.img;
+	const int W = f.W, H = f.H, gx = gsr_grid_x(W), gy = gsr_grid_y(H);
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (int)gsr_tile_order_max_segments(ntiles);   // whole tiles + the extra entries of heavy tiles' depth segments
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
 	// (one kernel for both modes of the maps: it reads v from the record; the blend has no anti-aliased form, so the third slot of
 	// gsr_variant carries ABS here)
 	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, absgrad, [&](auto, auto AUX, auto ABS) {
-		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0, ABS()>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, t_start, t_stop, W, H, gx, nslots,
-		           img.ranges, point_list, splat, checkpoints, img.final_C, slot_base, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		           img.tile_order, dL_dpix, slots, slot_valid, cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
+		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0, ABS()>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, f.s, t_start, t_stop, W, H, gx, nslots,
+		           img.ranges, f.bin.point_list, f.g.splat, f.bin.checkpoints, img.final_C, f.g.slot_base, bg, img.final_T, img.n_contrib,
+		           img.tile_max_contrib, img.tile_order, dL_dpix, f.slots, f.slot_valid, f.cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
 	});
 }

@@ -208,16 +208,16 @@ gsr_render_forward_wave_kernel(
 	                    (st_staged & 0xFFFFFull) | ((st_bands & 0x3FFFFFull) << 20) | ((st_hits & 0x3FFFFFull) << 42));
 }
 
-void gsr_launch_render_forward(int W, int H, GsrImage img, const uint32_t* point_list, const GsrSplat* splat, float4* checkpoints,
-                               const float* bg, float* out_color, bool ordered, bool cull, hipStream_t s, const GsrAuxBlend* aux)
+void gsr_launch_render_forward(const GsrFrame& f, const float* bg, float* out_color, bool ordered, const GsrAuxBlend* aux)
 {
-	const int gx = gsr_grid_x(W), gy = gsr_grid_y(H);
+	const GsrImage& img = f.img;
+	const int W = f.W, H = f.H, gx = gsr_grid_x(W), gy = gsr_grid_y(H);
 	const int ntiles = gx * gy;
 	const int nslots = ntiles + (ordered ? 3 * (int)gsr_tile_order_max_split(ntiles) : 0);
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
 	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, false, [&](auto, auto AUX, auto) {   // (one kernel for both modes: it reads v from the record)
-		gsr_launch(gsr_render_forward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, s, nullptr, nullptr, W, H, gx, nslots,
-		           img.ranges, point_list, splat, checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		           ordered ? img.tile_order : nullptr, out_color, cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
+		gsr_launch(gsr_render_forward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, f.s, nullptr, nullptr, W, H, gx, nslots,
+		           img.ranges, f.bin.point_list, f.g.splat, f.bin.checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
+		           ordered ? img.tile_order : nullptr, out_color, f.cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
 	});
 }

@@ -280,3 +280,140 @@ def test_trim_word_decoder_host_and_numpy_restatement_agree():
         want = util.trim_kept(rshape, np.full(tiles.shape, k), tiles, gx)
         got = np.frombuffer(out[k].encode(), np.uint8) == ord("1")
         assert np.array_equal(got, want), (k, int(w[k]), int(h[k]), hex(int(trim[k])))
+
+
+def _frame_entry_points():
+    """The entry points that open the state of a forward, as rows of a table: name, a call taking (P, R, W, H, buffers), the
+    buffers it takes, those it refuses as NULL, those it refuses misaligned, and whether it limits R to 32 bits."""
+    from diff_gaussian_rasterization import _C
+    L = _C.lib()
+    BWD_REQUIRED = ("background", "means3D", "viewmatrix", "projmatrix", "geometry", "image", "dL_dpix", "dL_dmean2D", "dL_dopacity",
+                    "dL_dmean3D", "dL_dscale", "dL_drot", "binning", "scratch")
+    BWD_POINTERS = tuple(n for n, t in _C.BackwardArgs._fields_ if t is ctypes.c_void_p and n != "stream")
+
+    def bwd(P, R, W, H, b):
+        a = _C.BackwardArgs()
+        a.P, a.num_rendered, a.width, a.height, a.M, a.tan_fovx, a.tan_fovy = P, R, W, H, 1, 1.0, 1.0
+        for n in BWD_POINTERS:
+            if n in b:
+                setattr(a, n, b[n])
+        return ctypes.byref(a)
+
+    state = ("geometry", "binning", "image")
+    aux = lambda: ctypes.byref(_C.AuxArgs(1, 4096, 4096, None, None, 4096))
+    rows = []
+    add = lambda name, call, buffers, required, aligned, limit, **kw: rows.append(dict(name=name, call=call, buffers=buffers, required=required,
+                                                                                       aligned=aligned, limit=limit, **kw))
+    render = lambda fn, *lead: lambda P, R, W, H, b: fn(*lead, P, R, W, H, b.get("background"), b.get("radii"), b.get("geometry"),
+                                                        b.get("binning"), b.get("image"), b.get("out_color"), None, 0)
+    add("gsr_forward_render", render(L.gsr_forward_render), state + ("background", "radii", "out_color"), state + ("background", "out_color"), state, True)
+    add("gsr_forward_render_aux", lambda P, R, W, H, b: render(L.gsr_forward_render_aux, aux())(P, R, W, H, b),
+        state + ("background", "radii", "out_color"), state + ("background", "out_color"), state, True)
+    # (the blend with nothing rendered, and the per-Gaussian pass over an empty range, return before any launch)
+    add("gsr_backward_blend", lambda P, R, W, H, b: L.gsr_backward_blend(bwd(P, R, W, H, b)), BWD_POINTERS, BWD_REQUIRED,
+        state + ("scratch",), False, only_if_rendered=("binning", "scratch"))
+    add("gsr_backward_blend_abs", lambda P, R, W, H, b: L.gsr_backward_blend_abs(bwd(P, R, W, H, b), None, 1), BWD_POINTERS, BWD_REQUIRED,
+        state + ("scratch",), False, only_if_rendered=("binning", "scratch"))
+    add("gsr_backward_gaussians", lambda P, R, W, H, b: L.gsr_backward_gaussians(bwd(P, R, W, H, b), 0, max(P, 0) if R else 0, 0), BWD_POINTERS,
+        BWD_REQUIRED, state + ("scratch",), False, only_if_rendered=("binning", "scratch"))
+    # (the fold reads no image; one of its two outputs must be there whatever P is)
+    add("gsr_absgrad_fold", lambda P, R, W, H, b: L.gsr_absgrad_fold(bwd(P, R, W, H, b), ctypes.byref(_C.AbsgradArgs(b.get("abs_dL_dmean2D", 4096), None)),
+                                                                    0, max(P, 0)),
+        ("geometry", "binning", "scratch"), ("geometry", "binning", "scratch"), ("geometry", "binning", "scratch"), False)
+    add("gsr_contributions", lambda P, R, W, H, b: L.gsr_contributions(P, R, W, H, b.get("geometry"), b.get("binning"), b.get("image"),
+                                                                       b.get("pixel_weight"), b.get("weight_sum"), b.get("weight_max"),
+                                                                       b.get("pixel_count"), b.get("own_scratch"), None, 0),
+        state + ("pixel_weight", "weight_sum", "weight_max", "pixel_count", "own_scratch"), state + ("own_scratch",), state + ("own_scratch",), True,
+        only_if_rendered=("binning", "own_scratch"))
+    add("gsr_features_forward", lambda P, R, W, H, b: L.gsr_features_forward(P, R, W, H, 4, b.get("geometry"), b.get("binning"), b.get("image"),
+                                                                             b.get("features"), b.get("out"), None, 0),
+        state + ("features", "out"), state + ("features", "out"), state, True)
+    add("gsr_features_backward", lambda P, R, W, H, b: L.gsr_features_backward(bwd(P, R, W, H, b), 4, b.get("features"), b.get("dL_dout"),
+                                                                               b.get("dL_dfeatures"), b.get("own_scratch"), 1),
+        state + ("scratch", "features", "dL_dout", "dL_dfeatures", "own_scratch"), state + ("scratch", "features", "dL_dout", "dL_dfeatures", "own_scratch"),
+        state + ("scratch", "own_scratch"), True)
+    add("gsr_distortion_forward", lambda P, R, W, H, b: L.gsr_distortion_forward(P, R, W, H, b.get("geometry"), b.get("binning"), b.get("image"),
+                                                                                 b.get("out"), b.get("state"), None, 0),
+        state + ("out", "state"), state + ("out", "state"), state + ("state",), True)
+    add("gsr_distortion_backward", lambda P, R, W, H, b: L.gsr_distortion_backward(bwd(P, R, W, H, b), b.get("state"), b.get("dL_dmap")),
+        state + ("scratch", "state", "dL_dmap"), state + ("scratch", "state", "dL_dmap"), state + ("scratch", "state"), True,
+        only_if_rendered=("binning", "scratch"))
+    add("gsr_median_forward", lambda P, R, W, H, b: L.gsr_median_forward(P, R, W, H, b.get("geometry"), b.get("binning"), b.get("image"),
+                                                                         b.get("out"), b.get("out_index"), b.get("out_dominant"),
+                                                                         b.get("out_weight"), b.get("state"), None, 0),
+        state + ("out", "out_index", "out_dominant", "out_weight", "state"), state + ("state",), state + ("state",), True)
+    add("gsr_median_backward", lambda P, R, W, H, b: L.gsr_median_backward(bwd(P, R, W, H, b), b.get("state"), b.get("dL_dmap")),
+        state + ("scratch", "state", "dL_dmap"), state + ("scratch", "state", "dL_dmap"), state + ("scratch", "state"), True,
+        only_if_rendered=("binning", "scratch"))
+    return L, rows
+
+
+def frame_refusal_table():
+    """Every row of test_frame_entry_points_refuse_alike: (entry point, description of the fault, return code, message)."""
+    L, rows = _frame_entry_points()
+    one, odd = 4096, 4104   # never dereferenced: 16-byte aligned, and 8-byte aligned only
+    out = []
+    for e in rows:
+        def run(what, P=4, R=8, W=32, H=16, **change):
+            b = {n: one for n in e["buffers"]}
+            b.update(change)
+            rc = e["call"](P, R, W, H, b)
+            out.append((e["name"], what, dict(P=P, R=R, W=W, H=H, **change), rc, L.gsr_last_error()))
+        for kw in (dict(P=-1), dict(R=-1), dict(W=0), dict(H=-3)):
+            run("sizes", **kw)
+        for n in e["required"]:
+            run("null", **{n: None})
+        for n in e["aligned"]:
+            run("align", **{n: odd})
+        if e["limit"]:
+            run("limit", R=1 << 32)
+        first = e["aligned"][0]
+        run("sizes before null", W=0, **{first: None})
+        run("null before align", **{first: None, e["aligned"][1]: odd})
+        if e["limit"]:
+            run("align before limit", R=1 << 32, **{first: odd})
+        if e.get("only_if_rendered"):
+            run("nothing rendered", R=0, **{n: None for n in e["only_if_rendered"]})
+        run("empty scene", P=0, **{n: None for n in e["buffers"]})
+    return out
+
+
+# the variants of one call report under that call's name
+_FRAME_SAID_BY = {"gsr_forward_render_aux": "gsr_forward_render", "gsr_backward_blend_abs": "gsr_backward_blend"}
+
+
+def test_frame_entry_points_refuse_alike():
+    """Every entry point that opens the state of a forward (geometry, image, binning, gradient slots), with P=4, R=8, a 32 x 16 image
+    and fake addresses that are never dereferenced, and exactly one fault at a time: bad sizes, each required buffer NULL, each buffer
+    whose alignment matters 8-byte aligned only, and R = 2^32 where the entry point limits R (the backward calls do not).  Each is
+    GSR_ERR_INVALID_ARGUMENT with a message under the entry point's name.  Of two faults the earlier class is reported: sizes, NULL,
+    alignment, the limit on R.  binning and the slots are needed only when something was rendered, and an empty scene is GSR_OK with
+    every pointer NULL and an empty gsr_last_error().  A valid call would launch, so none is made: nothing here touches a device."""
+    table = frame_refusal_table()
+    assert len({r[0] for r in table}) >= 12
+    single = {}
+    for name, what, args, rc, msg in table:
+        key = (name, what, tuple(sorted((k, v) for k, v in args.items() if (k, v) not in (("P", 4), ("R", 8), ("W", 32), ("H", 16)))))
+        single[key] = msg
+        if what in ("sizes", "null", "align", "limit"):
+            assert rc == -1 and msg, (name, args, rc, msg)
+            said_by = _FRAME_SAID_BY.get(name, name)
+            assert msg.decode().startswith(said_by + ":"), (name, args, msg)
+            if what == "sizes":
+                assert b"bad" in msg, (name, args, msg)
+        elif what in ("nothing rendered", "empty scene"):
+            assert rc == 0 and msg == b"", (name, what, args, rc, msg)
+    # of two faults the earlier class is reported: the pair's message is the earlier fault's own
+    for name, what, args, rc, msg in table:
+        if " before " not in what:
+            continue
+        assert rc == -1, (name, what, args, rc)
+        extra = {k: v for k, v in args.items() if (k, v) not in (("P", 4), ("R", 8), ("W", 32), ("H", 16))}
+        if what == "sizes before null":
+            earlier = {"W": 0}
+        elif what == "null before align":
+            earlier = {k: v for k, v in extra.items() if v is None}
+        else:
+            earlier = {k: v for k, v in extra.items() if k != "R"}
+        cls = what.split(" ")[0]
+        assert msg == single[(name, cls, tuple(sorted(earlier.items())))], (name, what, args, msg)
