@@ -12,7 +12,7 @@ There is no CPU fallback: a missing library or a non-HIP tensor raises.
 import ctypes
 import math
 import os
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -440,31 +440,89 @@ def absgrad_tensors(absgrad, P, device=None):
     return c
 
 
-def camera_backward_args(P, device):
-    """CamArgs of a backward with camera gradients (include/gsr_cam.h) -> (struct, (dL_dviewmatrix (4,4), dL_dprojmatrix (4,4),
-    dL_dcampos (3,))): the three outputs, which the fold kernel writes in full, and the scratch of P Gaussians, all from torch's
-    allocator; the struct keeps them alive until the calls that use it have been enqueued."""
+# which camera inputs take part in autograd (RenderOptions.camera) -> the inputs whose gradients the backward's camera target holds,
+# in the order of its struct: gsr_cam_args (include/gsr_cam.h) / gsr_cam_cm_args (include/gsr_cam_cm.h)
+CAMERA_TARGETS = {"cam": ("viewmatrix", "projmatrix", "campos"), "cm": ("viewmatrix", "intrinsics", "campos")}
+_CAMERA_SHAPES = {"viewmatrix": (4, 4), "projmatrix": (4, 4), "campos": (3,), "intrinsics": (4,)}
+
+
+def camera_target(kind, P, device):
+    """The camera target of a backward, kind "cam" or "cm" -> (CamArgs / CamCmArgs, the three gradients of CAMERA_TARGETS[kind]):
+    the outputs, which the fold kernel writes in full, and the scratch of P Gaussians, all from torch's allocator; the struct keeps
+    them alive until the calls that use it have been enqueued.  P == 0, where nothing is launched: (None, zeros)."""
     f32 = dict(dtype=torch.float32, device=device)
-    outs = (torch.empty((4, 4), **f32), torch.empty((4, 4), **f32), torch.empty((3,), **f32))
-    scratch = torch.empty((lib().gsr_cam_bytes(int(P)),), dtype=torch.uint8, device=device)
-    c = CamArgs()
-    c.dL_dviewmatrix, c.dL_dprojmatrix, c.dL_dcampos = (t.data_ptr() for t in outs)
-    c.scratch = scratch.data_ptr()
+    shapes = [_CAMERA_SHAPES[n] for n in CAMERA_TARGETS[kind]]
+    if P == 0:
+        return None, tuple(torch.zeros(s, **f32) for s in shapes)
+    outs = tuple(torch.empty(s, **f32) for s in shapes)
+    nbytes = lib().gsr_cam_bytes(int(P)) if kind == "cam" else lib().gsr_cam_cm_bytes(int(P))
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    c = CamArgs() if kind == "cam" else CamCmArgs()
+    for (field, _), t in zip(c._fields_, outs + (scratch,)):
+        setattr(c, field, t.data_ptr())
     c._keep = outs + (scratch,)
     return c, outs
 
 
-def camera_cm_backward_args(P, device):
-    """CamCmArgs of a backward with camera gradients under a camera model (include/gsr_cam_cm.h) -> (struct, (dL_dviewmatrix (4,4),
-    dL_dintrinsics (4,), dL_dcampos (3,))), as camera_backward_args()."""
-    f32 = dict(dtype=torch.float32, device=device)
-    outs = (torch.empty((4, 4), **f32), torch.empty((4,), **f32), torch.empty((3,), **f32))
-    scratch = torch.empty((lib().gsr_cam_cm_bytes(int(P)),), dtype=torch.uint8, device=device)
-    c = CamCmArgs()
-    c.dL_dviewmatrix, c.dL_dintrinsics, c.dL_dcampos = (t.data_ptr() for t in outs)
-    c.scratch = scratch.data_ptr()
-    c._keep = outs + (scratch,)
-    return c, outs
+class RenderOptions(NamedTuple):
+    """Everything of one render that is no differentiable input, checked: the one record the public entry points hand to the autograd
+    Functions (render_options() builds it).  camera: which camera inputs take part in autograd -- None, "cam" (the settings'
+    viewmatrix, projmatrix and campos, include/gsr_cam.h) or "cm" (viewmatrix, campos and the intrinsics tensor under camera_model,
+    include/gsr_cam_cm.h); the tied inputs are CAMERA_TARGETS[camera]."""
+    depth_alpha: Optional[str] = None
+    antialiasing: bool = False
+    densify_stats: Optional[tuple] = None
+    contrib_stats: Optional[tuple] = None
+    contrib_pixel_weight: Optional[torch.Tensor] = None
+    absgrad: Optional[tuple] = None
+    distortion: bool = False
+    median_depth: bool = False
+    index_maps: Optional[tuple] = None
+    camera_model: Optional[CameraModel] = None
+    camera: Optional[str] = None
+
+
+def render_options(raster_settings, depth_alpha=None, densify_stats=None, antialiasing=False, contrib_stats=None,
+                   contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None,
+                   model=None, camera_model_grads=False, mode_required=False):
+    """The public keywords -> (RenderOptions, the intrinsics tensor of camera_model_grads or None).  Runs every check that needs
+    neither P nor a device, in one order for every entry point: depth_alpha (ValueError), distortion and median_depth (TypeError for
+    anything but a bool, ValueError without a mode), index_maps (TypeError / ValueError), antialiasing and camera_grads (TypeError),
+    model, the `camera_model` keyword (TypeError / ValueError; NotImplementedError with camera_grads), camera_model_grads (TypeError /
+    ValueError).
+    mode_required: depth_alpha=None is refused too (rasterize_gaussians_depth_alpha)."""
+    if depth_alpha is not None or mode_required:
+        aux_mode(depth_alpha)
+    distortion_flag(distortion, depth_alpha)
+    median_flag(median_depth, depth_alpha)
+    if index_maps is not None:
+        index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
+    aa_flag(antialiasing)
+    camera_flag(camera_grads)
+    cm = camera_model(model)
+    camera_model_excludes(cm, camera_grads)
+    cmg = camera_model_grads_arg(camera_model_grads, cm)
+    camera = "cm" if cmg is not False else "cam" if camera_grads else None
+    return (RenderOptions(depth_alpha, antialiasing, densify_stats, contrib_stats, contrib_pixel_weight, absgrad, distortion,
+                          median_depth, index_maps, cm, camera), cmg if isinstance(cmg, torch.Tensor) else None)
+
+
+def check_render_tensors(options, features, intrinsics, P, device, raster_settings):
+    """The checks of a render's options that need P and the render's device (None: the render is not on a HIP device and will be
+    refused by the forward itself), at the top of every autograd forward: refused before anything runs.  A record that did not come
+    from render_options() is held to its rule for the maps too.  With settings.debug the intrinsics tensor and the model must agree."""
+    distortion_flag(options.distortion, options.depth_alpha)
+    median_flag(options.median_depth, options.depth_alpha)
+    if options.index_maps is not None:
+        index_map_tensors(options.index_maps, raster_settings.image_width, raster_settings.image_height, device)
+    if features is not None:
+        feature_tensor(features, P, device)
+    if options.contrib_stats is not None:
+        contrib_stat_tensors(options.contrib_stats, P)
+    if options.absgrad is not None:   # only the backward writes the tensors
+        absgrad_tensors(options.absgrad, P, device)
+    if intrinsics is not None and raster_settings.debug:
+        camera_model_matches(options.camera_model, intrinsics)
 
 
 # ---- which C entry point serves a variant: the only place that chooses between gsr_*, gsr_*_aux and gsr_*_aa -------------------
@@ -626,9 +684,9 @@ def run_backward(a, scratch, device, x=None, opacities=None, parts=None, before_
     blend pass, then the per-Gaussian pass for every (first, count) of `parts` (default: all Gaussians at once), writing rows from
     `first` on.  x: AuxArgs of a backward with map gradients, or None; opacities: the forward's opacity input (tensor or address; the
     logits in leaf mode) when the screen-space filter was on, else None; before_part(k) / after_part(k): called around part k's pass
-    (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_backward_args()) when
+    (view_parallel.py sets the part's output pointers and starts its collectives there).  cam: CamArgs (camera_target("cam", ...)) when
     the per-Gaussian pass shall also produce the camera gradients; it runs over all Gaussians at once, so not with `parts`.  With
-    camera_model it is the CamCmArgs (camera_cm_backward_args()) of the camera gradients under that model.
+    camera_model it is the CamCmArgs (camera_target("cm", ...)) of the camera gradients under that model.
     absgrad: AbsgradArgs (absgrad_tensors()) when the blend shall keep the per-pixel moduli of dL/dmean2D and a fold pass behind it
     shall overwrite abs_mean2D and add into abs_gradient_accum (include/gsr_absgrad.h); not with `parts` either.
     features: FeatureBackward (include/gsr_features.h) when a feature map took part in the loss: its pass runs between the blend (and
@@ -687,7 +745,7 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
     camera_model_excludes(cm, camera_flag(camera_grads))
     if not isinstance(camera_model_grads, bool):
         raise TypeError(f"{who}: camera_model_grads must be True or False here, got {camera_model_grads!r}")
-    cm_grads = camera_model_grads_arg(camera_model_grads, cm)
+    kind = "cam" if camera_grads else "cm" if camera_model_grads_arg(camera_model_grads, cm) else None
     cam, cam_grads = None, ()
     L = lib()
     dev = means3D.device
@@ -717,10 +775,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                     (cov3D_precomp, "cov3D_precomp"), (viewmatrix, "viewmatrix"), (projmatrix, "projmatrix"),
                     (dL_dout_color, "dL_dout_color"), (sh, "shs"), (campos, "campos")))
             scratch = backward_scratch(P, R, dev)
-            if camera_flag(camera_grads):
-                cam, cam_grads = camera_backward_args(P, dev)
-            elif cm_grads:
-                cam, cam_grads = camera_cm_backward_args(P, dev)
+            if kind is not None:
+                cam, cam_grads = camera_target(kind, P, dev)
             ab = None if absgrad is None else absgrad_tensors(absgrad, P, dev)
             if stats is None and not aa and aux is None and cam is None and ab is None and features is None and cm is None:   # nothing but the reference's backward: one call for both stages
                 _check(L.gsr_backward(P, int(degree), M, int(R), W, H, _ptr(background), _ptr(means3D), _ptr(sh), _ptr(colors),
@@ -744,10 +800,8 @@ def _backward_plain(who, aux, args, lean, skip_sh, debug_out, stats, antialiasin
                 set_backward_stats(a, stats, P, dev)
                 run_backward(a, scratch, dev, None if aux is None else aux_backward_args(*aux, dev), opacities if aa else None, cam=cam,
                              absgrad=ab, features=features, distortion=distortion, median=median, camera_model=cm)
-        elif camera_flag(camera_grads):   # no Gaussian: nothing is launched
-            cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4, 4), **f32), torch.zeros((3,), **f32))
-        elif cm_grads:
-            cam_grads = (torch.zeros((4, 4), **f32), torch.zeros((4,), **f32), torch.zeros((3,), **f32))
+        elif kind is not None:   # no Gaussian: nothing is launched
+            cam, cam_grads = camera_target(kind, 0, dev)
     if debug_out is not None:
         debug_out["dL_dconic"] = dL_dconic
     return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations) + tuple(cam_grads)

@@ -27,57 +27,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """reference __init__.py:22-45 (+ the optional densification-statistics tensors, the screen-space filter, the blend-weight
     statistics, the camera gradients, the absolute gradients, the feature channels, the per-pixel index maps, the camera model and
     the camera gradients under it, see GaussianRasterizer)"""
-    if index_maps is not None:
-        _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
-    return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), None,
-                  contrib_stats, contrib_pixel_weight, absgrad,
-                  *camera_inputs(raster_settings, camera_grads, camera_model, camera_model_grads), index_maps=index_maps)
-
-
-def _apply(features, *inputs, distortion=False, median_depth=False, index_maps=None):
-    """features=None: the Function of every release so far, on its own inputs; a tensor: the Function that takes it in front of them
-    and returns the feature map behind the other outputs.  distortion=True: the Function that returns the distortion map behind
-    depth and alpha, with `features` (a tensor or None) in front of the inputs.  median_depth=True or index_maps: the Function that
-    takes all four in front of the inputs."""
-    if median_depth or index_maps is not None:
-        return _RasterizeGaussiansMedian.apply(features, distortion, median_depth, index_maps, *inputs)
-    if distortion:
-        return _RasterizeGaussiansDistortion.apply(features, *inputs)
-    if features is None:
-        return _RasterizeGaussians.apply(*inputs)
-    return _RasterizeGaussiansFeatures.apply(features, *inputs)
-
-
-def camera_inputs(raster_settings, camera_grads, camera_model=None, camera_model_grads=False):
-    """What the autograd Functions take behind their own inputs.  camera_grads=True: the three camera tensors of the settings; a
-    camera model: the checked CameraModel alone (one input that is no tensor); neither: nothing, so a call without either is the call
-    it always was.  Anything but a bool raises TypeError; a bad camera model TypeError or ValueError (_C.camera_model); both together
-    NotImplementedError.  A camera model with camera_model_grads (True or the intrinsics tensor, _C.camera_model_grads_arg): four
-    inputs, the model, the settings' viewmatrix and campos, and the intrinsics tensor or None."""
-    cm = _C.camera_model(camera_model)
-    _C.camera_model_excludes(cm, _C.camera_flag(camera_grads))
-    cmg = _C.camera_model_grads_arg(camera_model_grads, cm)
-    if cmg is not False:
-        return (cm, raster_settings.viewmatrix, raster_settings.campos, None if cmg is True else cmg)
-    if cm is not None:
-        return (cm,)
-    if not camera_grads:
-        return ()
-    return (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
-
-
-def camera_grad_results(needs, grads, inputs):
-    """The three camera gradients of a backward, each shaped like its input, None where the input does not require one."""
-    return tuple(g.reshape(t.shape) if n else None for n, g, t in zip(needs, grads, inputs))
-
-
-def camera_model_grad_results(needs, grads, raster_settings):
-    """The gradients of the inputs (viewmatrix, campos, intrinsics) behind a CameraModel from a backward's (dL_dviewmatrix,
-    dL_dintrinsics, dL_dcampos), None where the input does not require one."""
-    dV, dK, dC = grads
-    return (dV.reshape(raster_settings.viewmatrix.shape) if needs[0] else None,
-            dC.reshape(raster_settings.campos.shape) if needs[1] else None, dK if needs[2] else None)
+    options, intrinsics = _C.render_options(raster_settings, None, densify_stats, antialiasing, contrib_stats, contrib_pixel_weight,
+                                            camera_grads, absgrad, False, False, index_maps, camera_model, camera_model_grads)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, options, features, *camera_positions(options, raster_settings, intrinsics))
 
 
 def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -86,66 +39,155 @@ def rasterize_gaussians_depth_alpha(means3D, means2D, sh, colors_precomp, opacit
                                     median_depth=False, index_maps=None, camera_model=None, camera_model_grads=False):
     """rasterize_gaussians() with the depth and alpha maps -> (color, radii, depth (1,H,W), alpha (1,H,W)[, distortion (1,H,W)]
     [, median_depth (1,H,W)][, feature_map])"""
-    _C.aux_mode(depth_alpha)
-    distortion = _C.distortion_flag(distortion, depth_alpha)
-    median_depth = _C.median_flag(median_depth, depth_alpha)
-    if index_maps is not None:
-        _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
-    return _apply(features, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                  cov3Ds_precomp, raster_settings, densify_stats, _C.aa_flag(antialiasing), depth_alpha,
-                  contrib_stats, contrib_pixel_weight, absgrad,
-                  *camera_inputs(raster_settings, camera_grads, camera_model, camera_model_grads),
-                  distortion=distortion, median_depth=median_depth, index_maps=index_maps)
+    options, intrinsics = _C.render_options(raster_settings, depth_alpha, densify_stats, antialiasing, contrib_stats,
+                                            contrib_pixel_weight, camera_grads, absgrad, distortion, median_depth, index_maps,
+                                            camera_model, camera_model_grads, mode_required=True)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, options, features, *camera_positions(options, raster_settings, intrinsics))
+
+
+# ---- what the two autograd Functions share (fused_params._RasterizeLeafGaussians is the other one) --------------------------------
+# the inputs of both Functions behind `raster_settings`, every one of them None by default
+OPTION_INPUTS = ("options", "features", "viewmatrix", "projmatrix", "campos", "intrinsics")
+
+
+def camera_positions(options, raster_settings, intrinsics):
+    """-> (viewmatrix, projmatrix, campos, intrinsics) for apply(): the settings' tensor (the intrinsics: the tensor given as
+    camera_model_grads) where options.camera ties that input into the graph, None everywhere else -- a camera tensor whose gradient
+    was not asked for is no input, so it cannot make an output require a gradient.  The kernels read the settings and the model's
+    floats; the positions only tie the tensors in."""
+    if options.camera is None:
+        return (None, None, None, None)
+    tied = _C.CAMERA_TARGETS[options.camera]
+    return tuple((intrinsics if n == "intrinsics" else getattr(raster_settings, n)) if n in tied else None for n in OPTION_INPUTS[2:])
+
+
+def after_render(ctx, options, features, raster_settings, P, num_rendered, color, radii, maps, state, opacities):
+    """What follows the render in every forward: the contrib statistics, the feature map, the distortion map, the median depth and
+    index maps, each from the state the render just left; then everything the backward needs goes on ctx, the names of the outputs
+    and of the saved tensors included.  maps: () or (depth, alpha, aux state); state: {name: tensor} of what the Function saves for
+    its own backward, with "means3D", "geomBuffer", "binningBuffer" and "imgBuffer" among them (extended here).  -> the output tuple
+    (color, radii[, depth, alpha][, distortion][, median_depth][, feature_map])."""
+    geom, binning, img = state["geomBuffer"], state["binningBuffer"], state["imgBuffer"]
+    W, H, debug = raster_settings.image_width, raster_settings.image_height, raster_settings.debug
+    outputs, saved = {"color": color, "radii": radii}, state
+    if maps:
+        outputs["depth"], outputs["alpha"] = maps[:2]
+    if options.contrib_stats is not None:   # once per forward, gradients enabled or not, never in backward (include/gsr_contrib.h)
+        _C.gaussian_contributions(geom, binning, img, num_rendered, P, W, H, options.contrib_stats, options.contrib_pixel_weight, debug)
+    if features is not None:   # with the weights the colours were blended with (include/gsr_features.h)
+        feature_map = _C.features_forward(geom, binning, img, num_rendered, P, W, H, features, debug)
+        saved["features"] = features
+    if maps:
+        saved["aux_state"] = maps[2]
+    if options.distortion:   # from the same weights and the records' depth values (include/gsr_distortion.h)
+        outputs["distortion"], saved["distortion_state"] = _C.distortion_forward(geom, binning, img, num_rendered, P, W, H, debug)
+    if options.median_depth or options.index_maps is not None:   # one launch for both (include/gsr_median.h)
+        median, median_state = _C.median_forward(geom, binning, img, num_rendered, P, W, H, options.index_maps, options.median_depth,
+                                                 debug)
+        if options.median_depth:
+            outputs["median_depth"], saved["median_state"] = median, median_state
+    if features is not None:   # last in the tuple
+        outputs["feature_map"] = feature_map
+    if options.antialiasing:   # the filter's backward reads the opacity input: the records hold opacity * rho
+        saved["opacities"] = opacities
+    ctx.raster_settings, ctx.options, ctx.P, ctx.num_rendered = raster_settings, options, P, num_rendered
+    ctx.output_names, ctx.saved_names = tuple(outputs), tuple(saved)
+    ctx.save_for_backward(*saved.values())   # each on its path only
+    ctx.mark_non_differentiable(radii)
+    # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
+    ctx.set_materialize_grads(False)
+    return tuple(outputs.values())
+
+
+class BackwardPlan(NamedTuple):
+    """What before_backward() decided from the output gradients that arrived."""
+    needs: dict          # input name -> it requires a gradient
+    saved: dict          # saved name -> tensor
+    answer: dict         # the frozen-scene short-cut has run: {"features": dL/dfeatures} is the whole backward; else None
+    grad_color: torch.Tensor
+    map_grads: tuple     # (dL/ddepth, dL/dalpha) as (H, W) or None
+    features: object     # _C.FeatureBackward, DistortionBackward, MedianBackward of the maps that took part in the loss, else None
+    distortion: object
+    median: object
+    aux: bool            # the depth-and-alpha backward kernels are needed
+    camera: str          # the camera target that is needed ("cam" / "cm"), None when no tied input requires a gradient
+
+
+def before_backward(ctx, input_names, grad_outputs):
+    """What precedes the kernels in every backward.  A map whose gradient did not arrive runs nothing; with neither dL/ddepth,
+    dL/dalpha nor a map that chains through the depth values, the default backward kernels run."""
+    st = ctx.raster_settings
+    needs = dict(zip(input_names, ctx.needs_input_grad))
+    grads = dict(zip(ctx.output_names, grad_outputs))
+    saved = dict(zip(ctx.saved_names, ctx.saved_tensors))
+    grad_map = grads.get("feature_map")
+    if grad_map is not None and needs["features"] and not any(v for n, v in needs.items() if n != "features"):
+        # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
+        answer = {"features": _C.features_backward_only(saved["geomBuffer"], saved["binningBuffer"], saved["imgBuffer"],
+                                                        ctx.num_rendered, ctx.P, st.image_width, st.image_height, saved["features"],
+                                                        grad_map, st.debug)}
+        return BackwardPlan(needs, saved, answer, None, (None, None), None, None, None, False, None)
+    features = None if grad_map is None else _C.FeatureBackward(saved["features"], grad_map)
+    grad_color = grads["color"]
+    if grad_color is None:  # the image took no part in the loss: the zero gradient autograd would have materialised
+        grad_color = torch.zeros((3, int(st.image_height), int(st.image_width)), dtype=torch.float32, device=saved["means3D"].device)
+    distortion = median = None
+    if grads.get("distortion") is not None:
+        distortion = _C.DistortionBackward(saved["distortion_state"], grads["distortion"])
+    if grads.get("median_depth") is not None:
+        median = _C.MedianBackward(saved["median_state"], grads["median_depth"])
+    grad_depth, grad_alpha = grads.get("depth"), grads.get("alpha")
+    if grad_depth is not None:
+        grad_depth = grad_depth.reshape(grad_depth.shape[-2:])
+    if grad_alpha is not None:
+        grad_alpha = grad_alpha.reshape(grad_alpha.shape[-2:])
+    # (the distortion map's or the median depth's gradient alone still takes the aux kernels: they write the slots' dL/dv word and
+    # chain it)
+    aux = grad_depth is not None or grad_alpha is not None or distortion is not None or median is not None
+    camera = ctx.options.camera
+    if camera is not None and not any(needs[n] for n in _C.CAMERA_TARGETS[camera]):
+        camera = None
+    return BackwardPlan(needs, saved, None, grad_color, (grad_depth, grad_alpha), features, distortion, median, aux, camera)
+
+
+def after_backward(plan, camera_grads, raster_settings):
+    """-> {input name: gradient} of `features` and of the tied camera inputs that require one, each shaped like its input;
+    camera_grads: the three results of the camera target in the order of _C.CAMERA_TARGETS[plan.camera]."""
+    out = {}
+    if plan.features is not None:   # (no Gaussian: nothing ran)
+        out["features"] = plan.features.grad if plan.features.grad is not None else torch.zeros_like(plan.features.features)
+    if plan.camera is not None:
+        for n, g in zip(_C.CAMERA_TARGETS[plan.camera], camera_grads):
+            if plan.needs[n]:
+                out[n] = g if n == "intrinsics" else g.reshape(getattr(raster_settings, n).shape)
+    return out
 
 
 class _RasterizeGaussians(torch.autograd.Function):
-    """The reference's Function, plus (depth_alpha = "depth" / "invdepth") two differentiable per-pixel outputs from the same blend pass
-    (include/gsr_aux.h): depth D = sum_i v_i alpha_i T_i (v_i = view-space z_i for "depth", 1 / z_i for "invdepth"; no background term)
-    and alpha A = 1 - T_final.  Colour and radii are bit-identical with and without the maps.  When neither map's gradient reaches the
-    backward, the default backward kernels run (the anti-aliased ones with antialiasing=True).
+    """The reference's Function: its nine inputs, then OPTION_INPUTS -- the checked _C.RenderOptions (None: the defaults), the
+    feature channels (P, K) or None, and the four camera tensors, each None unless options.camera ties it into the graph
+    (camera_positions()).  What each option does is written at GaussianRasterizer.
 
-    Camera gradients (include/gsr_cam.h): with the settings' viewmatrix, projmatrix and campos as three more inputs behind the others,
-    the backward returns their gradients too -- the camera-gradient kernels run when at least one of the three requires a gradient,
-    the default ones otherwise.  The kernels read the tensors of the settings; the inputs only tie them into the graph.
+    -> (color, radii[, depth, alpha][, distortion][, median_depth][, feature_map]).  Colour, radii and every map have the same bits
+    whatever else is returned.  In the backward a map whose gradient did not arrive runs nothing of its own, and when neither
+    dL/ddepth, dL/dalpha, dL/ddistortion nor dL/dmedian_depth arrived the default backward kernels run (before_backward()); the camera
+    variant of the per-Gaussian kernels runs when at least one tied camera input requires a gradient.
 
-    Absolute gradients (include/gsr_absgrad.h): absgrad = (abs_mean2D, abs_gradient_accum) is checked before anything runs and only
-    the backward writes the tensors; a non-tensor input, so the saved tensors stay as they are and the gradient tuple grows by a None.
+    A new option is one field of the record, one output name and one saved name in after_render() if it has any, and one input
+    position here and in _RasterizeLeafGaussians if it is differentiable; inputs, outputs and saved tensors are only ever reached
+    by name."""
 
-    Feature channels (include/gsr_features.h): _RasterizeGaussiansFeatures below takes `features` (P, K) in front of these inputs
-    and runs this forward and backward with it; through apply() of this class nothing of them is reached.
-
-    Distortion map (include/gsr_distortion.h): _RasterizeGaussiansDistortion below runs this forward with _distortion=True, which
-    returns the map behind depth and alpha and saves its per-pixel state behind the aux buffer; the same holds for it.
-
-    Median depth and index maps (include/gsr_median.h): _RasterizeGaussiansMedian below runs this forward with _median and / or
-    _index_maps: one launch after the render writes the caller's index tensors in place and, with _median=True, returns the
-    median-depth map behind the distortion map's place and saves its state behind the distortion state; the same holds for it.
-
-    Camera model (include/gsr_camera_model.h): a checked CameraModel as the ONE input behind the others (camera_inputs(); never
-    together with the three camera tensors) selects the camera-model kernels of the two per-Gaussian stages; the gradient tuple
-    grows by a None.
-
-    Camera gradients under a model (include/gsr_cam_cm.h): FOUR inputs behind the others -- the CameraModel, the settings'
-    viewmatrix and campos, and the intrinsics tensor (fx, fy, cx, cy) or None -- make the backward return dL/dviewmatrix, dL/dcampos
-    and dL/dintrinsics behind the model's None; the camera variant of the camera-model kernels runs when at least one of the three
-    requires a gradient, the plain camera-model kernels otherwise.  The kernels read the settings' tensors and the model's floats."""
+    INPUTS = ("means3D", "means2D", "sh", "colors_precomp", "opacities", "scales", "rotations", "cov3Ds_precomp",
+              "raster_settings") + OPTION_INPUTS
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, densify_stats=None, antialiasing=False, depth_alpha=None, contrib_stats=None,
-                contrib_pixel_weight=None, absgrad=None, *camera, _features=None, _distortion=False, _median=False,
-                _index_maps=None, _lead=None):
-        _C.distortion_flag(_distortion, depth_alpha)   # refused before anything runs
-        _C.median_flag(_median, depth_alpha)           # the same
-        if _index_maps is not None:   # the same
-            _C.index_map_tensors(_index_maps, raster_settings.image_width, raster_settings.image_height,
-                                 means3D.device if means3D.is_cuda else None)
-        if _features is not None:       # the same
-            _C.feature_tensor(_features, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
-        if contrib_stats is not None:   # the same
-            _C.contrib_stat_tensors(contrib_stats, int(means3D.size(0)))
-        if absgrad is not None:         # the same, the render's device included (a CPU means3D is refused by the forward itself)
-            _C.absgrad_tensors(absgrad, int(means3D.size(0)), means3D.device if means3D.is_cuda else None)
+                raster_settings, options=None, features=None, viewmatrix=None, projmatrix=None, campos=None, intrinsics=None):
+        options = _C.RenderOptions() if options is None else options
+        P = int(means3D.size(0))
+        # refused before anything runs (a CPU means3D is refused by the forward itself)
+        _C.check_render_tensors(options, features, intrinsics, P, means3D.device if means3D.is_cuda else None, raster_settings)
         # argument order of _C.rasterize_gaussians: reference __init__.py:64-84
         args = (
             raster_settings.bg,
@@ -168,17 +210,15 @@ class _RasterizeGaussians(torch.autograd.Function):
             raster_settings.prefiltered,
             raster_settings.debug,
         )
-        # the screen-space filter (include/gsr_aa.h): a keyword of the binding, so the debug snapshot holds the same tuple
-        kw = {"antialiasing": True} if antialiasing else {}
-        camera_model = camera[0] if len(camera) in (1, 4) else None   # (include/gsr_camera_model.h): a keyword of the binding too
-        if camera_model is not None:
-            kw["camera_model"] = camera_model
-        if len(camera) == 4 and camera[3] is not None and raster_settings.debug:   # the handle of the intrinsics and the model agree
-            _C.camera_model_matches(camera_model, camera[3])
+        # the screen-space filter (include/gsr_aa.h) and the camera model (include/gsr_camera_model.h): keywords of the binding, so
+        # the debug snapshot holds the same tuple
+        kw = {"antialiasing": True} if options.antialiasing else {}
+        if options.camera_model is not None:
+            kw["camera_model"] = options.camera_model
         maps = ()
-        if depth_alpha is not None:
+        if options.depth_alpha is not None:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer, *maps = \
-                _C.rasterize_gaussians_depth_alpha(depth_alpha, *args, **kw)
+                _C.rasterize_gaussians_depth_alpha(options.depth_alpha, *args, **kw)
         elif raster_settings.debug:  # reference __init__.py:87-94
             cpu_args = cpu_deep_copy_tuple(args)
             try:
@@ -189,140 +229,64 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise ex
         else:
             num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _C.rasterize_gaussians(*args, **kw)
-
-        if contrib_stats is not None:
-            # the blend-weight statistics of this view (include/gsr_contrib.h), from the state the render just left: once per forward,
-            # gradients enabled or not, never in backward
-            _C.gaussian_contributions(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
-                                      raster_settings.image_width, raster_settings.image_height, contrib_stats, contrib_pixel_weight,
-                                      raster_settings.debug)
-
-        fmap = ()
-        if _features is not None:
-            # the feature map, from the state the render just left and the weights it blended the colours with
-            fmap = (_C.features_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
-                                        raster_settings.image_width, raster_settings.image_height, _features, raster_settings.debug),)
-
-        dmap = dstate = ()
-        if _distortion:
-            # the distortion map, from the same state and weights and the records' depth values
-            d, st = _C.distortion_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
-                                          raster_settings.image_width, raster_settings.image_height, raster_settings.debug)
-            dmap, dstate = (d,), (st,)
-
-        mmap = mstate = ()
-        if _median or _index_maps is not None:
-            # the median-depth map and / or the caller's index maps, from the same state: one launch for both, gradients enabled or not
-            md, mst = _C.median_forward(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
-                                        raster_settings.image_width, raster_settings.image_height, _index_maps, _median,
-                                        raster_settings.debug)
-            if _median:
-                mmap, mstate = (md,), (mst,)
-
-        ctx.raster_settings = raster_settings
-        ctx.densify_stats = densify_stats
-        ctx.features = _features is not None   # then input 0 is `features` and every other input sits one place further back
-        ctx.distortion = _distortion           # then input 0 is `features` too, a tensor or None
-        ctx.median = _median
-        # how many inputs of the applied Function sit in front of this class's own
-        ctx.lead = _lead if _lead is not None else (1 if (_features is not None or _distortion) else 0)
-        ctx.num_rendered = num_rendered
-        ctx.antialiasing = antialiasing
-        ctx.depth_alpha = depth_alpha
-        ctx.camera = len(camera) == 3
-        ctx.camera_model = camera_model
-        ctx.camera_cm = len(camera) == 4   # viewmatrix, campos and the intrinsics (or None) behind the model (include/gsr_cam_cm.h)
-        ctx.absgrad = absgrad
-        # after the reference's ten: the aux state of the maps, the distortion map's and the median depth's per-pixel state, and the
-        # opacity input that the anti-aliased backward reads (the records hold opacity * rho), each saved on its path only
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *(() if _features is None else (_features,)), *maps[2:], *dstate, *mstate,
-                              *((opacities,) if antialiasing else ()))
-        ctx.mark_non_differentiable(radii)
-        # no zero tensor for the (integer) radii output on the way back: autograd would fill P words per step for nothing
-        ctx.set_materialize_grads(False)
-        return (color, radii, *maps[:2], *dmap, *mmap, *fmap)
+        # the reference's ten saved tensors
+        state = dict(colors_precomp=colors_precomp, means3D=means3D, scales=scales, rotations=rotations, cov3Ds_precomp=cov3Ds_precomp,
+                     radii=radii, sh=sh, geomBuffer=geomBuffer, binningBuffer=binningBuffer, imgBuffer=imgBuffer)
+        return after_render(ctx, options, features, raster_settings, P, num_rendered, color, radii, maps, state, opacities)
 
     @staticmethod
-    def backward(ctx, grad_out_color, _, grad_depth=None, grad_alpha=None):
-        return _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, None)[1]
-
-    @staticmethod
-    def backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grad_features_map, grad_distortion=None, grad_median=None):
-        """-> (dL/dfeatures or None, the gradient tuple of this class's inputs)"""
-        num_rendered = ctx.num_rendered
-        raster_settings = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer, *extra) = ctx.saved_tensors
-        off = ctx.lead
-        n_in = 15 + (3 if ctx.camera else 0) + (1 if ctx.camera_model is not None else 0) + (3 if ctx.camera_cm else 0)
-        fb = None
-        if ctx.features:
-            features, extra = extra[0], extra[1:]
-            if grad_features_map is not None and ctx.needs_input_grad[0] and not any(ctx.needs_input_grad[1:]):
-                # features on a frozen scene: their gradient alone, no colour backward, no gradient slots
-                return (_C.features_backward_only(geomBuffer, binningBuffer, imgBuffer, num_rendered, int(means3D.size(0)),
-                                                  raster_settings.image_width, raster_settings.image_height, features,
-                                                  grad_features_map, raster_settings.debug), (None,) * n_in)
-            if grad_features_map is not None:   # (no gradient reached the map: the feature pass is skipped)
-                fb = _C.FeatureBackward(features, grad_features_map)
-        if grad_out_color is None:  # the image took no part in the loss: the zero gradient autograd would have materialised
-            grad_out_color = torch.zeros((3, int(raster_settings.image_height), int(raster_settings.image_width)),
-                                         dtype=torch.float32, device=means3D.device)
-        if ctx.distortion and grad_distortion is not None:
-            # (no gradient reached the map: nothing of it runs, and without dL/dD and dL/dA the default backward kernels do)
-            kw_dist = {"distortion": _C.DistortionBackward(extra[1], grad_distortion)}
-        else:
-            kw_dist = {}
-        if ctx.median and grad_median is not None:   # the same for the median depth; its state sits behind the distortion state
-            kw_dist["median"] = _C.MedianBackward(extra[2 if ctx.distortion else 1], grad_median)
-        kw = {"antialiasing": True, "opacities": extra[-1]} if ctx.antialiasing else {}
-        cam_needs = tuple(ctx.needs_input_grad[15 + off:18 + off]) if ctx.camera else ()
-        if any(cam_needs):
+    def backward(ctx, *grad_outputs):
+        plan = before_backward(ctx, _RasterizeGaussians.INPUTS, grad_outputs)
+        if plan.answer is not None:
+            return tuple(map(plan.answer.get, _RasterizeGaussians.INPUTS))
+        raster_settings, options, s = ctx.raster_settings, ctx.options, plan.saved
+        kw = {"antialiasing": True, "opacities": s["opacities"]} if options.antialiasing else {}
+        if plan.camera == "cam":
             kw["camera_grads"] = True
-        cm_needs = tuple(ctx.needs_input_grad[16 + off:19 + off]) if ctx.camera_cm else ()
-        if any(cm_needs):
+        if plan.camera == "cm":
             kw["camera_model_grads"] = True
-        if fb is not None:
-            kw["features"] = fb
-        if ctx.absgrad is not None:
-            kw["absgrad"] = ctx.absgrad
-        if ctx.camera_model is not None:
-            kw["camera_model"] = ctx.camera_model
+        if plan.features is not None:
+            kw["features"] = plan.features
+        if options.absgrad is not None:
+            kw["absgrad"] = options.absgrad
+        if options.camera_model is not None:
+            kw["camera_model"] = options.camera_model
 
         # argument order of _C.rasterize_gaussians_backward: reference __init__.py:118-138
         args = (
             raster_settings.bg,
-            means3D,
-            radii,
-            colors_precomp,
-            scales,
-            rotations,
+            s["means3D"],
+            s["radii"],
+            s["colors_precomp"],
+            s["scales"],
+            s["rotations"],
             raster_settings.scale_modifier,
-            cov3Ds_precomp,
+            s["cov3Ds_precomp"],
             raster_settings.viewmatrix,
             raster_settings.projmatrix,
             raster_settings.tanfovx,
             raster_settings.tanfovy,
-            grad_out_color,
-            sh,
+            plan.grad_color,
+            s["sh"],
             raster_settings.sh_degree,
             raster_settings.campos,
-            geomBuffer,
-            num_rendered,
-            binningBuffer,
-            imgBuffer,
+            s["geomBuffer"],
+            ctx.num_rendered,
+            s["binningBuffer"],
+            s["imgBuffer"],
             raster_settings.debug,
         )
-        if grad_depth is not None or grad_alpha is not None or kw_dist:
-            # (the map's gradient alone still takes the aux kernels: they write the slots' dL/dv word and chain it)
-            hw = lambda g: None if g is None else g.reshape(g.shape[-2:])
-            grads = _C.rasterize_gaussians_backward_depth_alpha(ctx.depth_alpha, *args[:-1], extra[0], hw(grad_depth), hw(grad_alpha),
-                                                                raster_settings.debug, stats=ctx.densify_stats, **kw, **kw_dist)
-        elif raster_settings.debug and ctx.depth_alpha is None and not any(cam_needs) and not any(cm_needs):  # reference __init__.py:141-148
+        if plan.aux:
+            if plan.distortion is not None:
+                kw["distortion"] = plan.distortion
+            if plan.median is not None:
+                kw["median"] = plan.median
+            grads = _C.rasterize_gaussians_backward_depth_alpha(options.depth_alpha, *args[:-1], s["aux_state"], *plan.map_grads,
+                                                                raster_settings.debug, stats=options.densify_stats, **kw)
+        elif raster_settings.debug and options.depth_alpha is None and plan.camera is None:  # reference __init__.py:141-148
             cpu_args = cpu_deep_copy_tuple(args)
             try:
-                grads = _C.rasterize_gaussians_backward(*args, stats=ctx.densify_stats, **kw)
+                grads = _C.rasterize_gaussians_backward(*args, stats=options.densify_stats, **kw)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_bw.dump")
                 print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
@@ -330,99 +294,19 @@ class _RasterizeGaussians(torch.autograd.Function):
         else:
             # gradients of inputs that were not provided have no consumer below: the binding skips them.  (Neither map in the loss:
             # the default backward kernels, at the default cost.)
-            grads = _C.rasterize_gaussians_backward(*args, lean=not raster_settings.debug, stats=ctx.densify_stats, **kw)
+            grads = _C.rasterize_gaussians_backward(*args, lean=not raster_settings.debug, stats=options.densify_stats, **kw)
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = grads[:8]
-        cam_grads = ()
-        if ctx.camera:
-            cam_grads = camera_grad_results(cam_needs, grads[8:], (raster_settings.viewmatrix, raster_settings.projmatrix,
-                                                                   raster_settings.campos)) if any(cam_needs) else (None, None, None)
-        if ctx.camera_cm:
-            cam_grads = camera_model_grad_results(cm_needs, grads[8:], raster_settings) if any(cm_needs) else (None, None, None)
 
-        # gradient order: reference __init__.py:154-164
-        grad_features = None
-        if fb is not None:   # (no Gaussian: nothing ran)
-            grad_features = fb.grad if fb.grad is not None else torch.zeros_like(fb.features)
-        return grad_features, (
-            grad_means3D,
-            grad_means2D,
-            grad_sh if (sh.numel() != 0 and grad_sh is not None) else None,
-            grad_colors_precomp if colors_precomp.numel() != 0 else None,
-            grad_opacities,
-            grad_scales if scales.numel() != 0 else None,
-            grad_rotations if rotations.numel() != 0 else None,
-            grad_cov3Ds_precomp if cov3Ds_precomp.numel() != 0 else None,
-            None,
-            None,
-            None,
-            None,
-            None,
-            None,
-            None,
-            *(cam_grads if ctx.camera else ()),
-            *((None,) if ctx.camera_model is not None else ()),
-            *(cam_grads if ctx.camera_cm else ()),
-        )
-
-
-class _RasterizeGaussiansFeatures(torch.autograd.Function):
-    """_RasterizeGaussians with `features` (P, K) in front of its inputs -> (color, radii[, depth, alpha], feature_map (K, H, W)):
-    feature_map = sum_i features[i] alpha_i T_i with the colour pass's own weights, differentiable w.r.t. features and, through the
-    gradient slots of the colour backward, w.r.t. every geometry input (include/gsr_features.h).  Colour, radii and maps have the
-    bits of _RasterizeGaussians."""
-
-    @staticmethod
-    def forward(ctx, features, *inputs):
-        return _RasterizeGaussians.forward(ctx, *inputs, _features=features)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _, *grads):
-        grad_depth, grad_alpha = grads[:2] if len(grads) == 3 else (None, None)
-        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, grads[-1])
-        return (grad_features, *rest)
-
-
-class _RasterizeGaussiansDistortion(torch.autograd.Function):
-    """_RasterizeGaussians with a depth_alpha mode and the distortion map -> (color, radii, depth, alpha, distortion (1, H, W)
-    [, feature_map]): distortion = sum_{j<i} w_i w_j (v_i - v_j)^2 with the colour pass's own weights and the depth values of the
-    depth map, differentiable w.r.t. every geometry input through the gradient slots of the aux backward
-    (include/gsr_distortion.h).  `features` (P, K) or None sits in front of the inputs, as in _RasterizeGaussiansFeatures.  The other
-    outputs have the bits of _RasterizeGaussians."""
-
-    @staticmethod
-    def forward(ctx, features, *inputs):
-        return _RasterizeGaussians.forward(ctx, *inputs, _features=features, _distortion=True)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _, grad_depth, grad_alpha, grad_distortion, *grad_fmap):
-        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha,
-                                                                grad_fmap[0] if grad_fmap else None, grad_distortion)
-        return (grad_features, *rest)
-
-
-class _RasterizeGaussiansMedian(torch.autograd.Function):
-    """_RasterizeGaussians with the median-depth map and / or the per-pixel index maps (include/gsr_median.h) ->
-    (color, radii[, depth, alpha[, distortion][, median_depth (1, H, W)]][, feature_map]).  In front of the inputs: `features` (P, K)
-    or None, the distortion and median_depth flags, and index_maps = None or (median_index, dominant_index, dominant_weight), written
-    in place by the forward.  median_depth is v of the last blended Gaussian with T > 0.5, differentiable in v only: its gradient is
-    added into the aux backward's slots and chained to means3D along the view z axis.  The other outputs have the bits of
-    _RasterizeGaussians."""
-
-    @staticmethod
-    def forward(ctx, features, distortion, median_depth, index_maps, *inputs):
-        return _RasterizeGaussians.forward(ctx, *inputs, _features=features, _distortion=distortion, _median=median_depth,
-                                           _index_maps=index_maps, _lead=4)
-
-    @staticmethod
-    def backward(ctx, grad_out_color, _, *grads):
-        g = list(grads)
-        grad_depth, grad_alpha = (g.pop(0), g.pop(0)) if ctx.depth_alpha is not None else (None, None)
-        grad_distortion = g.pop(0) if ctx.distortion else None
-        grad_median = g.pop(0) if ctx.median else None
-        grad_features, rest = _RasterizeGaussians.backward_with(ctx, grad_out_color, grad_depth, grad_alpha, g[0] if g else None,
-                                                                grad_distortion, grad_median)
-        return (grad_features, None, None, None, *rest)
+        # reference __init__.py:154-164: no gradient for an input that was not provided
+        out = after_backward(plan, grads[8:], raster_settings)
+        out.update(means3D=grad_means3D, means2D=grad_means2D, opacities=grad_opacities,
+                   sh=grad_sh if (s["sh"].numel() != 0 and grad_sh is not None) else None,
+                   colors_precomp=grad_colors_precomp if s["colors_precomp"].numel() != 0 else None,
+                   scales=grad_scales if s["scales"].numel() != 0 else None,
+                   rotations=grad_rotations if s["rotations"].numel() != 0 else None,
+                   cov3Ds_precomp=grad_cov3Ds_precomp if s["cov3Ds_precomp"].numel() != 0 else None)
+        return tuple(map(out.get, _RasterizeGaussians.INPUTS))   # everything not named: None
 
 
 CameraModel = _C.CameraModel   # (model, fx, fy, cx, cy): the `camera_model` keyword, see GaussianRasterizer
@@ -556,27 +440,16 @@ class GaussianRasterizer(nn.Module):
                  contrib_pixel_weight=None, camera_grads=False, absgrad=None, distortion=False, median_depth=False, index_maps=None,
                  camera_model=None, camera_model_grads=False):
         super().__init__()
-        if depth_alpha is not None:
-            _C.aux_mode(depth_alpha)   # ValueError for an unknown mode
-        self.distortion = _C.distortion_flag(distortion, depth_alpha)   # TypeError for anything but a bool, ValueError without a mode
-        self.median_depth = _C.median_flag(median_depth, depth_alpha)   # the same
-        # TypeError for anything but a 3-tuple, ValueError for wrong tensors
-        if index_maps is not None:
-            _C.index_map_tensors(index_maps, raster_settings.image_width, raster_settings.image_height)
-        self.index_maps = index_maps
-        self.antialiasing = _C.aa_flag(antialiasing)   # TypeError for anything but a bool
-        self.camera_grads = _C.camera_flag(camera_grads)   # the same
-        # TypeError for anything but a CameraModel / 5-tuple, ValueError for bad values, NotImplementedError with camera_grads
-        self.camera_model = _C.camera_model(camera_model)
-        _C.camera_model_excludes(self.camera_model, self.camera_grads)
-        # ValueError without a model or for a wrong tensor, TypeError for anything but a bool or a tensor
-        self.camera_model_grads = _C.camera_model_grads_arg(camera_model_grads, self.camera_model)
+        # every keyword is checked here, as each call checks it again: the exceptions are those of _C.render_options()
+        options, intrinsics = _C.render_options(raster_settings, depth_alpha, densify_stats, antialiasing, contrib_stats,
+                                                contrib_pixel_weight, camera_grads, absgrad, distortion, median_depth, index_maps,
+                                                camera_model, camera_model_grads)
         self.raster_settings = raster_settings
-        self.densify_stats = densify_stats
-        self.depth_alpha = depth_alpha
-        self.contrib_stats = contrib_stats
-        self.contrib_pixel_weight = contrib_pixel_weight
-        self.absgrad = absgrad
+        self.densify_stats, self.depth_alpha, self.antialiasing = densify_stats, depth_alpha, antialiasing
+        self.contrib_stats, self.contrib_pixel_weight, self.absgrad = contrib_stats, contrib_pixel_weight, absgrad
+        self.distortion, self.median_depth, self.index_maps = distortion, median_depth, index_maps
+        self.camera_grads, self.camera_model = camera_grads, options.camera_model
+        self.camera_model_grads = intrinsics if intrinsics is not None else options.camera == "cm"
 
     def markVisible(self, positions):
         # Mark visible points (based on frustum culling for camera) with a boolean

@@ -8,6 +8,13 @@ GaussianRasterizer, fused_params.rasterize_leaf_gaussians, view_parallel.rasteri
 {plain, leaf} x {no maps, "depth", "invdepth"} x {filter off, on}; the plain path with precomputed colours and covariances; the plain
 path with densification statistics; the view-parallel path with the filter off and on.  The loss uses every output (random upstream
 gradients for image, depth and alpha).  Written per variant: every output, every input gradient, the statistics tensors.
+
+The options, each through GaussianRasterizer ("plain_opt_*") and rasterize_leaf_gaussians ("leaf_opt_*"): features (K = 1 and 5);
+distortion, median_depth and index_maps alone and all together with features; camera_grads; camera_model pinhole and fisheye;
+camera_model_grads as True and as the intrinsics tensor; absgrad; contrib_stats with a pixel weight; the frozen scene where only
+`features` requires a gradient; and one case per map where the map is produced and takes no part in the loss.  Written per case:
+every output, the gradient of every input (the camera tensors and the intrinsics count as inputs; an input without a gradient is
+written as an empty array) and every tensor written in place (index maps, absgrad, contrib and densification statistics).
 """
 import argparse
 import os
@@ -105,6 +112,83 @@ def main():
             outs = view_parallel.rasterize_view_parallel(t["means3D"], t["means2D"], t["shs"], t["opacities"], t["scales"],
                                                          t["rotations"], st, ex, stats=stats, antialiasing=aa)
             finish(f"viewparallel_{sh_mode}_{'aa' if aa else 'noaa'}", outs, t, stats)
+
+    # ---- the options -----------------------------------------------------------------------------------------------------------------
+    fx, fy = W / (2.0 * cam.tanfovx), H / (2.0 * cam.tanfovy)
+    pinhole, fisheye = ("pinhole", 0.9 * fx, 0.95 * fy, 0.5 * W + 7.3, 0.5 * H - 4.6), ("fisheye", 0.8 * fx, 0.8 * fx, 0.5 * W, 0.5 * H)
+    up = {"color": ups[0], "depth": ups[1], "alpha": ups[2], "distortion": torch.randn(1, H, W, generator=g).to(dev),
+          "median_depth": torch.randn(1, H, W, generator=g).to(dev), "feature_map": torch.randn(5, H, W, generator=g).to(dev)}
+    feats = torch.randn(P, 5, generator=g)
+    pixel_weight = torch.rand(H, W, generator=g).to(dev)
+
+    def option_case(kind, tag, opts, K=0, loss=None, camera=None, frozen=False, intrinsics=False):
+        """opts: keywords of both entry points but for placeholders: index_maps / absgrad / contrib_stats / stats = True make fresh
+        tensors.  loss: the outputs in the loss (default: all).  camera: which tensors of the settings require a gradient."""
+        opts, inplace, inputs, s = dict(opts), {}, {}, st
+        fresh = {"index_maps": lambda: (torch.zeros(H, W, dtype=torch.int32, device=dev), torch.zeros(1, H, W, dtype=torch.int32, device=dev),
+                                        torch.zeros(H, W, device=dev)),
+                 "absgrad": lambda: (torch.zeros(P, 2, device=dev), torch.zeros(P, device=dev)),
+                 "contrib_stats": lambda: (torch.zeros(P, device=dev), torch.zeros(P, device=dev), torch.zeros(P, dtype=torch.int32, device=dev)),
+                 "stats": new_stats}
+        for k, make in fresh.items():
+            if opts.get(k) is True:
+                opts[k] = make()
+                inplace.update({f"{k}{i}": t for i, t in enumerate(opts[k])})
+        if camera:
+            tensors = {n: getattr(st, n).clone().requires_grad_(True) for n in camera}
+            s = st._replace(**tensors)
+            inputs.update(tensors)
+        if intrinsics:
+            opts["camera_model_grads"] = inputs["intrinsics"] = torch.tensor(opts["camera_model"][1:], device=dev, requires_grad=True)
+        f = feats[:, :K].contiguous().to(dev).requires_grad_(True) if K else None
+        if kind == "plain":
+            t = activated()
+            if "stats" in opts:
+                opts["densify_stats"] = opts.pop("stats")
+            outs = GaussianRasterizer(s, **opts)(**{k: v.requires_grad_(not frozen) for k, v in t.items()}, features=f)
+        else:
+            pc = gsr_model.GaussianParams.from_activated(scene.means3D, scene.shs, scene.scales, scene.rotations, scene.opacities,
+                                                         device=dev, requires_grad=not frozen)
+            t = dict(zip(("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity"), pc.parameters()),
+                     means2D=torch.zeros_like(pc._xyz, requires_grad=not frozen))
+            outs = fused_params.rasterize_leaf_gaussians(pc._xyz, t["means2D"], pc._features_dc, pc._features_rest, pc._opacity,
+                                                         pc._scaling, pc._rotation, s, features=f, **opts)
+        inputs.update(t)
+        if f is not None:
+            inputs["features"] = f
+        names = ["color", "radii"] + (["depth", "alpha"] if opts.get("depth_alpha") else []) + \
+            [n for n in ("distortion", "median_depth") if opts.get(n)] + (["feature_map"] if K else [])
+        assert len(outs) == len(names), (tag, len(outs), names)
+        res = dict(zip(names, outs))
+        sum((res[n] * up[n][:res[n].shape[0]]).sum() for n in (loss or names) if n != "radii").backward()
+        torch.cuda.synchronize()
+        arrays = dict(res)
+        arrays.update({"grad_" + n: (torch.empty(0) if v.grad is None else v.grad) for n, v in inputs.items()})
+        arrays.update({"inplace_" + n: v for n, v in inplace.items()})
+        for n, v in arrays.items():
+            np.save(os.path.join(args.out_dir, f"{kind}_opt_{tag}.{n}.npy"), v.detach().cpu().numpy())
+        print(f"{kind}_opt_{tag}: {len(arrays)} arrays", flush=True)
+
+    everything = dict(depth_alpha="invdepth", distortion=True, median_depth=True)
+    for kind in ("plain", "leaf"):
+        option_case(kind, "features_k1", {}, K=1)
+        option_case(kind, "features_k5", dict(depth_alpha="depth"), K=5)
+        option_case(kind, "distortion", dict(depth_alpha="depth", distortion=True))
+        option_case(kind, "median_depth", dict(depth_alpha="depth", median_depth=True))
+        option_case(kind, "index_maps", dict(index_maps=True))
+        option_case(kind, "all_maps_features", dict(everything, index_maps=True, antialiasing=True, stats=True), K=5)
+        option_case(kind, "camera_grads", dict(camera_grads=True, depth_alpha="depth"), camera=("viewmatrix", "projmatrix", "campos"))
+        option_case(kind, "camera_model_pinhole", dict(camera_model=pinhole))
+        option_case(kind, "camera_model_fisheye", dict(camera_model=fisheye, depth_alpha="depth"))
+        option_case(kind, "camera_model_grads_true", dict(camera_model=pinhole, camera_model_grads=True), camera=("viewmatrix", "campos"))
+        option_case(kind, "camera_model_grads_tensor", dict(camera_model=fisheye, depth_alpha="depth"), camera=("viewmatrix", "campos"),
+                    intrinsics=True)
+        option_case(kind, "absgrad", dict(absgrad=True, stats=True))
+        option_case(kind, "contrib_stats", dict(contrib_stats=True, contrib_pixel_weight=pixel_weight))
+        option_case(kind, "frozen_features", dict(depth_alpha="depth"), K=5, frozen=True)
+        for unused in (("depth", "alpha"), ("distortion",), ("median_depth",), ("feature_map",)):
+            used = [n for n in ("color", "depth", "alpha", "distortion", "median_depth", "feature_map") if n not in unused]
+            option_case(kind, "unused_" + unused[0], everything, K=5, loss=used)
 
 
 if __name__ == "__main__":
