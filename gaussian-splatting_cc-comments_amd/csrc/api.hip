@@ -18,6 +18,7 @@
 #include "../../include/gsr_distortion.h"
 #include "../../include/gsr_median.h"
 #include "../../include/gsr_normals.h"
+#include "../../include/gsr_loss_ext.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1496,6 +1497,34 @@ extern "C" int gsr_l1_ssim_loss(int C, int H, int W, const float* img, const flo
 	if (!img || !gt || !loss_out || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_l1_ssim_loss: NULL pointer");
 	gsr_launch_l1_ssim(C, H, W, img, gt, lambda_dssim, loss_out, dL_dimg, scratch, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "l1_ssim_loss");
+}
+
+// ---- the fused loss with a pixel mask, an exposure and an inverse-depth term (include/gsr_loss_ext.h) ----
+extern "C" size_t gsr_loss_ext_scratch_bytes(int C, int H, int W)
+{
+	if (C <= 0 || H <= 0 || W <= 0) return 0;
+	size_t a, b, c;
+	int n, nxy;
+	return gsr_loss_ext_scratch_layout(C, H, W, &a, &b, &c, &n, &nxy);
+}
+
+extern "C" int gsr_l1_ssim_loss_ext(const gsr_loss_ext_args* args)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_l1_ssim_loss_ext";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL args", who);
+	const gsr_loss_ext_args& a = *args;
+	if (a.C <= 0 || a.H <= 0 || a.W <= 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad image size (%d x %d x %d)", who, a.C, a.H, a.W);
+	if (!a.img || !a.gt || !a.vals || !a.scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL pointer", who);
+	if (a.exposure && a.C != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: exposure needs C == 3 (got %d)", who, a.C);
+	if (a.dL_dexposure && !a.exposure) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dexposure without exposure", who);
+	if (!a.invdepth != !a.invdepth_prior) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: invdepth and invdepth_prior go together", who);
+	if (!a.invdepth && (a.invdepth_mask || a.dL_dinvdepth))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: invdepth_mask / dL_dinvdepth without invdepth and invdepth_prior", who);
+	if (!(a.invdepth_weight >= 0.f) || !std::isfinite(a.invdepth_weight))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: invdepth_weight must be finite and >= 0", who);
+	gsr_launch_l1_ssim_ext(a, (hipStream_t)a.stream);
+	return gsr_stage_done((hipStream_t)a.stream, 0, "l1_ssim_loss_ext");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

@@ -369,6 +369,11 @@ size_t gsr_loss_scratch_layout(int C, int H, int W, size_t* maps_off, size_t* pa
 void gsr_launch_l1_ssim(int C, int H, int W, const float* img, const float* gt, float lambda, float* loss_out, float* dL_dimg,
                         void* scratch, hipStream_t s);
 
+// loss_ext.hip: the same loss with a pixel mask, an exposure and an inverse-depth term (include/gsr_loss_ext.h)
+struct gsr_loss_ext_args;
+size_t gsr_loss_ext_scratch_layout(int C, int H, int W, size_t* maps_off, size_t* partial_off, size_t* epart_off, int* ntiles, int* ntiles_xy);
+void gsr_launch_l1_ssim_ext(const gsr_loss_ext_args& a, hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);
