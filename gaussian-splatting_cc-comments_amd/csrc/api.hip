@@ -19,6 +19,7 @@
 #include "../../include/gsr_median.h"
 #include "../../include/gsr_normals.h"
 #include "../../include/gsr_loss_ext.h"
+#include "../../include/gsr_bilagrid.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1525,6 +1526,81 @@ extern "C" int gsr_l1_ssim_loss_ext(const gsr_loss_ext_args* args)
 		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: invdepth_weight must be finite and >= 0", who);
 	gsr_launch_l1_ssim_ext(a, (hipStream_t)a.stream);
 	return gsr_stage_done((hipStream_t)a.stream, 0, "l1_ssim_loss_ext");
+}
+
+// ---- the bilateral grid of affine colour transforms (include/gsr_bilagrid.h) ----
+#define GSR_BILAGRID_MAX_BLOCKS ((1LL << 24) - 1)   // workgroups of 256 threads in one launch
+
+static bool gsr_bilagrid_sizes_ok(int H, int W, int L, int GH, int GW)
+{
+	return H >= 1 && W >= 1 && L >= 2 && GH >= 2 && GW >= 2;
+}
+// the kernels index pixels and grid entries with 32 bits
+static bool gsr_bilagrid_fits(long long count, int a, int b, int c) { return (double)count * a * b * c <= 2147483647.0; }
+
+static int gsr_bilagrid_check(const char* who, const gsr_bilagrid_args* args)
+{
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL args", who);
+	const gsr_bilagrid_args& a = *args;
+	if (a.H < 1 || a.W < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: bad image size (%d x %d)", who, a.H, a.W);
+	if (a.L < 2 || a.GH < 2 || a.GW < 2)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every grid axis must be at least 2 (got L %d, GH %d, GW %d)", who, a.L, a.GH, a.GW);
+	if (!gsr_bilagrid_fits(3, a.H, a.W, 1) || !gsr_bilagrid_fits(12, a.L, a.GH, a.GW))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the image or the grid exceeds 32-bit indexing", who);
+	if (gsr_bilagrid_tiles(a.H, a.W) > GSR_BILAGRID_MAX_BLOCKS || gsr_bilagrid_gather_blocks(a.H, a.L, a.GH, a.GW) > GSR_BILAGRID_MAX_BLOCKS)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the image or the grid needs more than 2^24 - 1 workgroups", who);
+	if (!a.grid || !a.img) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: grid or img is NULL", who);
+	return GSR_OK;
+}
+
+extern "C" size_t gsr_bilagrid_scratch_bytes(int H, int W, int L, int GH, int GW)
+{
+	if (!gsr_bilagrid_sizes_ok(H, W, L, GH, GW) || !gsr_bilagrid_fits(3, H, W, 1) || !gsr_bilagrid_fits(12, L, GH, GW)) return 0;
+	return gsr_bilagrid_scratch_size(H, W, L, GH, GW);
+}
+
+extern "C" int gsr_bilagrid_slice(const gsr_bilagrid_args* args)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_bilagrid_slice";
+	const int rc = gsr_bilagrid_check(who, args);
+	if (rc != GSR_OK) return rc;
+	if (!args->out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: out is NULL", who);
+	gsr_launch_bilagrid_slice(*args, (hipStream_t)args->stream);
+	return gsr_stage_done((hipStream_t)args->stream, 0, "bilagrid_slice");
+}
+
+extern "C" int gsr_bilagrid_slice_backward(const gsr_bilagrid_args* args)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_bilagrid_slice_backward";
+	const int rc = gsr_bilagrid_check(who, args);
+	if (rc != GSR_OK) return rc;
+	const gsr_bilagrid_args& a = *args;
+	if (!a.dL_dout) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dout is NULL", who);
+	if (!a.dL_dgrid && !a.dL_dimg) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dgrid and dL_dimg are both NULL", who);
+	if (a.dL_dgrid && !a.scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch is NULL", who);
+	gsr_launch_bilagrid_backward(a, (hipStream_t)a.stream);
+	return gsr_stage_done((hipStream_t)a.stream, 0, "bilagrid_backward");
+}
+
+extern "C" size_t gsr_bilagrid_tv_scratch_bytes(int N, int L, int GH, int GW)
+{
+	if (N < 1 || L < 2 || GH < 2 || GW < 2 || !gsr_bilagrid_fits(12LL * N, L, GH, GW)) return 0;
+	return gsr_bilagrid_tv_scratch_size(N, L, GH, GW);
+}
+
+extern "C" int gsr_bilagrid_tv(int N, int L, int GH, int GW, const float* grids, float* val, float* dL_dgrids, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_bilagrid_tv";
+	if (N < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: N must be at least 1 (got %d)", who, N);
+	if (L < 2 || GH < 2 || GW < 2)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every grid axis must be at least 2 (got L %d, GH %d, GW %d)", who, L, GH, GW);
+	if (!gsr_bilagrid_fits(12LL * N, L, GH, GW)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the grids exceed 32-bit indexing", who);
+	if (!grids || !val || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: grids, val or scratch is NULL", who);
+	gsr_launch_bilagrid_tv(N, L, GH, GW, grids, val, dL_dgrids, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "bilagrid_tv");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

@@ -374,6 +374,16 @@ struct gsr_loss_ext_args;
 size_t gsr_loss_ext_scratch_layout(int C, int H, int W, size_t* maps_off, size_t* partial_off, size_t* epart_off, int* ntiles, int* ntiles_xy);
 void gsr_launch_l1_ssim_ext(const gsr_loss_ext_args& a, hipStream_t s);
 
+// bilagrid.hip: the bilateral grid of affine colour transforms (include/gsr_bilagrid.h)
+struct gsr_bilagrid_args;
+long long gsr_bilagrid_tiles(int H, int W);                           // workgroups of the slice kernels
+long long gsr_bilagrid_gather_blocks(int H, int L, int GH, int GW);   // workgroups of the dL_dgrid gather
+size_t gsr_bilagrid_scratch_size(int H, int W, int L, int GH, int GW);
+size_t gsr_bilagrid_tv_scratch_size(int N, int L, int GH, int GW);
+void gsr_launch_bilagrid_slice(const gsr_bilagrid_args& a, hipStream_t s);
+void gsr_launch_bilagrid_backward(const gsr_bilagrid_args& a, hipStream_t s);
+void gsr_launch_bilagrid_tv(int N, int L, int GH, int GW, const float* grids, float* val, float* dL_dgrids, void* scratch, hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);
