@@ -174,10 +174,48 @@ class FusedAdam(torch.optim.Optimizer):
     Built like the reference builds its optimiser: `FusedAdam(l, lr=0.0, eps=1e-15)` with
     `l = [{'params': [t], 'lr': ..., 'name': ...}, ...]` (gaussian_model.py:243-252).
     `step(visible_radii=radii)` is the opt-in visible-only variant (NOT the reference's update rule):
-    Gaussians with radii <= 0 keep parameters and moments untouched; it needs every tensor's dim 0 = P."""
+    Gaussians with radii <= 0 keep parameters and moments untouched.  The kernel reads radii[row] for every
+    row of every tensor, so every parameter that has a gradient must have radii.numel() rows (dim 0 = P);
+    a step that cannot be taken is refused before any state is touched."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
+
+    def _check_step(self, visible_radii):
+        """Every refusal of step(), before a step count, a moment or a parameter is touched."""
+        if visible_radii is not None:
+            if not torch.is_tensor(visible_radii) or visible_radii.dim() != 1 or visible_radii.dtype != torch.int32 or \
+                    not visible_radii.is_cuda or not visible_radii.is_contiguous():
+                raise RuntimeError("FusedAdam: visible_radii must be a contiguous 1-D int32 tensor on the parameters' device")
+        for k, group in enumerate(self.param_groups):
+            name = f"group {group.get('name', k)!r}"
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError(f"FusedAdam, {name}: needs contiguous float32 HIP (cuda) parameters; there is no CPU path")
+                if p.grad.is_sparse:
+                    raise RuntimeError(f"FusedAdam, {name}: does not support sparse gradients")
+                if p.grad.dtype != torch.float32 or p.grad.device != p.device or p.grad.shape != p.shape:
+                    raise RuntimeError(f"FusedAdam, {name}: the gradient must be float32, on the parameter's device and of its shape")
+                state = self.state.get(p, {})
+                for key in ("exp_avg", "exp_avg_sq"):
+                    t = state.get(key)
+                    if t is None:
+                        continue
+                    if not t.is_contiguous():
+                        raise RuntimeError(f"FusedAdam, {name}: optimizer state tensors must be contiguous")
+                    if t.dtype != torch.float32 or t.device != p.device or t.shape != p.shape:
+                        raise RuntimeError(f"FusedAdam, {name}: {key} must be float32, on the parameter's device and of its shape "
+                                           f"{tuple(p.shape)}; got {t.dtype} {tuple(t.shape)} on {t.device}")
+                if ("exp_avg" in state) != ("exp_avg_sq" in state):
+                    raise RuntimeError(f"FusedAdam, {name}: exp_avg and exp_avg_sq go together")
+                if visible_radii is not None:
+                    if visible_radii.device != p.device:
+                        raise RuntimeError(f"FusedAdam, {name}: visible_radii is on {visible_radii.device}, the parameter on {p.device}")
+                    if p.dim() < 1 or p.size(0) != visible_radii.numel():
+                        raise RuntimeError(f"FusedAdam, {name}: visible_radii has {visible_radii.numel()} rows, the parameter has shape "
+                                           f"{tuple(p.shape)}: with visible_radii every parameter needs dim 0 = P")
 
     @torch.no_grad()
     def step(self, closure=None, visible_radii=None):
@@ -185,16 +223,13 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._check_step(visible_radii)
         batches = {}  # (device, betas, eps) -> [AdamGroup]
         keep = []
         for group in self.param_groups:
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("FusedAdam needs contiguous float32 HIP (cuda) parameters; there is no CPU path")
-                if p.grad.is_sparse:
-                    raise RuntimeError("FusedAdam does not support sparse gradients")
                 state = self.state[p]
                 if len(state) == 0 or "exp_avg" not in state:
                     state["step"] = state.get("step", 0)
@@ -204,20 +239,14 @@ class FusedAdam(torch.optim.Optimizer):
                 state["step"] = step
                 g = p.grad.contiguous()
                 m, v = state["exp_avg"], state["exp_avg_sq"]
-                if not (m.is_contiguous() and v.is_contiguous()):
-                    raise RuntimeError("FusedAdam: optimizer state tensors must be contiguous")
                 keep.append(g)
-                row = p.numel() // p.size(0) if (p.dim() > 0 and p.size(0) > 0) else 1
+                row = max(1, p.numel() // p.size(0)) if (p.dim() > 0 and p.size(0) > 0) else 1   # (P, 0, 3): no element, row 1
                 key = (p.device, tuple(float(b) for b in group["betas"]), float(group["eps"]))
                 batches.setdefault(key, []).append(AdamGroup(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), step,
                                                              float(group["lr"]), row))
         L = _C.lib()
         for (dev, betas, eps), groups in batches.items():
-            radii_ptr = None
-            if visible_radii is not None:
-                if visible_radii.dtype != torch.int32 or visible_radii.device != dev or not visible_radii.is_contiguous():
-                    raise RuntimeError("visible_radii must be a contiguous int32 tensor on the parameters' device")
-                radii_ptr = visible_radii.data_ptr()
+            radii_ptr = None if visible_radii is None else visible_radii.data_ptr()
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 for k in range(0, len(groups), ADAM_MAX_GROUPS):

@@ -354,6 +354,11 @@ int gsr_backward_leaf(
  * `step` is the group's 1-based step count of THIS update.  radii: NULL (reference semantics: every
  * element is updated) or [P] int -- then rows (numel/row Gaussians of `row` floats) whose radii <= 0
  * are left untouched ("visible-only" Adam; changes the optimisation, opt-in).
+ * With radii the kernel reads radii[e / row] for every element e of every group, and this call cannot
+ * know P: it is the CALLER's duty that every group has exactly P rows (numel == P * row) -- a group with
+ * more rows (a bilateral grid, an exposure in the same optimiser) reads past the end of radii, one with
+ * fewer is frozen by some other tensor's visibility.  fused_params.FusedAdam.step() refuses such a step
+ * before it touches any state.
  */
 #define GSR_ADAM_MAX_GROUPS 8
 typedef struct {
