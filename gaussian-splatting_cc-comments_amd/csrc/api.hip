@@ -20,6 +20,7 @@
 #include "../../include/gsr_normals.h"
 #include "../../include/gsr_loss_ext.h"
 #include "../../include/gsr_bilagrid.h"
+#include "../../include/gsr_mcmc.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1601,6 +1602,74 @@ extern "C" int gsr_bilagrid_tv(int N, int L, int GH, int GW, const float* grids,
 	if (!grids || !val || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: grids, val or scratch is NULL", who);
 	gsr_launch_bilagrid_tv(N, L, GH, GW, grids, val, dL_dgrids, scratch, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "bilagrid_tv");
+}
+
+// ---- fixed-budget (MCMC) training: noise injection, relocation, regulariser (include/gsr_mcmc.h) ----
+#define GSR_MCMC_MAX_BLOCKS ((1LL << 24) - 1)   // workgroups in one launch; only D can ask for more (P is held below by the 32-bit indices)
+// the kernels index every tensor with 32 bits
+static bool gsr_mcmc_fits(long long rows, long long row) { return (double)rows * (double)row <= 2147483647.0; }
+
+extern "C" int gsr_mcmc_noise(int P, float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* noise,
+                              float scaler, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_mcmc_noise";
+	if (P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, P);
+	if (!gsr_mcmc_fits(P, 4)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 4 P exceeds 32-bit indexing (P %d)", who, P);
+	if (!xyz || !opacity || !scaling || !rotation || !noise)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: xyz, opacity, scaling, rotation or noise is NULL", who);
+	gsr_launch_mcmc_noise(P, xyz, opacity, scaling, rotation, noise, scaler, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "mcmc_noise");
+}
+
+extern "C" int gsr_mcmc_relocate(const gsr_mcmc_relocate_args* args)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_mcmc_relocate";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL args", who);
+	const gsr_mcmc_relocate_args& a = *args;
+	if (a.P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, a.P);
+	if (a.D < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative entry count (D %d)", who, a.D);
+	if (a.ngroups < 1 || a.ngroups > GSR_ADAM_MAX_GROUPS) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 1..%d groups (got %d)", who, GSR_ADAM_MAX_GROUPS, a.ngroups);
+	if (!a.groups) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: groups is NULL", who);
+	if (a.opacity_group < 0 || a.opacity_group >= a.ngroups || a.scale_group < 0 || a.scale_group >= a.ngroups || a.opacity_group == a.scale_group)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity_group %d and scale_group %d must be two of the %d groups", who, a.opacity_group, a.scale_group,
+		                a.ngroups);
+	for (int k = 0; k < a.ngroups; k++) {
+		const gsr_mcmc_group& g = a.groups[k];
+		if (g.row < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: negative row", who, k);
+		if (g.row > 0 && !g.param) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: param is NULL", who, k);
+		if ((g.exp_avg != nullptr) != (g.exp_avg_sq != nullptr))
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: exp_avg and exp_avg_sq go together", who, k);
+		if (!gsr_mcmc_fits(a.P, g.row)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d exceeds 32-bit indexing (P %d, row %d)", who, k, a.P, g.row);
+	}
+	if (a.groups[a.opacity_group].row != 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the opacity group's row must be 1 (got %d)", who, a.groups[a.opacity_group].row);
+	if (a.groups[a.scale_group].row != 3) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the scale group's row must be 3 (got %d)", who, a.groups[a.scale_group].row);
+	if (!(a.min_opacity > 0.0f && a.min_opacity < 1.0f)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: min_opacity must lie in (0, 1) (got %g)", who, (double)a.min_opacity);
+	if (gsr_mcmc_relocate_blocks(a.D) > GSR_MCMC_MAX_BLOCKS) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: D needs more than 2^24 - 1 workgroups (D %d)", who, a.D);
+	if (a.D == 0) return GSR_OK;   // nothing to launch
+	if (!a.dst || !a.src || !a.counts) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dst, src or counts is NULL", who);
+	const int rc = gsr_launch_mcmc_relocate(a, (hipStream_t)a.stream);
+	if (rc != GSR_OK) return rc;
+	return gsr_stage_done((hipStream_t)a.stream, 0, "mcmc_relocate");
+}
+
+extern "C" size_t gsr_mcmc_regularizer_scratch_bytes(int P)
+{
+	if (P < 1 || !gsr_mcmc_fits(P, 3)) return 0;
+	return gsr_mcmc_reg_scratch_size(P);
+}
+
+extern "C" int gsr_mcmc_regularizer(int P, const float* opacity, const float* scaling, float w_o, float w_s, float* val, float* dL_dopacity,
+                                    float* dL_dscaling, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_mcmc_regularizer";
+	if (P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, P);
+	if (!gsr_mcmc_fits(P, 3)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 3 P exceeds 32-bit indexing (P %d)", who, P);
+	if (!opacity || !scaling || !val || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity, scaling, val or scratch is NULL", who);
+	gsr_launch_mcmc_regularizer(P, opacity, scaling, w_o, w_s, val, dL_dopacity, dL_dscaling, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "mcmc_reg");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

@@ -384,6 +384,16 @@ void gsr_launch_bilagrid_slice(const gsr_bilagrid_args& a, hipStream_t s);
 void gsr_launch_bilagrid_backward(const gsr_bilagrid_args& a, hipStream_t s);
 void gsr_launch_bilagrid_tv(int N, int L, int GH, int GW, const float* grids, float* val, float* dL_dgrids, void* scratch, hipStream_t s);
 
+// mcmc.hip: noise injection, relocation and the regulariser of fixed-budget training (include/gsr_mcmc.h)
+struct gsr_mcmc_relocate_args;
+long long gsr_mcmc_relocate_blocks(int D);   // workgroups of the per-entry launches
+size_t gsr_mcmc_reg_scratch_size(int P);
+void gsr_launch_mcmc_noise(int P, float* xyz, const float* opacity, const float* scaling, const float* rotation, const float* noise, float scaler,
+                           hipStream_t s);
+int gsr_launch_mcmc_relocate(const gsr_mcmc_relocate_args& a, hipStream_t s);   // GSR_OK, or the code of a failed memset
+void gsr_launch_mcmc_regularizer(int P, const float* opacity, const float* scaling, float w_o, float w_s, float* val, float* dL_dopacity,
+                                 float* dL_dscaling, void* scratch, hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);
