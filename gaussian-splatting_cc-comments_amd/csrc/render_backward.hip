@@ -19,9 +19,26 @@
 // reproducible.  Per-pixel arithmetic is that of backward.cu:507-599; G and alpha come
 // from the same roundings as in the forward kernel (gsr_pair_power; the forward's pre-halved conic terms give the same
 // bits), so the products the forward formed are the ones undone here.
+//
+// A lane's four pixels are two packed pairs: pair p holds the tile's band 2p (rows 8p .. 8p+3) in the .x halves of its v2f
+// registers and band 2p+1 in the .y halves.  Per staged instance each pair has a wave-uniform mode, two bits that say which of its
+// bands can be reached (gsr_tile_band_mask) and still have an instance to come (the band's largest n_contrib lies behind this one):
+//   0  the pair is skipped;
+//   3  the packed body: every operation a v_pk_*_f32 on both halves;
+//   1, 2  the same operations in the same order as plain fp32 instructions on the .x or the .y half alone.  The other band could
+//         not have hit: its alpha would be forced to 0, its state update the identity bit for bit, its additions exact zeros --
+//         leaving it out leaves the same sums (the sign of a zero in a per-lane partial aside, which the per-Gaussian pass,
+//         adding every slot to 0.f, does not see).
+// The modes are decided by the staging lanes; the body is written once over the mode (gsr_half below, the lambda `pair` in the kernel).  The default
+// instantiation has all four modes; AUX and ABS have no registers for them and evaluate every pair that is not skipped whole.
+// With GSR_DEBUG_NO_CULL every pair that has an instance left is evaluated whole by every instantiation.
 #include "render_common.h"
+#include <type_traits>
 
 #define GSR_BWD_NV 9
+#ifndef GSR_BWD_BAND_LAST
+#define GSR_BWD_BAND_LAST 1   // 0 (A/B builds): a band is left out of a pair by the band mask alone, not by its largest n_contrib
+#endif
 #define GSR_BWD_FLUSH 4   // reduced instances finished together (default variant): 4 x (8 values + 8 groups of the ninth) = 64 lanes
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -36,6 +53,44 @@ __device__ __forceinline__ float gsr_add_halves(v2f a)
 	return r;
 }
 
+// The pair body (the lambda `pair` in the kernel) is written once over a "mode" M, the pair's two reachable-band bits: M = 3 works on both halves of
+// every register pair (v2f: v_pk_*_f32), M = 1 on the .x half and M = 2 on the .y half alone (float: plain fp32 instructions that
+// name that half of the pair as their register; the other half is neither read nor written).  gsr_half<M> is the value type with
+// its access to a pair; the overloads below are the operations that have no common spelling for float and v2f.
+template <int M> struct gsr_half;
+template <> struct gsr_half<3> {
+	typedef v2f type;
+	static __device__ __forceinline__ v2f get(const v2f& a) { return a; }
+	static __device__ __forceinline__ void set(v2f& d, v2f s) { d = s; }
+	static __device__ __forceinline__ v2f select(bool h0, bool h1, v2f a) { return v2f{h0 ? a.x : 0.f, h1 ? a.y : 0.f}; }
+};
+template <> struct gsr_half<1> {
+	typedef float type;
+	static __device__ __forceinline__ float get(const v2f& a) { return a.x; }
+	static __device__ __forceinline__ void set(v2f& d, float s) { d.x = s; }
+	static __device__ __forceinline__ float select(bool h0, bool, float a) { return h0 ? a : 0.f; }
+};
+template <> struct gsr_half<2> {
+	typedef float type;
+	static __device__ __forceinline__ float get(const v2f& a) { return a.y; }
+	static __device__ __forceinline__ void set(v2f& d, float s) { d.y = s; }
+	static __device__ __forceinline__ float select(bool, bool h1, float a) { return h1 ? a : 0.f; }
+};
+__device__ __forceinline__ float gsr_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ v2f gsr_fma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ float gsr_exp2(float a) { return __builtin_amdgcn_exp2f(a); }
+__device__ __forceinline__ v2f gsr_exp2(v2f a) { return v2f{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)}; }
+__device__ __forceinline__ float gsr_rcp(float a) { return __builtin_amdgcn_rcpf(a); }
+__device__ __forceinline__ v2f gsr_rcp(v2f a) { return v2f{__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)}; }
+__device__ __forceinline__ float gsr_min99(float a) { return fminf(0.99f, a); }
+__device__ __forceinline__ v2f gsr_min99(v2f a) { return v2f{fminf(0.99f, a.x), fminf(0.99f, a.y)}; }
+__device__ __forceinline__ float gsr_lo(float a) { return a; }   // the value of the first / the second band of the mode
+__device__ __forceinline__ float gsr_lo(v2f a) { return a.x; }
+__device__ __forceinline__ float gsr_hi(float a) { return a; }
+__device__ __forceinline__ float gsr_hi(v2f a) { return a.y; }
+__device__ __forceinline__ float gsr_abs_sum(float a) { return __builtin_fabsf(a); }
+__device__ __forceinline__ float gsr_abs_sum(v2f a) { return __builtin_fabsf(a.x) + __builtin_fabsf(a.y); }
+
 // AUX (the depth-and-alpha variant, include/gsr.h gsr_aux_args): the depth channel is a fourth colour channel with background 0 --
 // its accum_rec (restarted from ckpt_depth / final_D by the depth segments), (v - accum_rec_D) dL/dD in dL/dalpha -- dL/dA enters
 // through the background term (A = 1 - T_final: -T_final (bg . dL/dpix - dL/dA)), and dL/dv = sum alpha T dL/dD is a tenth reduced
@@ -47,7 +102,8 @@ __device__ __forceinline__ float gsr_add_halves(v2f a)
 // on its own, as the AUX ones do; the other nine (ten) words are computed by the same operations as without ABS.
 // Waves per SIMD: four (at most 128 VGPRs) for every instantiation but <AUX, ABS>.  The AUX variant alone fills the 128 (left
 // to itself the compiler takes 130), and the two accumulators, the halved b and the terms' temporaries of ABS on top spill 10
-// registers to scratch at that limit: that instantiation takes 144 VGPRs and runs three waves per SIMD, without scratch.
+// registers to scratch at that limit: that instantiation takes 146 VGPRs (144 before the pair modes' staging) and runs three waves per
+// SIMD, without scratch.
 template <bool AUX, bool ABS>
 __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu((AUX && ABS) ? 3 : 4, 4))) gsr_render_backward_wave_kernel(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
@@ -73,11 +129,15 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	// 2 KB more per wave: 9.5 KB x 16 waves still fits one CU's 160 KB at 4 waves per SIMD.  The AUX variant keeps the
 	// per-instance finish (its tenth value would leave fewer lanes per flush and its LDS would not fit 16 waves).
 	__shared__ __attribute__((aligned(16))) float s_pend[GSR_WAVES_PER_WG][(AUX || ABS) ? 4 : GSR_BWD_FLUSH * 128];
+	// the one-band pair modes (gsr_half): the default instantiation has the registers for them; AUX and ABS are full at their limits
+	// with the packed body alone (spill 28 / 10 registers, <AUX, ABS> 158 VGPRs, with the three modes) and keep evaluating whole pairs
+	constexpr bool ONE_BAND = !(AUX || ABS);
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const int slot_id = blockIdx.x * GSR_WAVES_PER_WG + wave;
 	if (slot_id >= nslots) return;  // wave-uniform; no barriers below
 	GSR_TILE_CLOCK_START();
-	GSR_TILE_STAT(unsigned long long st_staged = 0; unsigned long long st_pairs = 0; unsigned long long st_pairs_hit = 0; unsigned long long st_reductions = 0; unsigned long long st_lanes_hit = 0;)
+	GSR_TILE_STAT(unsigned long long st_staged = 0; unsigned long long st_pairs = 0; unsigned long long st_pairs_hit = 0; unsigned long long st_reductions = 0; unsigned long long st_lanes_hit = 0;
+	              unsigned long long st_one_mask = 0; unsigned long long st_one_last = 0;)   // pairs evaluated on one band: by the band mask, by band_last
 	// workgroups are dispatched in index order: tile_order lists the tiles by descending work, so the long tiles
 	// start first and the short ones fill the end of the launch (binning.hip gsr_tile_order_kernel)
 	// A heavy tile (walk of at least two checkpoint strides) comes as one entry per DEPTH SEGMENT (bits 28..31 = segment + 1):
@@ -171,15 +231,15 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			}
 		}
 	}
-	// wave-uniform: the largest n_contrib among the 128 pixels of each pair; instances at or beyond it
-	// were blended into none of them, so the pair is skipped without evaluating anything
-	int pair_last[2];
+	// wave-uniform: the largest n_contrib among the 64 pixels of each band; instances at or beyond it
+	// were blended into none of them, so the staging lanes clear the band's bit and nothing of it is evaluated
+	int band_last[GSR_PIX_PER_LANE];
 #pragma unroll
-	for (int p = 0; p < 2; p++) {
-		int m = max(last_contributor[2 * p], last_contributor[2 * p + 1]);
+	for (int k = 0; k < GSR_PIX_PER_LANE; k++) {
+		int m = last_contributor[k];
 #pragma unroll
 		for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
-		pair_last[p] = __builtin_amdgcn_readfirstlane(m);
+		band_last[k] = __builtin_amdgcn_readfirstlane(m);
 	}
 
 	// back to front: batch position q = base + lane maps to range position top - 1 - q (top = n for a whole tile, the end of the segment otherwise)
@@ -214,8 +274,18 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	uint32_t pend_j = 0u;   // wave-uniform: their batch indices j, eight bits each (unused bytes 0, so every lane reads inside rec)
 
 	for (int base = 0; base < nw; base += 64) {
-		const uint32_t bands = (base + lane < nw) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
-		const bool keep = bands != 0u;
+		const uint32_t reach = (base + lane < nw) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
+		// The bands that still have an instance to come: at or beyond a band's largest n_contrib this one was blended into none of
+		// its pixels (c0 / c1 below false in all lanes).  Decided here, 64 instances per instruction, so that the walk below reads a
+		// pair's mode out of two bits: a scalar chain of compares and selects in front of each pair's branch cost the step 1.5 %.
+		const int position = top - 1 - (base + lane);   // in the full range
+		uint32_t live = 0u;
+#pragma unroll
+		for (int k = 0; k < GSR_PIX_PER_LANE; k++) live |= position < band_last[k] ? 1u << k : 0u;
+		// GSR_DEBUG_NO_CULL (and the A/B build without this): a pair lives while either of its bands does, and is evaluated whole
+		if (!(cull && GSR_BWD_BAND_LAST)) live = ((live & 3u) ? 3u : 0u) | ((live & 12u) ? 12u : 0u);
+		const uint32_t bands = reach & live;
+		const bool keep = cull ? bands != 0u : reach != 0u;   // (without the cull every instance is staged)
 		const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
 		const int cnt = __popcll(mask);
 		GSR_TILE_STAT(st_staged += (unsigned)cnt;)
@@ -229,9 +299,9 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			rec[1][pos] = make_float4(-0.5f * ra.z, -0.5f * ra.z, ra.w, ra.w);  // -0.5 conic a, conic b
 			rec[2][pos] = make_float4(-0.5f * rb.x, -0.5f * rb.x, rb.y, rb.y);  // -0.5 conic c, opacity
 			rec[3][pos] = make_float4(rc.x, rc.x, rc.y, rc.y);  // r, g
-			rec[4][pos] = make_float4(rc.z, rc.z, __int_as_float(top - 1 - (base + lane)), __uint_as_float(slot));  // b, position in the full range, slot
+			rec[4][pos] = make_float4(rc.z, rc.z, __int_as_float(position), __uint_as_float(slot));  // b, position in the full range, slot
 			if (AUX) rec[5][pos] = make_float4(rc.w, rc.w, 0.f, 0.f);   // depth value v
-			recb[pos] = bands;
+			recb[pos] = bands | (reach << 4);   // (bits 4..7: the band mask alone, for the diagnostic counters)
 		}
 		if (base + 64 + lane < nw) {
 			const float4* p = reinterpret_cast<const float4*>(splat + id_next);
@@ -269,46 +339,58 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 #pragma unroll
 			for (int i = 0; i < GSR_BWD_NV + 1; i++) acc[i] = v2f{-0.f, -0.f};  // x + (-0) is x for every x: the first pair's sums need no add
 			unsigned long long any = 0ull;  // lanes with a hit, kept as a scalar mask: the loop's branches test masks, not ballots of bools
-#pragma unroll
-			for (int p = 0; p < 2; p++) {
-				if (!(bands & (3u << (2 * p))) || contributor >= pair_last[p]) continue;  // scalar branch: no band of this pair can be reached
+			// One pair in mode M (its reachable bands: 3 both, 1 the .x band, 2 the .y band): the same operations in the same order
+			// on a v2f or on one half of every register pair.  A band left out could not have hit: its alpha would be forced to 0,
+			// its state update the identity bit for bit, and its additions exact zeros.
+			auto pair = [&](auto pc, auto mc) {
+				constexpr int p = decltype(pc)::value, M = decltype(mc)::value;
+				typedef gsr_half<M> Hf;
+				typedef typename Hf::type V_t;
 				// power = -0.5f * (a*dx*dx + c*dy*dy) - b*dx*dy in the reference's operation order (CA, CC carry the -0.5)
-				const v2f dy = Y - pfy[p];
-				const v2f power = (ax2 + (CC * dy) * dy) - bdx * dy;
+				const V_t dxh = Hf::get(dx);
+				const V_t dy = Hf::get(Y) - Hf::get(pfy[p]);
+				const V_t power = (Hf::get(ax2) + (Hf::get(CC) * dy) * dy) - Hf::get(bdx) * dy;
 				// __expf(x) = v_exp_f32(x * log2(e)) (the forward's form, same constant, same IEEE product): the two products as one
 				// packed multiply
-				const v2f pl = power * 1.44269504088896340736f;
-				const v2f G = {__builtin_amdgcn_exp2f(pl.x), __builtin_amdgcn_exp2f(pl.y)};
-				const v2f og = OP * G;
-				const v2f araw = {fminf(0.99f, og.x), fminf(0.99f, og.y)};
-				const bool c0 = contributor < last_contributor[2 * p], p0 = !(power.x > 0.0f), a0 = !(araw.x < 1.0f / 255.0f);
-				const bool c1 = contributor < last_contributor[2 * p + 1], p1 = !(power.y > 0.0f), a1 = !(araw.y < 1.0f / 255.0f);
-				const bool hit0 = c0 && p0 && a0, hit1 = c1 && p1 && a1;
+				const V_t pl = power * 1.44269504088896340736f;
+				const V_t G = gsr_exp2(pl);
+				const V_t og = Hf::get(OP) * G;
+				const V_t araw = gsr_min99(og);
 				// each ballot of ONE comparison is that comparison's own lane mask (no instruction); a ballot of the combined
 				// bool costs a v_cndmask + v_cmp round trip through a VGPR
-				const unsigned long long hits = (__builtin_amdgcn_ballot_w64(c0) & __builtin_amdgcn_ballot_w64(p0) & __builtin_amdgcn_ballot_w64(a0)) |
-				                                (__builtin_amdgcn_ballot_w64(c1) & __builtin_amdgcn_ballot_w64(p1) & __builtin_amdgcn_ballot_w64(a1));
+				bool hit0 = false, hit1 = false;
+				unsigned long long hits = 0ull;
+				if constexpr ((M & 1) != 0) {
+					const bool c0 = contributor < last_contributor[2 * p], p0 = !(gsr_lo(power) > 0.0f), a0 = !(gsr_lo(araw) < 1.0f / 255.0f);
+					hit0 = c0 && p0 && a0;
+					hits = __builtin_amdgcn_ballot_w64(c0) & __builtin_amdgcn_ballot_w64(p0) & __builtin_amdgcn_ballot_w64(a0);
+				}
+				if constexpr ((M & 2) != 0) {
+					const bool c1 = contributor < last_contributor[2 * p + 1], p1 = !(gsr_hi(power) > 0.0f), a1 = !(gsr_hi(araw) < 1.0f / 255.0f);
+					hit1 = c1 && p1 && a1;
+					hits |= __builtin_amdgcn_ballot_w64(c1) & __builtin_amdgcn_ballot_w64(p1) & __builtin_amdgcn_ballot_w64(a1);
+				}
 				GSR_TILE_STAT(st_pairs++;)
-				if (hits == 0ull) continue;  // wave-uniform
+				if (hits == 0ull) return;  // wave-uniform
 				GSR_TILE_STAT(st_pairs_hit++; st_lanes_hit += (unsigned)__popcll(hits);)
 				any |= hits;  // (lanes without a hit add exact zeros below)
 				// A pixel that did not hit runs the same update with alpha = 0, which is the identity on its state
 				// bit for bit (1 - 0 = 1, rcp(1) = 1, T * 1 = T, 0 * c + 1 * acc = acc): no per-state selects
-				const v2f alpha = {hit0 ? araw.x : 0.f, hit1 ? araw.y : 0.f};
-				const v2f oma = 1.f - alpha;
-				const v2f inv1ma = {__builtin_amdgcn_rcpf(oma.x), __builtin_amdgcn_rcpf(oma.y)};  // 1 ulp; IEEE division changed no parity figure
-				const v2f Tn = T[p] * inv1ma;
+				const V_t alpha = Hf::select(hit0, hit1, araw);
+				const V_t oma = 1.f - alpha;
+				const V_t inv1ma = gsr_rcp(oma);  // 1 ulp; IEEE division changed no parity figure
+				const V_t Tn = Hf::get(T[p]) * inv1ma;
 				// accum_rec and (c - accum_rec) cancel heavily when neighbouring colours are close: reference
 				// operation order, no contraction (backward.cu:553-559)
 				// dL/dalpha = sum_c (colour_c - accum_rec_c) * dL/dpix_c (backward.cu:553-559), as an FMA chain on the three
 				// differences.  The differences cancel heavily when neighbouring colours are close, so they are formed first and
 				// exactly as the reference forms them; what follows only accumulates.
-				const v2f d0 = C0 - ac0[p], d1 = C1 - ac1[p], d2 = C2 - ac2[p];
-				v2f dL_dalpha = __builtin_elementwise_fma(d2, dp2[p], __builtin_elementwise_fma(d1, dp1[p], d0 * dp0[p]));
-				v2f dV = {0.f, 0.f};
+				const V_t d0 = Hf::get(C0) - Hf::get(ac0[p]), d1 = Hf::get(C1) - Hf::get(ac1[p]), d2 = Hf::get(C2) - Hf::get(ac2[p]);
+				V_t dL_dalpha = gsr_fma(d2, Hf::get(dp2[p]), gsr_fma(d1, Hf::get(dp1[p]), d0 * Hf::get(dp0[p])));
+				V_t dV = Hf::get(V);
 				if (AUX) {   // the depth channel: the same term and update as a colour channel
-					dV = V - acD[p];
-					dL_dalpha = __builtin_elementwise_fma(dV, dpD[p], dL_dalpha);
+					dV = Hf::get(V) - Hf::get(acD[p]);
+					dL_dalpha = gsr_fma(dV, Hf::get(dpD[p]), dL_dalpha);
 				}
 				// accum_rec' = last_alpha * last_color + (1 - last_alpha) * accum_rec (backward.cu:553; the reference applies it
 				// lazily at the NEXT hit, from the same operands), written as accum_rec + alpha * (colour - accum_rec) on the
@@ -317,38 +399,58 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 				// 4e-7 ... 1.4e-6 of the CPU oracle's double-precision sums on C2 / C3.  Two further shortcuts were measured and
 				// rejected: f = (o G) dL/dalpha instead of (o dL/dalpha) G saves nothing and moves the needle-splat stress case to
 				// 1.03e-5.)
-				const v2f n0 = __builtin_elementwise_fma(alpha, d0, ac0[p]);
-				const v2f n1 = __builtin_elementwise_fma(alpha, d1, ac1[p]);
-				const v2f n2 = __builtin_elementwise_fma(alpha, d2, ac2[p]);
-				dL_dalpha = __builtin_elementwise_fma(dL_dalpha, Tn, tfb[p] * inv1ma);
+				const V_t n0 = gsr_fma(alpha, d0, Hf::get(ac0[p]));
+				const V_t n1 = gsr_fma(alpha, d1, Hf::get(ac1[p]));
+				const V_t n2 = gsr_fma(alpha, d2, Hf::get(ac2[p]));
+				dL_dalpha = gsr_fma(dL_dalpha, Tn, Hf::get(tfb[p]) * inv1ma);
 				// zero the partials of the pixel that did not hit (dL_dalpha of such a pixel is not zero by itself)
-				const v2f dla = {hit0 ? dL_dalpha.x : 0.f, hit1 ? dL_dalpha.y : 0.f};
-				const v2f dch = alpha * Tn;             // dchannel_dcolor; 0 without a hit
-				T[p] = Tn;
-				ac0[p] = n0;
-				ac1[p] = n1;
-				ac2[p] = n2;
+				const V_t dla = Hf::select(hit0, hit1, dL_dalpha);
+				const V_t dch = alpha * Tn;             // dchannel_dcolor; 0 without a hit
+				Hf::set(T[p], Tn);
+				Hf::set(ac0[p], n0);
+				Hf::set(ac1[p], n1);
+				Hf::set(ac2[p], n2);
 				if (AUX) {
-					acD[p] = __builtin_elementwise_fma(alpha, dV, acD[p]);
-					acc[9] = __builtin_elementwise_fma(dch, dpD[p], acc[9]);   // dL/dv = alpha T dL/dD
+					Hf::set(acD[p], gsr_fma(alpha, dV, Hf::get(acD[p])));
+					Hf::set(acc[9], gsr_fma(dch, Hf::get(dpD[p]), Hf::get(acc[9])));   // dL/dv = alpha T dL/dD
 				}
-				acc[6] = __builtin_elementwise_fma(dch, dp0[p], acc[6]);
-				acc[7] = __builtin_elementwise_fma(dch, dp1[p], acc[7]);
-				acc[8] = __builtin_elementwise_fma(dch, dp2[p], acc[8]);
-				acc[5] = __builtin_elementwise_fma(G, dla, acc[5]);  // dL/dopacity
-				const v2f f = (OP * dla) * G;                         // dL/dG * G
-				const v2f fdx = f * dx, fdy = f * dy;
-				acc[0] += fdx;
-				acc[1] += fdy;
-				acc[2] = __builtin_elementwise_fma(fdx, dx, acc[2]);
-				acc[3] = __builtin_elementwise_fma(fdx, dy, acc[3]);
-				acc[4] = __builtin_elementwise_fma(fdy, dy, acc[4]);
+				Hf::set(acc[6], gsr_fma(dch, Hf::get(dp0[p]), Hf::get(acc[6])));
+				Hf::set(acc[7], gsr_fma(dch, Hf::get(dp1[p]), Hf::get(acc[7])));
+				Hf::set(acc[8], gsr_fma(dch, Hf::get(dp2[p]), Hf::get(acc[8])));
+				Hf::set(acc[5], gsr_fma(G, dla, Hf::get(acc[5])));  // dL/dopacity
+				const V_t f = (Hf::get(OP) * dla) * G;                 // dL/dG * G
+				const V_t fdx = f * dxh, fdy = f * dy;
+				Hf::set(acc[0], Hf::get(acc[0]) + fdx);
+				Hf::set(acc[1], Hf::get(acc[1]) + fdy);
+				Hf::set(acc[2], gsr_fma(fdx, dxh, Hf::get(acc[2])));
+				Hf::set(acc[3], gsr_fma(fdx, dy, Hf::get(acc[3])));
+				Hf::set(acc[4], gsr_fma(fdy, dy, Hf::get(acc[4])));
 				if constexpr (ABS) {   // a pixel without a hit has f = 0: it adds exact zeros here as above
-					const v2f tx = __builtin_elementwise_fma(CA, fdx, CBh * fdy), ty = __builtin_elementwise_fma(CC, fdy, CBh * fdx);
-					absx += __builtin_fabsf(tx.x) + __builtin_fabsf(tx.y);
-					absy += __builtin_fabsf(ty.x) + __builtin_fabsf(ty.y);
+					const V_t tx = gsr_fma(Hf::get(CA), fdx, Hf::get(CBh) * fdy), ty = gsr_fma(Hf::get(CC), fdy, Hf::get(CBh) * fdx);
+					absx += gsr_abs_sum(tx);
+					absy += gsr_abs_sum(ty);
 				}
-			}
+			};
+			auto pair_of = [&](auto pc) {
+				constexpr int p = decltype(pc)::value;
+				const uint32_t m = (bands >> (2 * p)) & 3u;   // wave-uniform: the pair's bands that can be reached and have an instance left
+				if constexpr (ONE_BAND) {
+					GSR_TILE_STAT(if (m == 1u || m == 2u) { if (((bands >> (4 + 2 * p)) & 3u) == m) st_one_mask++; else st_one_last++; })
+					// Three if-then triangles in a row, not an if-else chain: the backend structurizes every diamond, uniform or not,
+					// into guarded blocks whose state can no longer be updated in place (measured in the ISA: 131 v_mov in this loop
+					// and 27 registers spilled, against 23 and none).  The two copies of m are opaque so that the tests stay apart.
+					uint32_t m1 = m, m2 = m;
+					asm volatile("" : "+s"(m1));
+					asm volatile("" : "+s"(m2));
+					if (m == 3u) pair(pc, std::integral_constant<int, 3>());
+					if (m1 == 1u) pair(pc, std::integral_constant<int, 1>());
+					if (m2 == 2u) pair(pc, std::integral_constant<int, 2>());
+				} else {
+					if (m != 0u) pair(pc, std::integral_constant<int, 3>());
+				}
+			};
+			pair_of(std::integral_constant<int, 0>());
+			pair_of(std::integral_constant<int, 1>());
 			if (any) {  // wave-uniform
 				GSR_TILE_STAT(st_reductions++;)
 				float v[GSR_BWD_NV];
@@ -442,7 +544,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 		}
 		__builtin_amdgcn_wave_barrier();
 	}
-	GSR_TILE_CLOCK_STOP(gsr_backward_tile_clock, slot_id, lane, st_staged | (st_pairs << 20) | (st_pairs_hit << 42), st_reductions | (st_lanes_hit << 24));   // one record per dispatch entry
+	GSR_TILE_CLOCK_STOP(gsr_backward_tile_clock, slot_id, lane, st_staged | (st_pairs << 20) | (st_pairs_hit << 42), st_reductions | (st_lanes_hit << 24), st_one_mask | (st_one_last << 32));   // one record per dispatch entry
 }
 
 void gsr_launch_render_backward(const GsrFrame& f, const float* bg, const float* dL_dpix, hipEvent_t t_start, hipEvent_t t_stop,

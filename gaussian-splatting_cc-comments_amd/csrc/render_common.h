@@ -23,28 +23,30 @@
 #define GSR_TILE_CLOCK_BUFFER(sym, setter)                                                           \
 	__device__ unsigned long long* sym = nullptr;                                                    \
 	extern "C" int setter(unsigned long long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(sym), &buf, sizeof(buf)); }
-// eight words per tile: start / end on the 100 MHz constant clock, HW_ID, XCC_ID, start / end on the shader clock
-// (s_memtime: with the pair above, the clock the wave actually ran at), two words of work counters (sa, sb)
+// nine words per tile (GSR_TILE_CLOCK_WORDS): start / end on the 100 MHz constant clock, HW_ID, XCC_ID, start / end on the shader clock
+// (s_memtime: with the pair above, the clock the wave actually ran at), three words of work counters (sa, sb, sc)
 #define GSR_TILE_CLOCK_START() const unsigned long long gsr_tc0 = __builtin_amdgcn_s_memrealtime(), gsr_tcc0 = __builtin_amdgcn_s_memtime()
-#define GSR_TILE_CLOCK_STOP(sym, tile, lane, sa, sb)                                                 \
+#define GSR_TILE_CLOCK_WORDS 9
+#define GSR_TILE_CLOCK_STOP(sym, tile, lane, sa, sb, sc)                                             \
 	do {                                                                                             \
 		unsigned long long* gsr_tc = sym;                                                            \
 		if (gsr_tc && (lane) == 0) {                                                                 \
-			gsr_tc[8 * (size_t)(tile)] = gsr_tc0;                                                    \
-			gsr_tc[8 * (size_t)(tile) + 1] = __builtin_amdgcn_s_memrealtime();                       \
-			gsr_tc[8 * (size_t)(tile) + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  /* HW_REG_HW_ID */  \
-			gsr_tc[8 * (size_t)(tile) + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20); /* HW_REG_XCC_ID */ \
-			gsr_tc[8 * (size_t)(tile) + 4] = gsr_tcc0;                                               \
-			gsr_tc[8 * (size_t)(tile) + 5] = __builtin_amdgcn_s_memtime();                           \
-			gsr_tc[8 * (size_t)(tile) + 6] = (sa);                                                   \
-			gsr_tc[8 * (size_t)(tile) + 7] = (sb);                                                   \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile)] = gsr_tc0;                                                    \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 1] = __builtin_amdgcn_s_memrealtime();                       \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  /* HW_REG_HW_ID */  \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 3] = __builtin_amdgcn_s_getreg((31 << 11) | 20); /* HW_REG_XCC_ID */ \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 4] = gsr_tcc0;                                               \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 5] = __builtin_amdgcn_s_memtime();                           \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 6] = (sa);                                                   \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 7] = (sb);                                                   \
+			gsr_tc[GSR_TILE_CLOCK_WORDS * (size_t)(tile) + 8] = (sc);                                                   \
 		}                                                                                            \
 	} while (0)
 #define GSR_TILE_STAT(x) x
 #else
 #define GSR_TILE_CLOCK_BUFFER(sym, setter)
 #define GSR_TILE_CLOCK_START()
-#define GSR_TILE_CLOCK_STOP(sym, tile, lane, sa, sb)
+#define GSR_TILE_CLOCK_STOP(sym, tile, lane, sa, sb, sc)
 #define GSR_TILE_STAT(x)
 #endif
 

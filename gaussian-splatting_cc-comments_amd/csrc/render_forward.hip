@@ -205,7 +205,7 @@ gsr_render_forward_wave_kernel(
 	// one record per dispatch entry; work counters: instances staged after the band cull (20 bits), bands evaluated (22), bands in which
 	// at least one pixel blended the instance (22)
 	GSR_TILE_CLOCK_STOP(gsr_forward_tile_clock, slot_id, lane, (unsigned long long)entry,
-	                    (st_staged & 0xFFFFFull) | ((st_bands & 0x3FFFFFull) << 20) | ((st_hits & 0x3FFFFFull) << 42));
+	                    (st_staged & 0xFFFFFull) | ((st_bands & 0x3FFFFFull) << 20) | ((st_hits & 0x3FFFFFull) << 42), 0ull);
 }
 
 void gsr_launch_render_forward(const GsrFrame& f, const float* bg, float* out_color, bool ordered, const GsrAuxBlend* aux)

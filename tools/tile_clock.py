@@ -79,6 +79,10 @@ def analyse(name, rec, waves_per_simd, out, forward=False):
         print(f"   work: {staged} instances staged after the band cull, {pairs} pixel pairs evaluated ({pairs / max(staged, 1):.2f} per staged instance), "
               f"{pairs_hit} of them with a hit ({pairs_hit / max(pairs, 1):.2f}), {lanes / max(pairs_hit, 1):.1f} of 64 lanes hit per such pair, "
               f"{red} wave reductions ({red / max(staged, 1):.2f} per staged instance)", file=out)
+        if rec.shape[1] >= 9:   # pairs evaluated on one band only (render_backward.hip, the pair modes)
+            one_mask, one_last = int((rec[:, 8] & 0xFFFFFFFF).sum()), int((rec[:, 8] >> 32).sum())
+            print(f"   one-band pairs: {one_mask + one_last} of the {pairs} evaluated ({(one_mask + one_last) / max(pairs, 1):.3f}): {one_mask} by the band mask "
+                  f"({one_mask / max(pairs, 1):.3f}), {one_last} more by a band's largest n_contrib ({one_last / max(pairs, 1):.3f})", file=out)
     print(f"   wave duration: mean {dur.mean():.1f}  median {np.median(dur):.1f}  p90 {np.percentile(dur, 90):.1f}  max {dur.max():.1f} us;"
           f"  waves per SIMD: min {count.min()} mean {count.mean():.2f} max {count.max()}", file=out)
     print(f"   sum of wave durations {dur.sum() / 1e3:.2f} ms = {dur.sum() / span:.0f} resident waves on average "
@@ -141,7 +145,7 @@ def main():
     # one record per DISPATCH ENTRY (a heavy tile is several: four band waves in the forward, one wave per depth segment in the
     # backward): room for the whole lists; unused entries keep t1 = 0 and are dropped by analyse()
     nrec = ntiles + 3 * min(2048, ntiles // 4) + min(4096, ntiles // 2) + 1
-    bufs = {k: torch.zeros(nrec, 8, dtype=torch.int64, device=dev) for k in ("forward", "backward")}
+    bufs = {k: torch.zeros(nrec, 9, dtype=torch.int64, device=dev) for k in ("forward", "backward")}   # GSR_TILE_CLOCK_WORDS
 
     captured = {}
     orig = _C.rasterize_gaussians
