@@ -170,11 +170,16 @@ def unpack_state(cap, P, W, H, tile_sort=False):
     return o
 
 
-def trim_kept(rshape, gauss, tile, gx):
+def trim_kept(rshape, gauss, tile, gx, gy=None):
     """numpy restatement of the binning's reading of the trim words (csrc/gsr_rect_trim.h: gsr_rect_unpack, gsr_trim_col_shift,
     gsr_trim_row_shift, gsr_trim_of, gsr_trim_columns): is instance (Gaussian gauss[i], tile tile[i]) -- a tile of that Gaussian's
-    rectangle -- kept in the list?"""
+    rectangle -- kept in the list?  gy: the grid's rows, for callers whose image may exceed 256 tiles a side."""
     P = rshape.shape[0]
+    if gx > 256 or (gy is not None and gy > 256):
+        # beyond 256 tiles a side the column-pair binning does not apply (csrc/tilebin.hip gsr_tilebin_applies): the packed word, whose
+        # fields are 8 bits wide, describes no rectangle there, and nothing is trimmed -- every instance is kept
+        assert not rshape[:, 1].any(), "a trim word is set on an image the column-pair binning does not take"
+        return np.ones(gauss.shape[0], bool)
     packed, trim = rshape[:, 0].astype(np.int64), rshape[:, 1].astype(np.int64)
     x0, y0, w, h = packed & 255, (packed >> 8) & 255, ((packed >> 16) & 255) + 1, (packed >> 24) + 1
     cs, rs = np.zeros(P, np.int64), np.zeros(P, np.int64)   # log2 of the columns per nibble / rows per unit
@@ -210,7 +215,7 @@ def trimmed_expectation(o, rshape, W, H):
     rng = o["ranges"].astype(np.int64)
     lens = rng[:, 1] - rng[:, 0]
     tile_of = np.repeat(np.arange(T, dtype=np.int64), lens)   # (the oracle's ranges partition [0, R) in tile order)
-    kept = trim_kept(rshape, o["point_list"], tile_of, gx)
+    kept = trim_kept(rshape, o["point_list"], tile_of, gx, gy)
     kcum = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
     new_len = kcum[rng[:, 1]] - kcum[rng[:, 0]]
     new_start = kcum[rng[:, 0]]
