@@ -21,6 +21,7 @@
 #include "../../include/gsr_loss_ext.h"
 #include "../../include/gsr_bilagrid.h"
 #include "../../include/gsr_mcmc.h"
+#include "../../include/gsr_densify.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1670,6 +1671,70 @@ extern "C" int gsr_mcmc_regularizer(int P, const float* opacity, const float* sc
 	if (!opacity || !scaling || !val || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity, scaling, val or scratch is NULL", who);
 	gsr_launch_mcmc_regularizer(P, opacity, scaling, w_o, w_s, val, dL_dopacity, dL_dscaling, scratch, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "mcmc_reg");
+}
+
+// ---- densification: clone, split and prune as one compaction (include/gsr_densify.h) ----
+extern "C" size_t gsr_densify_scratch_bytes(int P)
+{
+	if (P < 1) return 0;
+	return gsr_densify_scratch_size(P);
+}
+
+extern "C" int gsr_densify_plan(int P, const uint8_t* action, void* scratch, int32_t* totals, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_densify_plan";
+	if (P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, P);
+	if (!action || !scratch || !totals) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: action, scratch or totals is NULL", who);
+	if (gsr_densify_plan_blocks(P) > GSR_MCMC_MAX_BLOCKS) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P needs more than 2^24 - 1 workgroups (P %d)", who, P);
+	gsr_launch_densify_plan(P, action, scratch, totals, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "densify_plan");
+}
+
+extern "C" int gsr_densify_apply(const gsr_densify_args* args)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_densify_apply";
+	if (!args) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: NULL args", who);
+	const gsr_densify_args& a = *args;
+	if (a.P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, a.P);
+	if (a.K < 0 || a.C < 0 || a.S < 0 || a.C > a.K || (long long)a.K + a.S > a.P)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K %d, C %d, S %d are no counts over %d rows (0 <= C <= K, 0 <= S, K + S <= P)", who, a.K, a.C, a.S, a.P);
+	if (a.ngroups < 1 || a.ngroups > GSR_DENSIFY_MAX_GROUPS) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 1..%d groups (got %d)", who, GSR_DENSIFY_MAX_GROUPS, a.ngroups);
+	if (!a.groups) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: groups is NULL", who);
+	const long long Pout = (long long)a.K + a.C + (long long)GSR_DENSIFY_SPLIT_N * a.S;
+	for (int k = 0; k < a.ngroups; k++) {
+		const gsr_densify_group& g = a.groups[k];
+		if (g.row < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: negative row", who, k);
+		if ((g.exp_avg != nullptr) != (g.exp_avg_sq != nullptr))
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: exp_avg and exp_avg_sq go together", who, k);
+		if (!gsr_mcmc_fits(a.P, g.row) || !gsr_mcmc_fits(Pout, g.row))
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d exceeds 32-bit indexing (P %d, P' %lld, row %d)", who, k, a.P, Pout, g.row);
+		if (gsr_densify_copy_blocks(Pout * g.row) > GSR_MCMC_MAX_BLOCKS)
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d needs more than 2^24 - 1 workgroups", who, k);
+		if (g.row == 0) continue;
+		if (!g.param) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: param is NULL", who, k);
+		if (Pout > 0 && (!g.out_param || (g.exp_avg && (!g.out_exp_avg || !g.out_exp_avg_sq))))
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: group %d: an output is NULL", who, k);
+	}
+	const int named[3] = {a.xyz_group, a.scale_group, a.rotation_group}, want[3] = {3, 3, 4};
+	const char* const label[3] = {"xyz_group", "scale_group", "rotation_group"};
+	for (int n = 0; n < 3; n++) {
+		if (named[n] == -1 && a.S == 0) continue;
+		if (named[n] < 0 || named[n] >= a.ngroups)
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %s %d names none of the %d groups%s", who, label[n], named[n], a.ngroups, a.S > 0 ? " (needed with S > 0)" : "");
+		for (int m = 0; m < n; m++)
+			if (named[m] == named[n]) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %s and %s are one group (%d)", who, label[m], label[n], named[n]);
+		if (a.groups[named[n]].row != want[n])
+			return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the row of %s must be %d (got %d)", who, label[n], want[n], a.groups[named[n]].row);
+	}
+	if (gsr_densify_plan_blocks(a.P) > GSR_MCMC_MAX_BLOCKS) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P needs more than 2^24 - 1 workgroups (P %d)", who, a.P);
+	if (!a.action || !a.scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: action or scratch is NULL", who);
+	if (a.S > 0 && !a.noise) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: noise is NULL with S > 0", who);
+	if (Pout == 0) return GSR_OK;   // nothing to write
+	if (!a.src_of) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: src_of is NULL", who);
+	gsr_launch_densify_apply(a, (hipStream_t)a.stream);
+	return gsr_stage_done((hipStream_t)a.stream, 0, "densify_apply");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

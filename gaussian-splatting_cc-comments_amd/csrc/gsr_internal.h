@@ -394,6 +394,14 @@ int gsr_launch_mcmc_relocate(const gsr_mcmc_relocate_args& a, hipStream_t s);   
 void gsr_launch_mcmc_regularizer(int P, const float* opacity, const float* scaling, float w_o, float w_s, float* val, float* dL_dopacity,
                                  float* dL_dscaling, void* scratch, hipStream_t s);
 
+// densify.hip: clone, split and prune as one compaction (include/gsr_densify.h)
+struct gsr_densify_args;
+long long gsr_densify_plan_blocks(int P);             // workgroups of the count and the map launch
+long long gsr_densify_copy_blocks(long long words);   // workgroups of one group's copy launch
+size_t gsr_densify_scratch_size(int P);
+void gsr_launch_densify_plan(int P, const uint8_t* action, void* scratch, int32_t* totals, hipStream_t s);
+void gsr_launch_densify_apply(const gsr_densify_args& a, hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);
