@@ -22,6 +22,7 @@
 #include "../../include/gsr_bilagrid.h"
 #include "../../include/gsr_mcmc.h"
 #include "../../include/gsr_densify.h"
+#include "../../include/gsr_filter3d.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1735,6 +1736,81 @@ extern "C" int gsr_densify_apply(const gsr_densify_args* args)
 	if (!a.src_of) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: src_of is NULL", who);
 	gsr_launch_densify_apply(a, (hipStream_t)a.stream);
 	return gsr_stage_done((hipStream_t)a.stream, 0, "densify_apply");
+}
+
+// ---- Mip-Splatting's 3D smoothing filter: camera sweep, filtered activations, baked leaves, reset (include/gsr_filter3d.h) ----
+// what every entry point refuses about P; 0 where there is nothing to refuse
+static int gsr_filter3d_size(const char* who, int P)
+{
+	if (P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, P);
+	if (!gsr_mcmc_fits(P, 3)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 3 P exceeds 32-bit indexing (P %d)", who, P);
+	return GSR_OK;
+}
+
+extern "C" size_t gsr_filter3d_scratch_bytes(int P)
+{
+	if (P < 1 || !gsr_mcmc_fits(P, 3)) return 0;
+	return gsr_filter3d_scratch_size(P);
+}
+
+extern "C" int gsr_filter3d_compute(int P, int C, const float* xyz, const gsr_filter3d_camera* cameras, int per_camera, float* filter, void* scratch,
+                                    void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_filter3d_compute";
+	if (const int rc = gsr_filter3d_size(who, P)) return rc;
+	if (C < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: C must be at least 1 (got %d)", who, C);
+	if (!xyz || !cameras || !filter || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: xyz, cameras, filter or scratch is NULL", who);
+	gsr_launch_filter3d_sweep(P, C, xyz, cameras, per_camera != 0, filter, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_sweep");
+}
+
+static int gsr_filter3d_forward(const char* who, int P, const float* opacity, const float* scaling, const float* filter, float* out_o, float* out_s,
+                                int baked, void* stream)
+{
+	g_err[0] = 0;
+	if (const int rc = gsr_filter3d_size(who, P)) return rc;
+	if (!opacity || !scaling || !filter) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity, scaling or filter is NULL", who);
+	if (!out_o && !out_s) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: both outputs are NULL", who);
+	gsr_launch_filter3d_activate(P, opacity, scaling, filter, out_o, out_s, baked, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_activate");
+}
+
+extern "C" int gsr_filter3d_activate(int P, const float* opacity, const float* scaling, const float* filter, float* opacities, float* scales,
+                                     void* stream)
+{
+	return gsr_filter3d_forward("gsr_filter3d_activate", P, opacity, scaling, filter, opacities, scales, 0, stream);
+}
+
+extern "C" int gsr_filter3d_bake(int P, const float* opacity, const float* scaling, const float* filter, float* logits, float* log_scales,
+                                 void* stream)
+{
+	return gsr_filter3d_forward("gsr_filter3d_bake", P, opacity, scaling, filter, logits, log_scales, 1, stream);
+}
+
+extern "C" int gsr_filter3d_activate_backward(int P, const float* opacity, const float* scaling, const float* filter, const float* dL_dopacities,
+                                              const float* dL_dscales, float* dL_dopacity, float* dL_dscaling, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_filter3d_activate_backward";
+	if (const int rc = gsr_filter3d_size(who, P)) return rc;
+	if (!opacity || !scaling || !filter) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity, scaling or filter is NULL", who);
+	if (!dL_dopacity && !dL_dscaling) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: both outputs are NULL", who);
+	gsr_launch_filter3d_activate_backward(P, opacity, scaling, filter, dL_dopacities, dL_dscales, dL_dopacity, dL_dscaling, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_activate_bwd");
+}
+
+extern "C" int gsr_filter3d_reset_opacity(int P, float* opacity, const float* scaling, const float* filter, double max_opacity, float* exp_avg,
+                                          float* exp_avg_sq, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_filter3d_reset_opacity";
+	if (const int rc = gsr_filter3d_size(who, P)) return rc;
+	if (!opacity || !scaling || !filter) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: opacity, scaling or filter is NULL", who);
+	if ((exp_avg != nullptr) != (exp_avg_sq != nullptr)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: exp_avg and exp_avg_sq go together", who);
+	if (!(max_opacity > 0.0 && max_opacity < 1.0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: max_opacity must lie in (0, 1) (got %g)", who, max_opacity);
+	gsr_launch_filter3d_reset(P, opacity, scaling, filter, max_opacity, exp_avg, exp_avg_sq, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_reset");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

@@ -402,6 +402,18 @@ size_t gsr_densify_scratch_size(int P);
 void gsr_launch_densify_plan(int P, const uint8_t* action, void* scratch, int32_t* totals, hipStream_t s);
 void gsr_launch_densify_apply(const gsr_densify_args& a, hipStream_t s);
 
+// filter3d.hip: Mip-Splatting's 3D smoothing filter (include/gsr_filter3d.h)
+struct gsr_filter3d_camera;
+size_t gsr_filter3d_scratch_size(int P);
+void gsr_launch_filter3d_sweep(int P, int C, const float* xyz, const gsr_filter3d_camera* cameras, int per_camera, float* filter, void* scratch,
+                               hipStream_t s);
+void gsr_launch_filter3d_activate(int P, const float* opacity, const float* scaling, const float* filter, float* out_o, float* out_s, int baked,
+                                  hipStream_t s);   // baked: logit(opacities) and log(scales)
+void gsr_launch_filter3d_activate_backward(int P, const float* opacity, const float* scaling, const float* filter, const float* g_opacities,
+                                           const float* g_scales, float* d_opacity, float* d_scaling, hipStream_t s);
+void gsr_launch_filter3d_reset(int P, float* opacity, const float* scaling, const float* filter, double max_opacity, float* exp_avg, float* exp_avg_sq,
+                               hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);

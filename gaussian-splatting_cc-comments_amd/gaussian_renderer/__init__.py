@@ -18,6 +18,7 @@ Extension (not in the reference): `pipe.fused_activations = True` renders straig
 leaves (`pc._xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`) with the activations and
 their backward done inside the per-Gaussian kernels (fused_params.py) -- same result dict.
 `pipe.antialiasing = True` (where upstream's PipelineParams keeps it) renders with the screen-space filter (GaussianRasterizer).
+`filter_3d=` renders with Mip-Splatting's 3D smoothing filter folded into the opacities and scales (fused_filter3d).
 """
 import math
 
@@ -84,7 +85,7 @@ def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
            absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False, camera_model=None,
-           camera_model_grads=None):
+           camera_model_grads=None, filter_3d=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -117,7 +118,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     camera_model_grads (extension): True, or the float32 (4,) tensor (fx, fy, cx, cy) that is the autograd handle of the model's
     intrinsics -- the camera's world_view_transform and camera_center (and the tensor) take part in autograd behind the camera
     model (see GaussianRasterizer): pose refinement and self-calibration on calibrated and fisheye cameras; None =
-    getattr(pipe, "camera_model_grads", False); on both paths."""
+    getattr(pipe, "camera_model_grads", False); on both paths.
+    filter_3d (extension): the float32 (P, 1) tensor of fused_filter3d.compute_filter_3d() -- Mip-Splatting's 3D smoothing filter: the
+    rasterizer receives fused_filter3d.filtered_activations(pc._opacity, pc._scaling, filter_3d) as its opacities and scales, and the
+    gradients reach the two leaves through that function's backward.  Always the GaussianRasterizer path, under
+    pipe.fused_activations too: the two per-Gaussian leaf kernels do not know the filter, and teaching them means new instantiations
+    across every variant of both (a follow-up).  Not with pipe.compute_cov3D_python (NotImplementedError): the covariance of
+    pc.get_covariance() carries no filter."""
     from diff_gaussian_rasterization import _C
     _C.normals_flag(normals)   # a switch: anything but a bool is refused
     if camera_model is None:
@@ -131,6 +138,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     camera_model_grads = _C.camera_model_grads_arg(camera_model_grads, camera_model)   # refused before anything runs too
     if antialiasing is None:
         antialiasing = getattr(pipe, "antialiasing", False)
+    if filter_3d is not None:   # refused before anything runs, and before the kernel library is loaded
+        import fused_filter3d
+        if bool(pipe.compute_cov3D_python):
+            raise NotImplementedError("filter_3d with pipe.compute_cov3D_python: pc.get_covariance() carries no 3D filter")
+        fused_filter3d._check(opacity=pc._opacity, scaling=pc._scaling, filter_3d=filter_3d)
+        fused_filter3d._check_device(pc._opacity, pc._scaling, filter_3d)
     xyz = pc.get_xyz
     # carrier of the screen-space gradient: zeros, a non-leaf that keeps its grad
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
@@ -147,7 +160,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         extras["absgrad"] = absgrad
     python_cov = bool(pipe.compute_cov3D_python)
     python_sh = bool(pipe.convert_SHs_python)
-    leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh
+    leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh and filter_3d is None
     user_channels = None
     if normals:   # three more feature channels behind the caller's own
         n = _gaussian_normals(viewpoint_camera, pc, leaf, camera_grads is True or camera_model_grads is not False)
@@ -182,6 +195,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         inputs["cov3D_precomp"] = pc.get_covariance(scaling_modifier)
     else:
         inputs["scales"], inputs["rotations"] = pc.get_scaling, pc.get_rotation
+    if filter_3d is not None:
+        inputs["opacities"], inputs["scales"] = fused_filter3d.filtered_activations(pc._opacity, pc._scaling, filter_3d)
     if override_color is not None:
         inputs["colors_precomp"] = override_color
     elif python_sh:
