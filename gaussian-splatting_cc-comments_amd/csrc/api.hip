@@ -23,6 +23,7 @@
 #include "../../include/gsr_mcmc.h"
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_filter3d.h"
+#include "../../include/gsr_knn.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1824,6 +1825,68 @@ extern "C" int gsr_knn_mean_dist2(int P, const float* points, float* mean_dist2,
 	if (!aligned16(scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "gsr_knn_mean_dist2: scratch must be 16-byte aligned");
 	gsr_launch_knn(P, points, mean_dist2, scratch, (hipStream_t)stream);
 	return gsr_check_hip(hipGetLastError(), "knn kernels");
+}
+
+// ---- the neighbour graph (include/gsr_knn.h, knn_graph.hip) -----------------------------------------------
+extern "C" size_t gsr_knn_search_scratch_bytes(int P, int Q) { return gsr_knn_search_scratch_size(P, Q); }
+
+extern "C" int gsr_knn_search(int P, const float* points, int Q, const float* queries, int K, float* dist2, int* idx, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_knn_search";
+	if (P < 0 || Q < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (P %d, Q %d)", who, P, Q);
+	if (K < 1 || K > GSR_KNN_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must lie in 1..%d (got %d)", who, GSR_KNN_MAX_K, K);
+	if (!queries && Q != P) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the self-set form (queries NULL) needs Q == P (got %d, %d)", who, Q, P);
+	if (P == 0 || Q == 0) return GSR_OK;
+	if ((int64_t)Q * K > INT32_MAX) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: Q*K must stay below 2^31", who);
+	if (!points || !dist2 || !idx || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	gsr_launch_knn_search(P, points, Q, queries, K, dist2, idx, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "knn_search");
+}
+
+extern "C" size_t gsr_knn_graph_scratch_bytes(int E, int P) { return gsr_knn_graph_scratch_size(E, P); }
+
+extern "C" int gsr_knn_graph_build(int E, const int* idx, int P, int* offsets, int* edges, int* num_valid, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_knn_graph_build";
+	if (E < 0 || P < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (E %d, P %d)", who, E, P);
+	if (P == INT32_MAX) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P + 1 offsets must stay below 2^31", who);
+	if (E == 0 || P == 0) {   // no edge has a target
+		if (!offsets) return GSR_OK;
+		gsr_launch_knn_graph_build(0, nullptr, P, offsets, nullptr, num_valid, nullptr, (hipStream_t)stream);
+		return gsr_stage_done((hipStream_t)stream, 0, "knn_graph_build");
+	}
+	if (!idx || !offsets || !edges || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	gsr_launch_knn_graph_build(E, idx, P, offsets, edges, num_valid, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "knn_graph_build");
+}
+
+extern "C" int gsr_knn_gather(int Q, int K, int C, const float* x, const int* idx, float* out, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_knn_gather";
+	if (Q < 0 || K < 0 || C < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (Q %d, K %d, C %d)", who, Q, K, C);
+	const int64_t E = (int64_t)Q * K;
+	if (E > INT32_MAX || E * C >= ((int64_t)1 << 39)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: Q*K must stay below 2^31 and Q*K*C below 2^39", who);
+	if (E == 0 || C == 0) return GSR_OK;
+	if (!x || !idx || !out) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	gsr_launch_knn_gather(E, C, x, idx, out, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "knn_gather");
+}
+
+extern "C" int gsr_knn_gather_backward(int P, int C, const int* offsets, const int* edges, const float* grad_out, float* grad_x, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_knn_gather_backward";
+	if (P < 0 || C < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (P %d, C %d)", who, P, C);
+	if ((int64_t)P * C >= ((int64_t)1 << 39)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P*C must stay below 2^39", who);
+	if (P == 0 || C == 0) return GSR_OK;
+	if (!offsets || !edges || !grad_out || !grad_x) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	gsr_launch_knn_gather_backward(P, C, offsets, edges, grad_out, grad_x, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "knn_gather_bwd");
 }
 
 extern "C" int gsr_adam_step(int ngroups, const gsr_adam_group* groups, double beta1, double beta2, double eps,

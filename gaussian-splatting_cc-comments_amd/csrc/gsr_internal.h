@@ -432,3 +432,10 @@ int gsr_launch_adam(int ngroups, const gsr_adam_group* groups, double beta1, dou
 // knn.hip
 size_t gsr_knn_scratch_size(int P);
 void gsr_launch_knn(int P, const float* points, float* mean_dist2, void* scratch, hipStream_t s);
+// knn_graph.hip
+size_t gsr_knn_search_scratch_size(int P, int Q);
+void gsr_launch_knn_search(int P, const float* points, int Q, const float* queries, int K, float* dist2, int* idx, void* scratch, hipStream_t s);
+size_t gsr_knn_graph_scratch_size(int E, int P);
+void gsr_launch_knn_graph_build(int E, const int* idx, int P, int* offsets, int* edges, int* num_valid, void* scratch, hipStream_t s);
+void gsr_launch_knn_gather(int64_t E, int C, const float* x, const int* idx, float* out, hipStream_t s);
+void gsr_launch_knn_gather_backward(int P, int C, const int* offsets, const int* edges, const float* grad_out, float* grad_x, hipStream_t s);

@@ -18,27 +18,7 @@
 //     (uniform address: one s_load serves 64 lanes), so the scan is pure VALU work with no LDS and no
 //     barrier;
 //   * the wave's radius shrinks as the scan proceeds (own box first), pruning most boxes.
-#include <float.h>
-
-#include "gsr_internal.h"
-
-#define GSR_KNN_BOX 256
-#define GSR_KNN_SUPER 16  // boxes per super box
-
-struct GsrKnnBox { float mnx, mny, mnz, mxx, mxy, mxz; };
-
-__device__ __forceinline__ float gsr_wave_min(float v)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-	return v;
-}
-__device__ __forceinline__ float gsr_wave_max(float v)
-{
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-	return v;
-}
+#include "gsr_knn_common.h"
 
 // ---- bounds of the cloud (simple_knn.cu:182-190: both reductions start from {0,0,0}) ------------------
 __global__ void __launch_bounds__(256) gsr_knn_bounds_partial_kernel(int P, const float* __restrict__ pts, GsrKnnBox* __restrict__ partial)
@@ -144,24 +124,6 @@ __global__ void __launch_bounds__(256) gsr_knn_super_kernel(int nb, int ns, cons
 }
 
 // ---- the search ---------------------------------------------------------------------------------------------
-// squared distance from p to the box (0 inside), simple_knn.cu:116-126
-__device__ __forceinline__ float gsr_point_box_dist2(const GsrKnnBox& b, float x, float y, float z)
-{
-	float dx = 0.f, dy = 0.f, dz = 0.f;
-	if (x < b.mnx || x > b.mxx) dx = fminf(fabsf(x - b.mnx), fabsf(x - b.mxx));
-	if (y < b.mny || y > b.mxy) dy = fminf(fabsf(y - b.mny), fabsf(y - b.mxy));
-	if (z < b.mnz || z > b.mxz) dz = fminf(fabsf(z - b.mnz), fabsf(z - b.mxz));
-	return dx * dx + dy * dy + dz * dz;
-}
-// lower bound of the squared distance between any point of q and any point of b; never above the fp32
-// point-box distance of a point inside q (same expression shape, monotone rounding)
-__device__ __forceinline__ float gsr_box_box_dist2(const GsrKnnBox& b, const GsrKnnBox& q)
-{
-	const float dx = fmaxf(0.f, fmaxf(b.mnx - q.mxx, q.mnx - b.mxx));
-	const float dy = fmaxf(0.f, fmaxf(b.mny - q.mxy, q.mny - b.mxy));
-	const float dz = fmaxf(0.f, fmaxf(b.mnz - q.mxz, q.mnz - b.mxz));
-	return dx * dx + dy * dy + dz * dz;
-}
 // updateKBest<3>, simple_knn.cu:128-142, as a branch-free insertion
 __device__ __forceinline__ void gsr_knn_insert(float4 me, float4 c, float& k0, float& k1, float& k2)
 {
@@ -222,18 +184,7 @@ __global__ void __launch_bounds__(256) gsr_knn_search_kernel(int P, const float4
 // ---- host side ----------------------------------------------------------------------------------------------
 #define GSR_KNN_PARTIALS 1024
 
-struct GsrKnnScratch {
-	GsrKnnBox* bounds;
-	GsrKnnBox* partial;
-	uint32_t *codes, *codes_alt, *idx, *idx_alt;
-	float4* sorted;
-	GsrKnnBox* boxes;
-	GsrKnnBox* supers;
-	void* table;
-	size_t total;
-};
-
-static GsrKnnScratch gsr_knn_carve(void* base, int P)
+GsrKnnScratch gsr_knn_carve(void* base, int P)
 {
 	const int nb = (P + GSR_KNN_BOX - 1) / GSR_KNN_BOX, ns = (nb + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER;
 	size_t off = 0;
@@ -253,19 +204,31 @@ static GsrKnnScratch gsr_knn_carve(void* base, int P)
 
 size_t gsr_knn_scratch_size(int P) { return P > 0 ? gsr_knn_carve(nullptr, P).total : 0; }
 
+void gsr_knn_cloud_bounds(int P, const float* points, const GsrKnnScratch& k, hipStream_t s)
+{
+	const int np = min(GSR_KNN_PARTIALS, (P + 255) / 256);
+	hipLaunchKernelGGL(gsr_knn_bounds_partial_kernel, dim3(np), dim3(256), 0, s, P, points, k.partial);
+	hipLaunchKernelGGL(gsr_knn_bounds_final_kernel, dim3(1), dim3(64), 0, s, np, k.partial, k.bounds);
+}
+
+const uint32_t* gsr_knn_morton_order(int n, const float* pts, const GsrKnnBox* bounds, const GsrKnnScratch& k, hipStream_t s)
+{
+	const int nb = (n + GSR_KNN_BOX - 1) / GSR_KNN_BOX, ns = (nb + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER;
+	hipLaunchKernelGGL(gsr_knn_morton_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, pts, bounds, k.codes, k.idx);
+	int in_first = 1;
+	gsr_radix_sort_u32(k.codes, k.idx, k.codes_alt, k.idx_alt, (size_t)n, 30, k.table, &in_first, 1, 4, s);
+	const uint32_t* order = in_first ? k.idx : k.idx_alt;
+	hipLaunchKernelGGL(gsr_knn_gather_kernel, dim3(nb), dim3(GSR_KNN_BOX), 0, s, n, pts, order, k.sorted, k.boxes);
+	hipLaunchKernelGGL(gsr_knn_super_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, nb, ns, k.boxes, k.supers);
+	return in_first ? k.codes : k.codes_alt;
+}
+
 void gsr_launch_knn(int P, const float* points, float* mean_dist2, void* scratch, hipStream_t s)
 {
 	GsrKnnScratch k = gsr_knn_carve(scratch, P);
 	const int nb = (P + GSR_KNN_BOX - 1) / GSR_KNN_BOX, ns = (nb + GSR_KNN_SUPER - 1) / GSR_KNN_SUPER;
-	const int np = min(GSR_KNN_PARTIALS, (P + 255) / 256);
 	GsrProfScope p(s, "knn");
-	hipLaunchKernelGGL(gsr_knn_bounds_partial_kernel, dim3(np), dim3(256), 0, s, P, points, k.partial);
-	hipLaunchKernelGGL(gsr_knn_bounds_final_kernel, dim3(1), dim3(64), 0, s, np, k.partial, k.bounds);
-	hipLaunchKernelGGL(gsr_knn_morton_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, points, k.bounds, k.codes, k.idx);
-	int in_first = 1;
-	gsr_radix_sort_u32(k.codes, k.idx, k.codes_alt, k.idx_alt, (size_t)P, 30, k.table, &in_first, 1, 4, s);
-	const uint32_t* order = in_first ? k.idx : k.idx_alt;
-	hipLaunchKernelGGL(gsr_knn_gather_kernel, dim3(nb), dim3(GSR_KNN_BOX), 0, s, P, points, order, k.sorted, k.boxes);
-	hipLaunchKernelGGL(gsr_knn_super_kernel, dim3((ns + 255) / 256), dim3(256), 0, s, nb, ns, k.boxes, k.supers);
+	gsr_knn_cloud_bounds(P, points, k, s);
+	gsr_knn_morton_order(P, points, k.bounds, k, s);
 	hipLaunchKernelGGL(gsr_knn_search_kernel, dim3(nb), dim3(256), 0, s, P, k.sorted, k.boxes, k.supers, nb, ns, mean_dist2);
 }
