@@ -11,9 +11,12 @@
 // provably misses, per tile COLUMN of the rectangle: up to three tile rows off the top and up to three off the bottom of every
 // column (two bits each: a nibble per column, eight columns in one word), empty columns off the left and right edge.  A rectangle
 // wider than eight tiles shares a nibble among 2, 4, ... 32 neighbouring columns, one taller than 16 tiles counts the rows in units
-// of 2, 4, ... 16: coarser, never wrong.  What is kept is a superset of what can contribute (the bound is taken over the column's whole
-// strip of pixel centres, with margins far above the fp32 error of `power` and of exp), so every output -- image, radii, gradients --
-// has the same bits with and without it (GSR_DEBUG_NO_TRIM; tests/test_trim_gpu.py, tools/determinism_stress.py), and the slots of
+// of 2, 4, ... 16: coarser, never wrong.  What is kept is a superset of what can contribute IN THE KERNELS' ARITHMETIC: the bound is
+// taken over the column's whole strip of pixel centres, the conic's determinant enters by a lower bound of its fp32 value, and the
+// threshold grows with the magnitude of the terms that cancel in the kernels' fp32 `power` (both derived in gsr_rect_trim below; a
+// constant margin covers an ordinary splat and loses tiles of a needle 1000 px long whose centre lies far off the pixels it covers),
+// so every output -- image, radii, gradients -- has the same bits with and without it (GSR_DEBUG_NO_TRIM; tests/test_trim_gpu.py,
+// tests/test_trim_needles_gpu.py, tests/test_trim_needles_cpu.py, tools/trim_stress.py, tools/determinism_stress.py), and the slots of
 // the left-out instances are exactly slots the backward never marks valid.  num_rendered, tiles_touched and the gradient slots keep
 // the reference's numbering over the WHOLE rectangle; point_list and the tile ranges are the reference's with the left-out instances
 // removed (the reference's own, bit for bit, with GSR_DEBUG_NO_TRIM and on the tile-sort path).
@@ -35,6 +38,8 @@ __host__ __device__ __forceinline__ void gsr_rect_unpack(uint32_t r, uint32_t& x
 
 #define GSR_TRIM_GROUPS 8        // nibbles of a trim word: column groups of a rectangle
 #define GSR_TRIM_MAX_UNITS 3     // row units it can take off either end of a column group
+#define GSR_TRIM_K1 2.0f         // units of 2^-23 (ca cc + cb cb) by which the fp32 determinant may be off: gsr_rect_trim (1)
+#define GSR_TRIM_K2 4.0f         // units of 2^-23 (ca X^2 + 2 |cb| X Y + cc Y^2) by which the fp32 `power` may be off, in q: gsr_rect_trim (2)
 
 // log2 of the columns that share a nibble (w <= 8: 0) and of the rows per unit (h <= 16: 0): the smallest powers of two with
 // at most 8 groups / at most 16 units
@@ -78,20 +83,46 @@ __device__ __forceinline__ uint32_t gsr_rect_trim(float px, float py, float ca, 
 	if (w <= 0 || h <= 0) return 0u;
 	const uint32_t cs = gsr_trim_col_shift((uint32_t)w), rs = gsr_trim_row_shift((uint32_t)h);
 	const int groups = (int)(((uint32_t)w + (1u << cs) - 1u) >> cs);
-	// (v_sqrt_f32 / v_rcp_f32 / v_log_f32 as they are, 1 ulp: the margins below are a thousand times that; the IEEE expansions of
+	// (v_sqrt_f32 / v_rcp_f32 / v_log_f32 as they are, 1 ulp: the relative margins below are a thousand times that; the IEEE expansions of
 	// sqrtf and of the division cost the geometry kernel, which the whole binning chain waits for, 7 us at 1 M Gaussians)
-	const float det = ca * cc - cb * cb;
-	// q = ca dx^2 + 2 cb dx dy + cc dy^2 <= tau is necessary for alpha >= 1 / 255; the margin (0.1 % + 0.01) is thousands of times the
-	// error of the kernels' fp32 `power` and exp at these magnitudes (tau <= 11.1)
-	const float tau = 2.0f * __logf(255.0f * opacity) * 1.001f + 0.01f;
-	if (!(det > 0.0f) || !(ca > 0.0f) || !(cc > 0.0f) || !(tau == tau)) return 0u;   // not an ellipse this bound understands: keep everything
+	// (1) The determinant.  T = ca cc and B = cb cb cancel: for a needle 1000 : 1 at 45 degrees to a few digits.  With u = 2^-24,
+	// det0 = fl(fl(T) - fl(B)) = (fl(T) - fl(B)) (1 + d), |d| <= u, and |fl(T) - T| <= u T, |fl(B) - B| <= u B, so the exact
+	// determinant of the three floats lies within u det0 + u (T + B) <= u T (1 + u) + u (T + B) of det0; forming the bound itself
+	// (the sum, the product, the subtraction: 3 roundings, each <= u T (1 + 3 u)) adds less than another u (T + B):
+	// |det - det0| < 3 u (T + B) = 1.5 * 2^-23 (T + B).  GSR_TRIM_K1 = 2 is the next whole number; what it leaves over
+	// (2^-24 (T + B)) pays for the rounding of the fp32 sum T + B.  Every length below grows as det shrinks, so the LOWER end is used.
+	const float det0 = ca * cc - cb * cb;
+	const float dspan = (GSR_TRIM_K1 * 0x1p-23f) * (ca * cc + cb * cb);
+	const float det = det0 - dspan;
+	// (2) The threshold.  q = ca dx^2 + 2 cb dx dy + cc dy^2 <= 2 ln(255 opacity) is necessary for alpha >= 1 / 255 in exact
+	// arithmetic.  The blend kernels decide with `power` = fl(fl(-0.5 fl(fl(fl(ca dx) dx) + fl(fl(cc dy) dy))) - fl(fl(cb dx) dy))
+	// (gsr_pair_power, render_common.h; dx, dy the kernels' own rounded mean - pixel): four roundings on the way of the squares,
+	// three on the way of the mixed term, so |-2 power - q| <= ((1 + u)^4 - 1) M = 2 * 2^-23 M (1 + 2 u) with
+	// M = ca dx^2 + 2 |cb dx dy| + cc dy^2, the magnitude of what cancels.  M grows with |dx| and |dy|; it is taken at X, Y, the
+	// largest |dx| and |dy| of the rectangle's pixel columns and rows (the same subtractions the kernels round).  GSR_TRIM_K2 = 4,
+	// twice the bound: the other half pays for the seven roundings of M's own evaluation here and keeps the second-order terms out of the
+	// argument.  For a splat of a few pixels this adds 1e-5 to tau; for a needle whose centre lies thousands of pixels off, M reaches
+	// 1e6 and the term 0.5.  The constant part (0.1 % + 0.01 in q, 0.005 in `power`) remains for what has an absolute or a relative
+	// error of a few u: v_log here, the kernels' exp and product (1e-6 of alpha), and the roundings of the lengths below -- of
+	// tau cc - det lo^2 above all, whose error 6 u tau cc is 3e-4 of the 0.001 tau cc the margin adds to it.
+	const float X = fmaxf(fabsf((float)(x0 * GSR_TILE_X) - px), fabsf((float)((x0 + w) * GSR_TILE_X - 1) - px));
+	const float Y = fmaxf(fabsf((float)(y0 * GSR_TILE_Y) - py), fabsf((float)((y0 + h) * GSR_TILE_Y - 1) - py));
+	const float tau0 = 2.0f * __logf(255.0f * opacity) * 1.001f + 0.01f;
+	const float tau = tau0 + (GSR_TRIM_K2 * 0x1p-23f) * (ca * X * X + 2.0f * fabsf(cb) * X * Y + cc * Y * Y);
+	if (!(det > 0.0f) || !(ca > 0.0f) || !(cc > 0.0f) || !(tau == tau)) return 0u;   // not an ellipse this bound understands (or one whose determinant is all rounding): keep everything
 	uint32_t trim = 0u;
 	uint32_t first = (uint32_t)groups, last = 0u;
-	if (tau > 0.0f) {
+	if (tau0 > 0.0f) {
 		const float inv_det = __builtin_amdgcn_rcpf(det);
 		const float ex = __builtin_amdgcn_sqrtf(tau * cc * inv_det) * 1.0001f + 0.01f;      // half width of the ellipse
 		const float eyy = __builtin_amdgcn_sqrtf(tau * ca * inv_det) * 1.0001f + 0.01f;     // half height
-		const float xs = -cb * __builtin_amdgcn_sqrtf(tau * inv_det * __builtin_amdgcn_rcpf(ca));                // dx of the ellipse's bottom point (largest dy); its top point: -xs
+		// dx of the ellipse's bottom point (largest dy), -cb sqrt(tau / (det ca)); its top point: the negative.  Only known as well as
+		// det: it lies in [bx0, bx1], from det's upper end (det0 + dspan; sqrt(r) >= r for r <= 1 saves the second square root) to its
+		// lower one.  (With the lower end in place of det the boundary below peaks at -cb sqrt(tau cc / (det (det + cb^2))) instead:
+		// farther out by less than 1 + 8 u (ca cc + cb^2) / (det + cb^2) <= 1 + 2e-6, inside the 1e-4.)
+		const float xs = fabsf(cb) * __builtin_amdgcn_sqrtf(tau * inv_det * __builtin_amdgcn_rcpf(ca));
+		const float xs1 = xs * 1.0001f + 0.01f, xs0 = xs * (det * __builtin_amdgcn_rcpf(det0 + dspan)) * 0.9999f - 0.01f;
+		const float bx0 = cb <= 0.0f ? xs0 : -xs1, bx1 = cb <= 0.0f ? xs1 : -xs0;
 		const float inv_cc = __builtin_amdgcn_rcpf(cc);
 #pragma unroll
 		for (int c = 0; c < GSR_TRIM_GROUPS; c++) {
@@ -102,12 +133,13 @@ __device__ __forceinline__ uint32_t gsr_rect_trim(float px, float py, float ca, 
 			uint32_t t = GSR_TRIM_MAX_UNITS, b = GSR_TRIM_MAX_UNITS;   // the ellipse misses the strip: as much off as the word can say
 			if (!(lo > ex) && !(hi < -ex)) {   // (written so that a NaN anywhere keeps the column whole: every comparison below is false then)
 				lo = fmaxf(lo, -ex); hi = fminf(hi, ex);
-				// largest dy over the strip: the ellipse's bottom point if its dx lies inside, else at the nearer end (the boundary is concave)
+				// largest dy over the strip: the ellipse's bottom point if its dx can lie inside, else at the nearer end (the boundary is
+				// concave, and so is the one drawn with det's lower end, which lies outside it everywhere)
 				const float rlo = __builtin_amdgcn_sqrtf(fmaxf(0.0f, tau * cc - det * lo * lo)), rhi = __builtin_amdgcn_sqrtf(fmaxf(0.0f, tau * cc - det * hi * hi));
 				float ymax = fmaxf((-cb * lo + rlo) * inv_cc, (-cb * hi + rhi) * inv_cc);
 				float ymin = fminf((-cb * lo - rlo) * inv_cc, (-cb * hi - rhi) * inv_cc);
-				if (lo <= xs && xs <= hi) ymax = eyy;
-				if (lo <= -xs && -xs <= hi) ymin = -eyy;
+				if (lo <= bx1 && bx0 <= hi) ymax = eyy;
+				if (lo <= -bx0 && -bx1 <= hi) ymin = -eyy;
 				ymax = ymax * 1.0001f + 0.01f;
 				ymin = ymin * 1.0001f - 0.01f;
 				// tile rows that hold a pixel centre in [py + ymin, py + ymax] -- or fewer: rows of the bounds themselves

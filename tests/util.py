@@ -40,9 +40,10 @@ def hip_settings(scene, cam, D, dev, scale_modifier=1.0, debug=False, prefiltere
 
 
 def hip_forward_backward(scene, cam, D, dpix=None, dev="cuda:0", colors_precomp=None, cov3D_precomp=None,
-                         scale_modifier=1.0, use_sh=True, use_scale_rot=True, debug=False):
+                         scale_modifier=1.0, use_sh=True, use_scale_rot=True, debug=False, antialiasing=False):
     """Runs GaussianRasterizer fwd (+bwd when dpix is given) and returns numpy outputs, including
-    the intermediates read out of the opaque state buffers through the published layouts."""
+    the intermediates read out of the opaque state buffers through the published layouts.
+    antialiasing: the screen-space filter with opacity compensation (the records then hold opacity * rho)."""
     from diff_gaussian_rasterization import GaussianRasterizer, _C, _RasterizeGaussians
     dev = torch.device(dev)
     leaf = lambda t: t.to(dev).clone().requires_grad_(True)
@@ -64,13 +65,13 @@ def hip_forward_backward(scene, cam, D, dpix=None, dev="cuda:0", colors_precomp=
     captured = {}
     orig = _C.rasterize_gaussians
 
-    def spy(*a):
-        r = orig(*a)
+    def spy(*a, **k):
+        r = orig(*a, **k)
         captured["R"], captured["geom"], captured["binning"], captured["img"] = r[0], r[3], r[4], r[5]
         return r
     _C.rasterize_gaussians = spy
     try:
-        color, radii = GaussianRasterizer(settings)(means3D=means, means2D=means2D, opacities=opac, **kw)
+        color, radii = GaussianRasterizer(settings, antialiasing=antialiasing)(means3D=means, means2D=means2D, opacities=opac, **kw)
     finally:
         _C.rasterize_gaussians = orig
     out = dict(color=color.detach().cpu().numpy(), radii=radii.cpu().numpy(), num_rendered=captured["R"])
