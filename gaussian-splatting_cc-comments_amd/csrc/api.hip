@@ -24,6 +24,7 @@
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_filter3d.h"
 #include "../../include/gsr_knn.h"
+#include "../../include/gsr_rigidity.h"
 
 #define GSR_MAX_DEVICES 64
 // Beside the depth sort the SH colour kernel is held to two workgroups per CU (unused dynamic LDS on top of its staging area): it has
@@ -1887,6 +1888,34 @@ extern "C" int gsr_knn_gather_backward(int P, int C, const int* offsets, const i
 	if (!offsets || !edges || !grad_out || !grad_x) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
 	gsr_launch_knn_gather_backward(P, C, offsets, edges, grad_out, grad_x, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "knn_gather_bwd");
+}
+
+// ---- the neighbour-rigidity losses (include/gsr_rigidity.h, rigidity.hip) ------------------------------------
+static bool gsr_rigidity_fits(int P, int K) { return P >= 0 && K >= 0 && K <= GSR_RIGIDITY_MAX_K && (int64_t)P * K <= INT32_MAX; }
+
+extern "C" size_t gsr_rigidity_scratch_bytes(int P, int K) { return gsr_rigidity_fits(P, K) ? gsr_rigidity_scratch_size(P, K) : 0; }
+
+extern "C" int gsr_rigidity_loss(int P, int K, const float* xyz, const float* rotation, const int* idx, const float* prev_offset, const float* prev_dist,
+                                 const float* weight, const float* prev_inv_rot, const int* offsets, const int* edges, float w_rigid, float w_rot,
+                                 float w_iso, float* values, float* grad_xyz, float* grad_rot, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_rigidity_loss";
+	if (P < 0 || K < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (P %d, K %d)", who, P, K);
+	if (K > GSR_RIGIDITY_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must lie in 1..%d (got %d)", who, GSR_RIGIDITY_MAX_K, K);
+	if (!values) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: values is NULL", who);
+	if ((int64_t)P * K > INT32_MAX) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P*K must stay below 2^31", who);
+	if (P == 0 || K == 0) {   // no edge: zeros
+		gsr_launch_rigidity_zero(P, values, grad_xyz, grad_rot, (hipStream_t)stream);
+		return gsr_stage_done((hipStream_t)stream, 0, "rigidity_fold");
+	}
+	if (!xyz || !rotation || !idx || !prev_offset || !prev_dist || !weight || !prev_inv_rot || !offsets || !scratch)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if ((grad_xyz || grad_rot) && !edges) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: edges is NULL and a gradient is asked for", who);
+	if (!aligned16(scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	gsr_launch_rigidity_loss(P, K, xyz, rotation, idx, prev_offset, prev_dist, weight, prev_inv_rot, offsets, edges, w_rigid, w_rot, w_iso, values, grad_xyz,
+	                         grad_rot, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "rigidity_fold");
 }
 
 extern "C" int gsr_adam_step(int ngroups, const gsr_adam_group* groups, double beta1, double beta2, double eps,

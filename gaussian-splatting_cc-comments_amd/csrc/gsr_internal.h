@@ -439,3 +439,9 @@ size_t gsr_knn_graph_scratch_size(int E, int P);
 void gsr_launch_knn_graph_build(int E, const int* idx, int P, int* offsets, int* edges, int* num_valid, void* scratch, hipStream_t s);
 void gsr_launch_knn_gather(int64_t E, int C, const float* x, const int* idx, float* out, hipStream_t s);
 void gsr_launch_knn_gather_backward(int P, int C, const int* offsets, const int* edges, const float* grad_out, float* grad_x, hipStream_t s);
+// rigidity.hip
+size_t gsr_rigidity_scratch_size(int P, int K);
+void gsr_launch_rigidity_zero(int P, float* values, float* grad_xyz, float* grad_rot, hipStream_t s);
+void gsr_launch_rigidity_loss(int P, int K, const float* xyz, const float* rotation, const int* idx, const float* prev_offset, const float* prev_dist,
+                              const float* weight, const float* prev_inv_rot, const int* offsets, const int* edges, float w_rigid, float w_rot, float w_iso,
+                              float* values, float* grad_xyz, float* grad_rot, void* scratch, hipStream_t s);
