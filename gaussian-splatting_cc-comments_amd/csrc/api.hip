@@ -254,6 +254,9 @@ extern "C" int gsr_binning_layout_of(int P, int64_t R, int W, int H, gsr_binning
 	o->point_list = off;     off = gsr_align_up(off + n * 4);
 	o->point_list_alt = off; off = gsr_align_up(off + n * 4);
 	o->tile_keys = off;      off = gsr_align_up(off + n * 4);
+	// the forward's band masks: R bytes of tile_keys_alt behind the validity bytes (which tile_ranges / row_scatter clear in whole words:
+	// hence the rounding).  4 ceil(R / 4) + R <= 4 R from R = 2 on, and the array is never smaller than 256 bytes.
+	o->band_masks = off + gsr_align_up(n, 4);
 	o->tile_keys_alt = off;  off = gsr_align_up(off + n * 4);
 	{
 		const size_t a = gsr_radix_table_bytes(n), b = gsr_tilebin_row_table_bytes(n);   // tile sort (sort.hip) / pass 2 of tilebin.hip
@@ -508,6 +511,7 @@ GsrBinning gsr_binning_view(void* blob, int P, int64_t R, int W, int H)
 	bn.point_list_alt = (uint32_t*)(b + l.point_list_alt);
 	bn.tile_keys = (uint32_t*)(b + l.tile_keys);
 	bn.tile_keys_alt = (uint32_t*)(b + l.tile_keys_alt);
+	bn.band_masks = (uint8_t*)(b + l.band_masks);
 	bn.sort_table = (void*)(b + l.sort_table);
 	bn.checkpoints = (float4*)(b + l.checkpoints);
 	return bn;

@@ -90,8 +90,10 @@ struct GsrBinning {
 	uint32_t* point_list_alt;  // ping-pong partner
 	uint32_t* tile_keys;       // sorted tile ids (final)
 	uint32_t* tile_keys_alt;   // after the forward: [R] validity BYTES of the backward's gradient slots (zeroed by tile_ranges)
+	uint8_t* band_masks;       // [R] bytes inside tile_keys_alt, behind the validity bytes: gsr_tile_band_mask of every list position the forward
+	                           // blend staged, for the backward blend (render_forward.hip / render_backward.hip)
 	void* sort_table;          // radix histogram table for the R-sized tile sort
-	float4* checkpoints;       // [gsr_checkpoint_records(R)][256] depth checkpoints of heavy tiles (see GSR_CKPT_STRIDE)
+	float4* checkpoints;      // [gsr_checkpoint_records(R)][256] depth checkpoints of heavy tiles (see GSR_CKPT_STRIDE)
 };
 
 // Per-call pointers of the depth-and-alpha variants of the blend kernels (include/gsr.h gsr_aux_args)

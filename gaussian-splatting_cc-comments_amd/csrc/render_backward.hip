@@ -22,7 +22,7 @@
 //
 // A lane's four pixels are two packed pairs: pair p holds the tile's band 2p (rows 8p .. 8p+3) in the .x halves of its v2f
 // registers and band 2p+1 in the .y halves.  Per staged instance each pair has a wave-uniform mode, two bits that say which of its
-// bands can be reached (gsr_tile_band_mask) and still have an instance to come (the band's largest n_contrib lies behind this one):
+// bands can be reached (gsr_tile_band_mask, as the forward blend evaluated and stored it: "The band masks" below) and still have an instance to come (the band's largest n_contrib lies behind this one):
 //   0  the pair is skipped;
 //   3  the packed body: every operation a v_pk_*_f32 on both halves;
 //   1, 2  the same operations in the same order as plain fp32 instructions on the .x or the .y half alone.  The other band could
@@ -104,10 +104,27 @@ __device__ __forceinline__ float gsr_abs_sum(v2f a) { return __builtin_fabsf(a.x
 // to itself the compiler takes 130), and the two accumulators, the halved b and the terms' temporaries of ABS on top spill 10
 // registers to scratch at that limit: that instantiation takes 146 VGPRs (144 before the pair modes' staging) and runs three waves per
 // SIMD, without scratch.
-template <bool AUX, bool ABS>
-__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu((AUX && ABS) ? 3 : 4, 4))) gsr_render_backward_wave_kernel(
+//
+// The band masks (RECOMPUTE = false, the product's kernels).  reach -- gsr_tile_band_mask of the record against this tile -- is the value
+// the forward blend computed for the same list position from the same six record fields and the same tile origin, and stored as that
+// position's byte of band_masks (render_forward.hip).  The byte is loaded with the position's id, at the same index (band_masks is
+// indexed like point_list) and the same distance ahead; the record and the slot_base word of a position whose byte is 0 are not
+// gathered (it is not staged: reach = 0), and gsr_tile_band_mask is not evaluated here.  Invariants:
+//   * No byte is read that the forward did not write.  The walk ends at n = min(range length, tile_max_contrib).  tile_max_contrib is
+//     a position (+ 1) inside a batch that some forward wave of the tile staged whole, and that wave stored the bytes of that batch and
+//     of every batch before it.  For a band-split tile the maximum is taken over its four band waves and the argument holds for the wave
+//     that has it.  A depth-segment wave here reads positions [seg_a, top) with top <= n.
+//   * The load is in bounds wherever the id load beside it is: same index, one byte for four.
+//   * cull == 0 (GSR_DEBUG_NO_CULL here) does not consult the array: reach = 0xF, every record gathered.  A forward run with
+//     GSR_DEBUG_NO_CULL stored 0xF everywhere, which is what a default backward then reads.
+//   * The bytes belong to the forward state: nothing after the forward blend writes them, so a second backward over the same state,
+//     or over a state restored from a debug snapshot of the blobs, sees the same bytes.
+// RECOMPUTE = true (GSR_DEBUG_RECOMPUTE_BANDS, kernels of their own): the array is ignored, every record of the walk is gathered and
+// its mask computed from it.  Both forms stage the same instances with the same bands: the results are the same bits.
+template <bool AUX, bool ABS, bool RECOMPUTE>
+__device__ __forceinline__ void gsr_render_backward_wave(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-	const GsrSplat* __restrict__ splat, const float4* __restrict__ checkpoints, const float* __restrict__ final_C, const uint32_t* __restrict__ slot_base, const float* __restrict__ bg,
+	const uint8_t* __restrict__ band_masks, const GsrSplat* __restrict__ splat, const float4* __restrict__ checkpoints, const float* __restrict__ final_C, const uint32_t* __restrict__ slot_base, const float* __restrict__ bg,
 	const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,
 	const uint32_t* __restrict__ tile_order, const float* __restrict__ dL_dpixels, GsrGradSlot* __restrict__ slots,
 	uint8_t* __restrict__ slot_valid, int cull, GsrAuxBlend aux)
@@ -166,6 +183,7 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	}
 	const int nw = top - seg_a;
 	const uint32_t* plist = point_list + range.x;
+	const uint8_t* pmask = band_masks + range.x;
 	const size_t plane = (size_t)H * W;
 	const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
 	const float ddelx_dx = 0.5f * W, ddely_dy = 0.5f * H;
@@ -245,13 +263,21 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	// back to front: batch position q = base + lane maps to range position top - 1 - q (top = n for a whole tile, the end of the segment otherwise)
 	float4 ra = make_float4(0, 0, 0, 0), rb = ra, rc = ra;   // (rc.w: the depth value v in the AUX variant)
 	uint32_t sbase = 0u;  // first gradient slot of the staged Gaussian (dense per-Gaussian array, cache resident)
-	if (lane < nw) {
+	// the band mask of a position of the walk as the forward left it: 0 outside the walk, 0xF where the array is not consulted
+	// (RECOMPUTE keeps no masks: its tests are the positions' own, and the parent form of this loop is what it compiles to)
+	auto mask_at = [&](int q) -> uint32_t {
+		if (RECOMPUTE || q >= nw) return 0u;
+		return cull ? (uint32_t)pmask[top - 1 - q] : 0xFu;
+	};
+	uint32_t m_cur = mask_at(lane);   // of the batch whose records are in ra, rb, rc; m_next: of the batch whose ids are in id_next
+	if (RECOMPUTE ? lane < nw : m_cur != 0u) {
 		const uint32_t id = plist[top - 1 - lane];
 		const float4* p = reinterpret_cast<const float4*>(splat + id);
 		ra = p[0]; rb = p[1]; rc = p[2];
 		sbase = slot_base[id];
 	}
 	uint32_t id_next = (64 + lane < nw) ? plist[top - 1 - (64 + lane)] : 0u;
+	uint32_t m_next = mask_at(64 + lane);
 	const int out_index = lane >> 3;                  // 8-lane group c ends up holding the wave total of v[c]
 	float* const red_w = s_red[wave] + lane * 9;                       // this lane's row
 	// column lane / 8, rows (lane % 8) + 8 k.  (Two of the eight 8-lane groups share seven banks in each of these reads: 2 conflict
@@ -274,7 +300,8 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	uint32_t pend_j = 0u;   // wave-uniform: their batch indices j, eight bits each (unused bytes 0, so every lane reads inside rec)
 
 	for (int base = 0; base < nw; base += 64) {
-		const uint32_t reach = (base + lane < nw) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
+		uint32_t reach = m_cur;   // (0 beyond the walk)
+		if constexpr (RECOMPUTE) reach = (base + lane < nw) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
 		// The bands that still have an instance to come: at or beyond a band's largest n_contrib this one was blended into none of
 		// its pixels (c0 / c1 below false in all lanes).  Decided here, 64 instances per instruction, so that the walk below reads a
 		// pair's mode out of two bits: a scalar chain of compares and selects in front of each pair's branch cost the step 1.5 %.
@@ -303,12 +330,14 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 			if (AUX) rec[5][pos] = make_float4(rc.w, rc.w, 0.f, 0.f);   // depth value v
 			recb[pos] = bands | (reach << 4);   // (bits 4..7: the band mask alone, for the diagnostic counters)
 		}
-		if (base + 64 + lane < nw) {
+		if (RECOMPUTE ? base + 64 + lane < nw : m_next != 0u) {   // survivors of the forward's test only: a lane that skips the gather keeps a stale record and is not staged
 			const float4* p = reinterpret_cast<const float4*>(splat + id_next);
 			ra = p[0]; rb = p[1]; rc = p[2];
 			sbase = slot_base[id_next];
 		}
+		m_cur = m_next;
 		id_next = (base + 128 + lane < nw) ? plist[top - 1 - (base + 128 + lane)] : 0u;
+		m_next = mask_at(base + 128 + lane);
 		__builtin_amdgcn_wave_barrier();
 
 #pragma clang loop unroll(disable)
@@ -547,6 +576,23 @@ __global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_w
 	GSR_TILE_CLOCK_STOP(gsr_backward_tile_clock, slot_id, lane, st_staged | (st_pairs << 20) | (st_pairs_hit << 42), st_reductions | (st_lanes_hit << 24), st_one_mask | (st_one_last << 32));   // one record per dispatch entry
 }
 
+#define GSR_BWD_KERNEL(name, RECOMPUTE)                                                                                                        \
+	template <bool AUX, bool ABS>                                                                                                              \
+	__global__ void __launch_bounds__(64 * GSR_WAVES_PER_WG) __attribute__((amdgpu_waves_per_eu((AUX && ABS) ? 3 : 4, 4))) name(                \
+		int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,                           \
+		const uint8_t* __restrict__ band_masks, const GsrSplat* __restrict__ splat, const float4* __restrict__ checkpoints,                    \
+		const float* __restrict__ final_C, const uint32_t* __restrict__ slot_base, const float* __restrict__ bg,                               \
+		const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_max_contrib,             \
+		const uint32_t* __restrict__ tile_order, const float* __restrict__ dL_dpixels, GsrGradSlot* __restrict__ slots,                        \
+		uint8_t* __restrict__ slot_valid, int cull, GsrAuxBlend aux)                                                                           \
+	{                                                                                                                                          \
+		gsr_render_backward_wave<AUX, ABS, RECOMPUTE>(W, H, gx, nslots, ranges, point_list, band_masks, splat, checkpoints, final_C, slot_base, bg, \
+		                                              final_Ts, n_contrib, tile_max_contrib, tile_order, dL_dpixels, slots, slot_valid, cull, aux); \
+	}
+GSR_BWD_KERNEL(gsr_render_backward_wave_kernel, false)             // the band masks are the forward's
+GSR_BWD_KERNEL(gsr_render_backward_recompute_kernel, true)         // GSR_DEBUG_RECOMPUTE_BANDS
+#undef GSR_BWD_KERNEL
+
 void gsr_launch_render_backward(const GsrFrame& f, const float* bg, const float* dL_dpix, hipEvent_t t_start, hipEvent_t t_stop,
                                 const GsrAuxBlend* aux, bool absgrad)
 {
@@ -557,9 +603,12 @@ void gsr_launch_render_backward(const GsrFrame& f, const float* bg, const float*
 	const int nwg = (nslots + GSR_WAVES_PER_WG - 1) / GSR_WAVES_PER_WG;
 	// (one kernel for both modes of the maps: it reads v from the record; the blend has no anti-aliased form, so the third slot of
 	// gsr_variant carries ABS here)
-	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, absgrad, [&](auto, auto AUX, auto ABS) {
-		gsr_launch(gsr_render_backward_wave_kernel<AUX() != 0, ABS()>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, f.s, t_start, t_stop, W, H, gx, nslots,
-		           img.ranges, f.bin.point_list, f.g.splat, f.bin.checkpoints, img.final_C, f.g.slot_base, bg, img.final_T, img.n_contrib,
+	// (... and the first, which no blend kernel has a use for, carries GSR_DEBUG_RECOMPUTE_BANDS)
+	gsr_variant((f.debug & GSR_DEBUG_RECOMPUTE_BANDS) != 0, aux ? GSR_AUX_DEPTH : 0, absgrad, [&](auto RECOMPUTE, auto AUX, auto ABS) {
+		auto kernel = gsr_render_backward_wave_kernel<AUX() != 0, ABS()>;
+		if (RECOMPUTE()) kernel = gsr_render_backward_recompute_kernel<AUX() != 0, ABS()>;
+		gsr_launch(kernel, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, f.s, t_start, t_stop, W, H, gx, nslots,
+		           img.ranges, f.bin.point_list, f.bin.band_masks, f.g.splat, f.bin.checkpoints, img.final_C, f.g.slot_base, bg, img.final_T, img.n_contrib,
 		           img.tile_max_contrib, img.tile_order, dL_dpix, f.slots, f.slot_valid, f.cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
 	});
 }

@@ -11,6 +11,8 @@
 // The blend kernels take `cull` as a launch argument: 0 (GSR_DEBUG_NO_CULL in the `debug` mask of the C ABI, include/gsr.h)
 // disables the exact-result-preserving culling below -- every instance of the reference's tile list is evaluated on every
 // band -- to bisect a suspected culling error.  Nothing is read from the environment.
+// The forward blend stores each list position's mask as a byte (GsrBinning::band_masks) and the backward blend reads it back instead of
+// evaluating gsr_tile_band_mask a second time (GSR_DEBUG_RECOMPUTE_BANDS: it evaluates it); the replay walk (gsr_replay.h) computes its own.
 
 #define GSR_WAVES_PER_WG 1
 #define GSR_PIX_PER_LANE 4

@@ -6,7 +6,8 @@
 //
 // Decomposition (render_common.h): one wave64 per tile, four pixels per lane, no workgroup
 // barrier.  Per batch of 64 instances each lane gathers one 48-byte splat record (prefetched one
-// batch ahead, ids two batches ahead), tests it against the tile (gsr_tile_band_mask) and the
+// batch ahead, ids two batches ahead), tests it against the tile (gsr_tile_band_mask), stores the
+// test's four bits as the position's byte of band_masks (the backward blend reads them back) and the
 // survivors are compacted into the wave's LDS slice; the inner loop broadcasts one record per
 // iteration to all lanes.  Skipped instances
 // are exactly those that blend into no pixel of the tile, so results are unchanged and
@@ -38,7 +39,7 @@ gsr_render_forward_wave_kernel(
 	int W, int H, int gx, int nslots, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
 	const GsrSplat* __restrict__ splat, float4* __restrict__ checkpoints, float* __restrict__ final_C, const float* __restrict__ bg, float* __restrict__ final_T,
 	uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_max_contrib, const uint32_t* __restrict__ tile_order,
-	float* __restrict__ out_color, int cull, GsrAuxBlend aux)
+	float* __restrict__ out_color, uint8_t* __restrict__ band_masks, int cull, GsrAuxBlend aux)
 {
 	__shared__ float4 s_rec[GSR_WAVES_PER_WG][3][64];
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -63,6 +64,7 @@ gsr_render_forward_wave_kernel(
 	const uint2 range = ranges[tile];
 	const int n = (int)(range.y - range.x);
 	const uint32_t* plist = point_list + range.x;
+	uint8_t* const pmask = band_masks + range.x;   // the band masks of the list's positions, for the backward (below)
 	// a heavy tile leaves depth checkpoints for the backward (gsr_internal.h GSR_CKPT_STRIDE): wave-uniform
 	const bool heavy = n >= 2 * GSR_CKPT_STRIDE;
 	bool walked_deep = false;   // a checkpoint was stored: only then can the backward cut this tile, and only then is final_C read
@@ -111,6 +113,12 @@ gsr_render_forward_wave_kernel(
 			}
 		}
 		const uint32_t bands = (base + lane < n) ? (cull ? gsr_tile_band_mask(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, x0f, y0f) : 0xFu) : 0u;
+		// The backward blend walks the same positions of the same list against the same tile: it takes this value instead of
+		// evaluating gsr_tile_band_mask again, and gathers the records of the positions with a non-zero byte only
+		// (render_backward.hip).  One byte per position, stored for every position of every batch this wave stages, so the masks are
+		// there up to the end of the batch that holds the wave's largest n_contrib -- as far as the backward walks.  The four band
+		// waves of a split tile compute the same value from the same record and tile: their concurrent identical stores are benign.
+		if (base + lane < n) pmask[base + lane] = (uint8_t)bands;
 		const bool keep = bands != 0u;
 		const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
 		const int cnt = __popcll(mask);
@@ -218,6 +226,6 @@ void gsr_launch_render_forward(const GsrFrame& f, const float* bg, float* out_co
 	gsr_variant(false, aux ? GSR_AUX_DEPTH : 0, false, [&](auto, auto AUX, auto) {   // (one kernel for both modes: it reads v from the record)
 		gsr_launch(gsr_render_forward_wave_kernel<AUX() != 0>, dim3(nwg), dim3(64 * GSR_WAVES_PER_WG), 0, f.s, nullptr, nullptr, W, H, gx, nslots,
 		           img.ranges, f.bin.point_list, f.g.splat, f.bin.checkpoints, img.final_C, bg, img.final_T, img.n_contrib, img.tile_max_contrib,
-		           ordered ? img.tile_order : nullptr, out_color, f.cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
+		           ordered ? img.tile_order : nullptr, out_color, f.bin.band_masks, f.cull ? 1 : 0, aux ? *aux : GsrAuxBlend{});
 	});
 }

@@ -38,7 +38,7 @@ class ImageLayout(ctypes.Structure):
 
 class BinningLayout(ctypes.Structure):
     _fields_ = [(n, _sz) for n in ("point_list", "point_list_alt", "tile_keys", "tile_keys_alt", "sort_table",
-                                   "checkpoints", "total", "tile_key_bytes", "column_pairs")]
+                                   "checkpoints", "total", "tile_key_bytes", "column_pairs", "band_masks")]
 
 
 class KernelTime(ctypes.Structure):
@@ -118,6 +118,7 @@ class AuxLayout(ctypes.Structure):
 # diagnostic bits as an int in the same argument, per call -- nothing is read from the environment.
 DEBUG_SYNC, DEBUG_NO_CULL, DEBUG_SERIAL, DEBUG_NO_SPLIT, DEBUG_TILE_SORT, DEBUG_RADIX_DEPTH, DEBUG_NO_TRIM = 1, 2, 4, 8, 16, 32, 64
 DEBUG_MEDIAN_FULL_WALK = 128   # include/gsr_median.h: median_forward() without its early exit
+DEBUG_RECOMPUTE_BANDS = 256    # the backward blend computes the band masks itself instead of reading the forward's bytes
 
 
 def _dbg(debug):

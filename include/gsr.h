@@ -55,6 +55,9 @@ typedef enum {
                                 image, radii, gradients and num_rendered, bit for bit; shorter tile lists) */
 #define GSR_DEBUG_NO_SPLIT 8 /* gsr_forward_render: heavy tiles (instance lists >= 640 and >= 2x the mean) are blended by one wave like
                                 every other tile, not by four waves of one 16x4-pixel band each (same results either way) */
+#define GSR_DEBUG_RECOMPUTE_BANDS 256 /* gsr_backward_blend*: the blend computes every instance's band mask from its record, as the forward blend did,
+                                instead of reading the bytes the forward stored (gsr_binning_layout.band_masks), and gathers every record of
+                                the walk: same results bit for bit; bisects a suspected stale or missing mask */
 
 /* Message of the last failing call on this thread ("" if none). */
 const char* gsr_last_error(void);
@@ -133,6 +136,10 @@ typedef struct {
 	                          of sorted instance i follows from `ranges`; [point_list_alt, tile_keys_alt) then holds up to R interleaved
 	                          8-byte records {u32 y0 | (h - 1) << 8, u32 Gaussian id}, sorted by tile column, then depth) unless
 	                          GSR_DEBUG_TILE_SORT is passed; 0: always the tile sort */
+	size_t band_masks;     /* [R] u8, of which the first L are used; inside tile_keys_alt, behind the validity flags (nothing else moved).  Byte i =
+	                          the four 16x4-pixel bands of its tile that the instance at point_list[i] can reach (the blend kernels' conservative
+	                          test; 0xF with GSR_DEBUG_NO_CULL), stored by the forward blend for every list position it staged -- in each tile at
+	                          least the positions below tile_max_contrib, which are all the backward blend reads; the rest is undefined */
 } gsr_binning_layout;
 
 int gsr_geometry_layout_of(int P, gsr_geometry_layout* out);
