@@ -23,6 +23,7 @@
 #include "../../include/gsr_mcmc.h"
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_filter3d.h"
+#include "../../include/gsr_tsdf.h"
 #include "../../include/gsr_knn.h"
 #include "../../include/gsr_rigidity.h"
 
@@ -1817,6 +1818,91 @@ extern "C" int gsr_filter3d_reset_opacity(int P, float* opacity, const float* sc
 	if (!(max_opacity > 0.0 && max_opacity < 1.0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: max_opacity must lie in (0, 1) (got %g)", who, max_opacity);
 	gsr_launch_filter3d_reset(P, opacity, scaling, filter, max_opacity, exp_avg, exp_avg_sq, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_reset");
+}
+
+// ---- TSDF fusion and marching tetrahedra (include/gsr_tsdf.h) ----
+// what every entry point refuses about the grid; 0 where there is nothing to refuse
+static int gsr_tsdf_grid_check(const char* who, const gsr_tsdf_grid* g, int least)
+{
+	if (!g) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: grid is NULL", who);
+	if (g->nx < least || g->ny < least || g->nz < least)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every dimension must be at least %d (got %d x %d x %d)", who, least, g->nx, g->ny, g->nz);
+	if ((long long)g->nx * g->ny > 0x7fffffffLL || (long long)g->nx * g->ny * g->nz > 0x7fffffffLL)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: %d x %d x %d nodes exceed 32-bit indexing", who, g->nx, g->ny, g->nz);
+	if (!std::isfinite(g->origin[0]) || !std::isfinite(g->origin[1]) || !std::isfinite(g->origin[2]))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the origin must be finite", who);
+	if (!(g->voxel_size > 0.0f) || !std::isfinite(g->voxel_size))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: voxel_size must be finite and positive (got %g)", who, (double)g->voxel_size);
+	return GSR_OK;
+}
+
+extern "C" int gsr_tsdf_integrate(const gsr_tsdf_grid* grid, float* wsum, float* dsum, float* csum, int C, const gsr_filter3d_camera* cameras,
+                                  const gsr_filter3d_camera* cameras_host, int H, int W, const float* depth, const float* color, const float* weight,
+                                  float sdf_trunc, float depth_trunc, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_tsdf_integrate";
+	if (const int rc = gsr_tsdf_grid_check(who, grid, 1)) return rc;
+	if (C < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: C must be at least 1 (got %d)", who, C);
+	if (H < 1 || W < 1 || H > (1 << 24) || W > (1 << 24) || (long long)H * W > 0x7fffffffLL)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: H and W must lie in 1 .. 2^24 with H W below 2^31 (got %d x %d)", who, H, W);
+	if (!wsum || !dsum || !cameras || !depth) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: wsum, dsum, cameras or depth is NULL", who);
+	if (color && !csum) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: color without csum", who);
+	if (!(sdf_trunc > 0.0f) || !std::isfinite(sdf_trunc))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: sdf_trunc must be finite and positive (got %g)", who, (double)sdf_trunc);
+	if (!(depth_trunc > 0.0f)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: depth_trunc must be positive or +inf (got %g)", who, (double)depth_trunc);
+	if (cameras_host)
+		for (int c = 0; c < C; c++)
+			if (cameras_host[c].W != (float)W || cameras_host[c].H != (float)H)
+				return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: camera %d is %g x %g, the depth maps are %d x %d", who, c, (double)cameras_host[c].W,
+				                (double)cameras_host[c].H, W, H);
+	gsr_launch_tsdf_integrate(*grid, wsum, dsum, csum, C, cameras, H, W, depth, color, weight, sdf_trunc, depth_trunc, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "tsdf_integrate");
+}
+
+extern "C" size_t gsr_tsdf_mesh_scratch_bytes(long long nodes)
+{
+	if (nodes < 8 || nodes > 0x7fffffffLL) return 0;
+	return gsr_tsdf_mesh_scratch_size(nodes);
+}
+
+extern "C" int gsr_tsdf_mesh_plan(const gsr_tsdf_grid* grid, const float* wsum, const float* dsum, float min_weight, void* scratch,
+                                  gsr_tsdf_mesh_plan_t* plan, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_tsdf_mesh_plan";
+	if (plan) plan->magic = 0;
+	if (const int rc = gsr_tsdf_grid_check(who, grid, 2)) return rc;
+	if (!wsum || !dsum || !scratch || !plan) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: wsum, dsum, scratch or plan is NULL", who);
+	if (((uintptr_t)scratch & 7) != 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 8-byte aligned", who);
+	if (!(min_weight > 0.0f) || !std::isfinite(min_weight))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: min_weight must be finite and positive (got %g)", who, (double)min_weight);
+	long long totals[2] = {0, 0};
+	if (const int rc = gsr_check_hip(gsr_launch_tsdf_mesh_plan(*grid, wsum, dsum, min_weight, scratch, totals, (hipStream_t)stream), "tsdf_mesh_plan")) return rc;
+	plan->V = totals[0]; plan->F = totals[1];
+	plan->grid = *grid; plan->wsum = wsum; plan->dsum = dsum; plan->scratch = scratch; plan->min_weight = min_weight;
+	plan->magic = GSR_TSDF_PLAN_MAGIC;
+	return GSR_OK;
+}
+
+extern "C" int gsr_tsdf_mesh_emit(const gsr_tsdf_mesh_plan_t* plan, long long V, long long F, const float* csum, float* vertices, float* colors,
+                                  int32_t* faces, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_tsdf_mesh_emit";
+	if (!plan) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: plan is NULL", who);
+	if (plan->magic != GSR_TSDF_PLAN_MAGIC) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the plan was not filled in by gsr_tsdf_mesh_plan", who);
+	if (const int rc = gsr_tsdf_grid_check(who, &plan->grid, 2)) return rc;
+	if (!plan->wsum || !plan->dsum || !plan->scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: the plan holds a NULL pointer", who);
+	if (V < 0 || F < 0 || V > 0x7fffffffLL || F > 0x7fffffffLL)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: V and F must lie in 0 .. 2^31 - 1 (got %lld, %lld)", who, V, F);
+	if (V != plan->V || F != plan->F)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: V %lld, F %lld are not the plan's (%lld, %lld)", who, V, F, plan->V, plan->F);
+	if (colors && !csum) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: colors without csum", who);
+	if (V == 0) return GSR_OK;   // nothing to write
+	if (!vertices || (F > 0 && !faces)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: vertices or faces is NULL", who);
+	gsr_launch_tsdf_mesh_emit(*plan, csum, vertices, colors, faces, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "tsdf_mesh_emit");
 }
 
 extern "C" size_t gsr_knn_scratch_bytes(int P) { return gsr_knn_scratch_size(P); }

@@ -416,6 +416,17 @@ void gsr_launch_filter3d_activate_backward(int P, const float* opacity, const fl
 void gsr_launch_filter3d_reset(int P, float* opacity, const float* scaling, const float* filter, double max_opacity, float* exp_avg, float* exp_avg_sq,
                                hipStream_t s);
 
+// tsdf.hip: TSDF fusion of depth maps and marching tetrahedra (include/gsr_tsdf.h)
+struct gsr_tsdf_grid;
+struct gsr_tsdf_mesh_plan_t;
+size_t gsr_tsdf_mesh_scratch_size(long long nodes);
+long long gsr_tsdf_integrate_blocks(const gsr_tsdf_grid& g);
+void gsr_launch_tsdf_integrate(const gsr_tsdf_grid& g, float* wsum, float* dsum, float* csum, int C, const gsr_filter3d_camera* cameras, int H, int W,
+                               const float* depth, const float* color, const float* weight, float sdf_trunc, float depth_trunc, hipStream_t s);
+hipError_t gsr_launch_tsdf_mesh_plan(const gsr_tsdf_grid& g, const float* wsum, const float* dsum, float min_weight, void* scratch, long long totals[2],
+                                     hipStream_t s);   // synchronises the stream: totals = {V, F} on the host
+void gsr_launch_tsdf_mesh_emit(const gsr_tsdf_mesh_plan_t& plan, const float* csum, float* vertices, float* colors, int32_t* faces, hipStream_t s);
+
 // normals.hip: per-Gaussian normals, depth normals and the normal-consistency loss (include/gsr_normals.h).  world: 0 = view-space output
 void gsr_launch_gaussian_normals(int P, const float* scales, const float* rotations, const float* means3D, const float* viewmatrix, int world,
                                  float* out, hipStream_t s);

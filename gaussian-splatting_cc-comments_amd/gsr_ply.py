@@ -162,3 +162,89 @@ def fetch_ply(path):
     colors = np.vstack([v["red"], v["green"], v["blue"]]).T / 255.0
     normals = np.vstack([v["nx"], v["ny"], v["nz"]]).T
     return points, colors, normals
+
+
+# ---- triangle mesh (fused_tsdf.TSDFVolume.extract_mesh) ---------------------------------------------------
+def write_mesh_ply(path, vertices, faces, colors=None):
+    """The triangle mesh MeshLab, Blender and Open3D read: binary little-endian, element `vertex` with float x y z and, with `colors`,
+    uchar red green blue; element `face` with `property list uchar int vertex_indices`, three indices a face.  vertices (V,3) float,
+    faces (F,3) integer, colors (V,3): uint8 as they are, floating point in [0, 1] scaled by 255 and rounded.  numpy arrays or torch
+    tensors; V = 0 and F = 0 are allowed."""
+    to_np = lambda t: t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    v = np.ascontiguousarray(to_np(vertices), dtype="<f4").reshape(-1, 3)
+    f = to_np(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"faces name vertices outside 0 .. {len(v) - 1}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = to_np(colors).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"colors has {len(c)} rows, expected {len(v)}")
+        if c.dtype != np.uint8:
+            c = np.rint(np.clip(np.nan_to_num(c.astype(np.float64)), 0.0, 1.0) * 255.0).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vrec = np.empty(len(v), dtype=np.dtype(fields))
+    for k, n in enumerate("xyz"):
+        vrec[n] = v[:, k]
+    if colors is not None:
+        for k, n in enumerate(("red", "green", "blue")):
+            vrec[n] = c[:, k]
+    frec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    frec["n"] = 3
+    frec["i"] = f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property {_NAMES[t[-2:]]} {n}" for n, t in fields]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vrec.tobytes())
+        out.write(frec.tobytes())
+
+
+def read_mesh_ply(path):
+    """-> (vertices (V,3) float32, faces (F,3) int32, colors (V,3) uint8 or None) of a file write_mesh_ply() wrote: binary
+    little-endian, a scalar `vertex` element followed by a `face` element of one list property whose lists all have three entries."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []   # [name, count, [property tokens]]
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: end of file inside the header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property":
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: a mesh must be binary_little_endian, not {fmt!r}")
+        if [e[0] for e in elements] != ["vertex", "face"]:
+            raise ValueError(f"{path}: expected the elements vertex and face, found {[e[0] for e in elements]}")
+        (_, V, vprops), (_, F, fprops) = elements
+        if any(p[0] == "list" or p[0] not in _TYPES for p in vprops):
+            raise ValueError(f"{path}: the vertex element must hold scalar properties only")
+        if len(fprops) != 1 or fprops[0][0] != "list" or fprops[0][1] not in _TYPES or fprops[0][2] not in _TYPES:
+            raise ValueError(f"{path}: the face element must hold one list property")
+        vdtype = np.dtype([(p[1], "<" + _TYPES[p[0]]) for p in vprops])
+        fdtype = np.dtype([("n", "<" + _TYPES[fprops[0][1]]), ("i", "<" + _TYPES[fprops[0][2]], (3,))])
+        vbuf, fbuf = f.read(V * vdtype.itemsize), f.read(F * fdtype.itemsize)
+        if len(vbuf) != V * vdtype.itemsize or len(fbuf) != F * fdtype.itemsize:
+            raise ValueError(f"{path}: the file is truncated")
+    vrec, frec = np.frombuffer(vbuf, dtype=vdtype, count=V), np.frombuffer(fbuf, dtype=fdtype, count=F)
+    if F and not (frec["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are supported")
+    vertices = np.stack([vrec["x"], vrec["y"], vrec["z"]], axis=1).astype(np.float32) if V else np.zeros((0, 3), np.float32)
+    colors = None
+    if all(n in vrec.dtype.names for n in ("red", "green", "blue")):
+        colors = np.stack([vrec["red"], vrec["green"], vrec["blue"]], axis=1).astype(np.uint8) if V else np.zeros((0, 3), np.uint8)
+    return vertices, np.ascontiguousarray(frec["i"]).astype(np.int32).reshape(-1, 3), colors
