@@ -24,6 +24,7 @@
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_filter3d.h"
 #include "../../include/gsr_tsdf.h"
+#include "../../include/gsr_vq.h"
 #include "../../include/gsr_knn.h"
 #include "../../include/gsr_rigidity.h"
 
@@ -1978,6 +1979,41 @@ extern "C" int gsr_knn_gather_backward(int P, int C, const int* offsets, const i
 	if (!offsets || !edges || !grad_out || !grad_x) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
 	gsr_launch_knn_gather_backward(P, C, offsets, edges, grad_out, grad_x, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "knn_gather_bwd");
+}
+
+// ---- vector quantisation (include/gsr_vq.h, vq.hip) -----------------------------------------------------------
+static int gsr_vq_check(const char* who, int N, int D, int K)
+{
+	if (N < 0) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: negative count (N %d)", who, N);
+	if (D < 1 || D > GSR_VQ_MAX_D) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: D must lie in 1..%d (got %d)", who, GSR_VQ_MAX_D, D);
+	if (K < 1 || K > GSR_VQ_MAX_K) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: K must lie in 1..%d (got %d)", who, GSR_VQ_MAX_K, K);
+	return GSR_OK;
+}
+
+extern "C" size_t gsr_vq_assign_scratch_bytes(int N, int D, int K) { return gsr_vq_assign_scratch_size(N, D, K); }
+
+extern "C" int gsr_vq_assign(int N, int D, const float* x, int K, const float* codebook, int* idx, float* dist2, void* scratch, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_vq_assign";
+	if (const int rc = gsr_vq_check(who, N, D, K)) return rc;
+	if (N == 0) return GSR_OK;
+	if (!x || !codebook || !idx || !scratch) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	if (!aligned16(scratch)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scratch must be 16-byte aligned", who);
+	gsr_launch_vq_assign(N, D, x, K, codebook, idx, dist2, scratch, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "vq_assign");
+}
+
+extern "C" int gsr_vq_update(int N, int D, const float* x, const float* weight, int K, const int* offsets, const int* members, float* codebook,
+                             int* count, float* wsum, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_vq_update";
+	if (const int rc = gsr_vq_check(who, N, D, K)) return rc;
+	if (N == 0) return GSR_OK;
+	if (!x || !offsets || !members || !codebook) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: required pointer is NULL", who);
+	gsr_launch_vq_update(D, x, weight, K, offsets, members, codebook, count, wsum, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "vq_update");
 }
 
 // ---- the neighbour-rigidity losses (include/gsr_rigidity.h, rigidity.hip) ------------------------------------

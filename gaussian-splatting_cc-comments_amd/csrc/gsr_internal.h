@@ -452,6 +452,11 @@ size_t gsr_knn_graph_scratch_size(int E, int P);
 void gsr_launch_knn_graph_build(int E, const int* idx, int P, int* offsets, int* edges, int* num_valid, void* scratch, hipStream_t s);
 void gsr_launch_knn_gather(int64_t E, int C, const float* x, const int* idx, float* out, hipStream_t s);
 void gsr_launch_knn_gather_backward(int P, int C, const int* offsets, const int* edges, const float* grad_out, float* grad_x, hipStream_t s);
+// vq.hip: nearest-code search and centroid update (include/gsr_vq.h)
+size_t gsr_vq_assign_scratch_size(int N, int D, int K);
+void gsr_launch_vq_assign(int N, int D, const float* x, int K, const float* codebook, int* idx, float* dist2, void* scratch, hipStream_t s);
+void gsr_launch_vq_update(int D, const float* x, const float* weight, int K, const int* offsets, const int* members, float* codebook, int* count,
+                          float* wsum, hipStream_t s);
 // rigidity.hip
 size_t gsr_rigidity_scratch_size(int P, int K);
 void gsr_launch_rigidity_zero(int P, float* values, float* grad_xyz, float* grad_rot, hipStream_t s);
