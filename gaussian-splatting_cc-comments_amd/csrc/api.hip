@@ -23,6 +23,7 @@
 #include "../../include/gsr_mcmc.h"
 #include "../../include/gsr_densify.h"
 #include "../../include/gsr_filter3d.h"
+#include "../../include/gsr_slice4d.h"
 #include "../../include/gsr_tsdf.h"
 #include "../../include/gsr_vq.h"
 #include "../../include/gsr_knn.h"
@@ -1819,6 +1820,96 @@ extern "C" int gsr_filter3d_reset_opacity(int P, float* opacity, const float* sc
 	if (!(max_opacity > 0.0 && max_opacity < 1.0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: max_opacity must lie in (0, 1) (got %g)", who, max_opacity);
 	gsr_launch_filter3d_reset(P, opacity, scaling, filter, max_opacity, exp_avg, exp_avg_sq, (hipStream_t)stream);
 	return gsr_stage_done((hipStream_t)stream, 0, "filter3d_reset");
+}
+
+// ---- 4D Gaussians at a time stamp: the slice and the harmonic colour coefficients (include/gsr_slice4d.h) ----
+// what every entry point refuses about P; 0 where there is nothing to refuse
+static int gsr_slice4d_size(const char* who, int P)
+{
+	if (P < 1) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: P must be at least 1 (got %d)", who, P);
+	if (!gsr_mcmc_fits(P, 6)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: 6 P exceeds 32-bit indexing (P %d)", who, P);
+	return GSR_OK;
+}
+
+// ... and about the leaves and the two scalars of the slice
+static int gsr_slice4d_inputs(const char* who, int P, const float* xyz, const float* t, const float* scaling, const float* scaling_t,
+                              const float* rotation, const float* rotation_r, const float* opacity, double modifier, double cutoff)
+{
+	if (const int rc = gsr_slice4d_size(who, P)) return rc;
+	if (!xyz || !t || !scaling || !scaling_t || !rotation || !rotation_r || !opacity)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: xyz, t, scaling, scaling_t, rotation, rotation_r or opacity is NULL", who);
+	if (!(std::isfinite(modifier) && modifier > 0.0))
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: scaling_modifier must be finite and positive (got %g)", who, modifier);
+	if (!(cutoff >= 0.0 && cutoff < 1.0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: cutoff must lie in [0, 1) (got %g)", who, cutoff);
+	return GSR_OK;
+}
+
+extern "C" int gsr_slice4d_forward(int P, const float* xyz, const float* t, const float* scaling, const float* scaling_t, const float* rotation,
+                                   const float* rotation_r, const float* opacity, double time, double scaling_modifier, double cutoff, float* means3D,
+                                   float* cov3D, float* opacities, float* velocity, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_slice4d_forward";
+	if (const int rc = gsr_slice4d_inputs(who, P, xyz, t, scaling, scaling_t, rotation, rotation_r, opacity, scaling_modifier, cutoff)) return rc;
+	if (!means3D && !cov3D && !opacities && !velocity) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every output is NULL", who);
+	gsr_launch_slice4d_forward(P, xyz, t, scaling, scaling_t, rotation, rotation_r, opacity, time, scaling_modifier, cutoff, means3D, cov3D, opacities,
+	                           velocity, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "slice4d_forward");
+}
+
+extern "C" int gsr_slice4d_backward(int P, const float* xyz, const float* t, const float* scaling, const float* scaling_t, const float* rotation,
+                                    const float* rotation_r, const float* opacity, double time, double scaling_modifier, double cutoff,
+                                    const float* dL_dmeans3D, const float* dL_dcov3D, const float* dL_dopacities, const float* dL_dvelocity,
+                                    float* dL_dxyz, float* dL_dt, float* dL_dscaling, float* dL_dscaling_t, float* dL_drotation, float* dL_drotation_r,
+                                    float* dL_dopacity, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_slice4d_backward";
+	if (const int rc = gsr_slice4d_inputs(who, P, xyz, t, scaling, scaling_t, rotation, rotation_r, opacity, scaling_modifier, cutoff)) return rc;
+	if (!dL_dxyz && !dL_dt && !dL_dscaling && !dL_dscaling_t && !dL_drotation && !dL_drotation_r && !dL_dopacity)
+		return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: every output is NULL", who);
+	gsr_slice4d_backward_args a;
+	a.P = P;
+	a.xyz = xyz; a.t = t; a.scaling = scaling; a.scaling_t = scaling_t; a.rotation = rotation; a.rotation_r = rotation_r; a.opacity = opacity;
+	a.time = time; a.modifier = scaling_modifier; a.cutoff = cutoff;
+	a.g_means3D = dL_dmeans3D; a.g_cov3D = dL_dcov3D; a.g_opacities = dL_dopacities; a.g_velocity = dL_dvelocity;
+	a.d_xyz = dL_dxyz; a.d_t = dL_dt; a.d_scaling = dL_dscaling; a.d_scaling_t = dL_dscaling_t; a.d_rotation = dL_drotation;
+	a.d_rotation_r = dL_drotation_r; a.d_opacity = dL_dopacity;
+	gsr_launch_slice4d_backward(a, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "slice4d_backward");
+}
+
+// what both harmonic entry points refuse about their sizes and the period
+static int gsr_harmonic_inputs(const char* who, int P, int N, int M, const float* features_t, const float* t, double period)
+{
+	if (const int rc = gsr_slice4d_size(who, P)) return rc;
+	if (N < 0 || N > GSR_HARMONIC_MAX_N) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: N must lie in 0..%d (got %d)", who, GSR_HARMONIC_MAX_N, N);
+	if (M < 1 || M > GSR_HARMONIC_MAX_M) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: M must lie in 1..%d (got %d)", who, GSR_HARMONIC_MAX_M, M);
+	if (!features_t || !t) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: features_t or t is NULL", who);
+	if (!(std::isfinite(period) && period > 0.0)) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: period must be finite and positive (got %g)", who, period);
+	return GSR_OK;
+}
+
+extern "C" int gsr_harmonic_features(int P, int N, int M, const float* features_t, const float* t, double time, double period, float* shs, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_harmonic_features";
+	if (const int rc = gsr_harmonic_inputs(who, P, N, M, features_t, t, period)) return rc;
+	if (!shs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: shs is NULL", who);
+	gsr_launch_harmonic_forward(P, N, M, features_t, t, time, period, shs, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "harmonic_forward");
+}
+
+extern "C" int gsr_harmonic_features_backward(int P, int N, int M, const float* features_t, const float* t, double time, double period,
+                                              const float* dL_dshs, float* dL_dfeatures_t, float* dL_dt, void* stream)
+{
+	g_err[0] = 0;
+	const char* who = "gsr_harmonic_features_backward";
+	if (const int rc = gsr_harmonic_inputs(who, P, N, M, features_t, t, period)) return rc;
+	if (!dL_dshs) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: dL_dshs is NULL", who);
+	if (!dL_dfeatures_t && !dL_dt) return gsr_fail(GSR_ERR_INVALID_ARGUMENT, "%s: both outputs are NULL", who);
+	gsr_launch_harmonic_backward(P, N, M, features_t, t, time, period, dL_dshs, dL_dfeatures_t, dL_dt, (hipStream_t)stream);
+	return gsr_stage_done((hipStream_t)stream, 0, "harmonic_backward");
 }
 
 // ---- TSDF fusion and marching tetrahedra (include/gsr_tsdf.h) ----

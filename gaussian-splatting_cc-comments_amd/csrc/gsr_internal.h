@@ -416,6 +416,22 @@ void gsr_launch_filter3d_activate_backward(int P, const float* opacity, const fl
 void gsr_launch_filter3d_reset(int P, float* opacity, const float* scaling, const float* filter, double max_opacity, float* exp_avg, float* exp_avg_sq,
                                hipStream_t s);
 
+// slice4d.hip: 4D Gaussians at a time stamp, the slice and the harmonic colour coefficients (include/gsr_slice4d.h)
+struct gsr_slice4d_backward_args {
+	int P;
+	const float *xyz, *t, *scaling, *scaling_t, *rotation, *rotation_r, *opacity;
+	double time, modifier, cutoff;
+	const float *g_means3D, *g_cov3D, *g_opacities, *g_velocity;   // any may be NULL: zero
+	float *d_xyz, *d_t, *d_scaling, *d_scaling_t, *d_rotation, *d_rotation_r, *d_opacity;   // any may be NULL: not written
+};
+void gsr_launch_slice4d_forward(int P, const float* xyz, const float* t, const float* scaling, const float* scaling_t, const float* rotation,
+                                const float* rotation_r, const float* opacity, double time, double modifier, double cutoff, float* means3D,
+                                float* cov3D, float* opacities, float* velocity, hipStream_t s);
+void gsr_launch_slice4d_backward(const gsr_slice4d_backward_args& a, hipStream_t s);
+void gsr_launch_harmonic_forward(int P, int N, int M, const float* features_t, const float* t, double time, double period, float* shs, hipStream_t s);
+void gsr_launch_harmonic_backward(int P, int N, int M, const float* features_t, const float* t, double time, double period, const float* g_shs,
+                                  float* d_features_t, float* d_t, hipStream_t s);
+
 // tsdf.hip: TSDF fusion of depth maps and marching tetrahedra (include/gsr_tsdf.h)
 struct gsr_tsdf_grid;
 struct gsr_tsdf_mesh_plan_t;

@@ -19,6 +19,7 @@ leaves (`pc._xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation`) 
 their backward done inside the per-Gaussian kernels (fused_params.py) -- same result dict.
 `pipe.antialiasing = True` (where upstream's PipelineParams keeps it) renders with the screen-space filter (GaussianRasterizer).
 `filter_3d=` renders with Mip-Splatting's 3D smoothing filter folded into the opacities and scales (fused_filter3d).
+`time=` renders a model of 4D Gaussians conditioned on that time stamp (fused_slice4d).
 """
 import math
 
@@ -85,7 +86,7 @@ def _unpack(out, depth_alpha, features, distortion=False, median_depth=False):
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, densify_stats=None,
            depth_alpha=None, antialiasing=None, contrib_stats=None, contrib_pixel_weight=None, camera_grads=None,
            absgrad=None, features=None, distortion=False, median_depth=False, index_maps=None, normals=False, camera_model=None,
-           camera_model_grads=None, filter_3d=None):
+           camera_model_grads=None, filter_3d=None, time=None):
     """Render the scene seen from `viewpoint_camera`.  `bg_color` must live on the GPU.
     densify_stats (extension): see GaussianRasterizer -- the statistics of train.py:157-159 updated by the backward.
     depth_alpha (extension): "depth" or "invdepth" adds "depth" and "alpha" (1, H, W) to the dict -- see GaussianRasterizer.
@@ -124,7 +125,18 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     gradients reach the two leaves through that function's backward.  Always the GaussianRasterizer path, under
     pipe.fused_activations too: the two per-Gaussian leaf kernels do not know the filter, and teaching them means new instantiations
     across every variant of both (a follow-up).  Not with pipe.compute_cov3D_python (NotImplementedError): the covariance of
-    pc.get_covariance() carries no filter."""
+    pc.get_covariance() carries no filter.
+    time (extension): a Python float -- `pc` is a model of 4D Gaussians (Yang et al., "Real-time Photorealistic Dynamic Scene
+    Representation and Rendering with 4D Gaussian Splatting") and must carry `_t` (P,1), `_scaling_t` (P,1) and `_rotation_r` (P,4) beside
+    the usual leaves (TypeError otherwise, before anything runs).  The rasterizer receives fused_slice4d.slice_at(pc._xyz, pc._t,
+    pc._scaling, pc._scaling_t, pc._rotation, pc._rotation_r, pc._opacity, time, scaling_modifier) as its means3D, cov3D_precomp and
+    opacities, and the gradients reach the seven leaves through that function's backward.  If `pc` has `_features_t` (P, N+1, M, 3)
+    (with `pc.time_period`) the rasterizer receives fused_slice4d.harmonic_features(pc._features_t, pc._t, time, pc.time_period) as its
+    shs, otherwise pc.get_features.  Always the GaussianRasterizer path, as with filter_3d; every other extension keyword works
+    unchanged on top.  "viewspace_points" is zeros_like of the sliced means; "visibility_filter" is (radii > 0) &
+    fused_slice4d.visible_at(opacities): a Gaussian whose temporal marginal is at or below the cutoff is not visible.  "radii" and the
+    denominators of densify_stats are not touched: a masked Gaussian inside the frustum still has its radius and still counts there.
+    Not with filter_3d, pipe.compute_cov3D_python or pipe.convert_SHs_python (NotImplementedError).  None: today's code path."""
     from diff_gaussian_rasterization import _C
     _C.normals_flag(normals)   # a switch: anything but a bool is refused
     if camera_model is None:
@@ -138,13 +150,31 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     camera_model_grads = _C.camera_model_grads_arg(camera_model_grads, camera_model)   # refused before anything runs too
     if antialiasing is None:
         antialiasing = getattr(pipe, "antialiasing", False)
+    if time is not None:   # refused before anything runs too
+        import fused_slice4d
+        missing = [n for n in ("_t", "_scaling_t", "_rotation_r") if not hasattr(pc, n)]
+        if missing:
+            raise TypeError(f"time=: the model must carry _t, _scaling_t and _rotation_r (4D Gaussians); it lacks {', '.join(missing)}")
+        for on, what in ((filter_3d is not None, "filter_3d"), (bool(pipe.compute_cov3D_python), "pipe.compute_cov3D_python"),
+                         (bool(pipe.convert_SHs_python), "pipe.convert_SHs_python")):
+            if on:
+                raise NotImplementedError(f"time= with {what}: the time slice hands the rasterizer its own covariance, opacities and SH coefficients")
+        leaves4d = (pc._xyz, pc._t, pc._scaling, pc._scaling_t, pc._rotation, pc._rotation_r, pc._opacity)
+        fused_slice4d._check(**dict(zip(fused_slice4d.LEAVES, leaves4d)))
+        fused_slice4d._check_scalars(time, scaling_modifier, 0.05)
+        harmonics = hasattr(pc, "_features_t")
+        if harmonics:
+            fused_slice4d._check(t=pc._t, features_t=pc._features_t)
+            fused_slice4d._check_period(pc.time_period)
+        fused_slice4d._check_device(*leaves4d, *((pc._features_t,) if harmonics else ()))
+        sliced = fused_slice4d.slice_at(*leaves4d, float(time), scaling_modifier=float(scaling_modifier))
     if filter_3d is not None:   # refused before anything runs, and before the kernel library is loaded
         import fused_filter3d
         if bool(pipe.compute_cov3D_python):
             raise NotImplementedError("filter_3d with pipe.compute_cov3D_python: pc.get_covariance() carries no 3D filter")
         fused_filter3d._check(opacity=pc._opacity, scaling=pc._scaling, filter_3d=filter_3d)
         fused_filter3d._check_device(pc._opacity, pc._scaling, filter_3d)
-    xyz = pc.get_xyz
+    xyz = pc.get_xyz if time is None else sliced[0]
     # carrier of the screen-space gradient: zeros, a non-leaf that keeps its grad
     screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True, device=xyz.device) + 0
     try:
@@ -160,7 +190,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         extras["absgrad"] = absgrad
     python_cov = bool(pipe.compute_cov3D_python)
     python_sh = bool(pipe.convert_SHs_python)
-    leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh and filter_3d is None
+    leaf = bool(getattr(pipe, "fused_activations", False)) and override_color is None and not python_cov and not python_sh and filter_3d is None and time is None
     user_channels = None
     if normals:   # three more feature channels behind the caller's own
         n = _gaussian_normals(viewpoint_camera, pc, leaf, camera_grads is True or camera_model_grads is not False)
@@ -189,9 +219,11 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth),
                        user_channels=user_channels)
 
-    inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity,
+    inputs = dict(means3D=xyz, means2D=screenspace_points, opacities=pc.get_opacity if time is None else sliced[2],
                   shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None)
-    if python_cov:
+    if time is not None:
+        inputs["cov3D_precomp"] = sliced[1]
+    elif python_cov:
         inputs["cov3D_precomp"] = pc.get_covariance(scaling_modifier)
     else:
         inputs["scales"], inputs["rotations"] = pc.get_scaling, pc.get_rotation
@@ -201,10 +233,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         inputs["colors_precomp"] = override_color
     elif python_sh:
         inputs["colors_precomp"] = _python_sh_colors(viewpoint_camera, pc)
+    elif time is not None and harmonics:
+        inputs["shs"] = fused_slice4d.harmonic_features(pc._features_t, pc._t, float(time), float(pc.time_period))
     else:
         inputs["shs"] = pc.get_features
 
     out = GaussianRasterizer(raster_settings=settings, densify_stats=densify_stats, depth_alpha=depth_alpha,
                              antialiasing=antialiasing, **extras)(**inputs, **feat)
-    return _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth),
-                   user_channels=user_channels)
+    result = _result(out[0], screenspace_points, *_unpack(out, depth_alpha, features, distortion, median_depth),
+                     user_channels=user_channels)
+    if time is not None:
+        result["visibility_filter"] = result["visibility_filter"] & fused_slice4d.visible_at(sliced[2])
+    return result
