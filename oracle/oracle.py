@@ -188,6 +188,62 @@ def blend_backward_exact(s, dL_dpix):
     return g
 
 
+BLEND_TENSORS = ("dL_dmeans2D", "dL_dconic", "dL_dopacity", "dL_dcolors")
+# where each tensor's components sit among the nine of a row (mean2D x, y; conic a, b, c; opacity; colour r, g, b)
+BLEND_COLUMNS = dict(dL_dmeans2D=slice(0, 2), dL_dconic=slice(2, 5), dL_dopacity=slice(5, 6), dL_dcolors=slice(6, 9))
+
+
+CKPT_STRIDE = 512   # csrc/render_common.h GSR_CKPT_STRIDE: list positions between the forward's (T, C) checkpoints of a heavy tile
+
+
+def restart_positions(s, kept=None, stride=CKPT_STRIDE):
+    """uint8 marks, indexed like point_list: the list positions at which a backward walk may start from the forward's checkpoint --
+    every `stride`-th position of a tile's list, counted among the entries `kept` (bool, like point_list; None: all) as a binning
+    that leaves instances out counts them."""
+    R = s["num_rendered"]
+    kept = np.ones(R, bool) if kept is None else np.asarray(kept, bool)
+    rng = s["ranges"].astype(np.int64)
+    lens = rng[:, 1] - rng[:, 0]
+    start = np.repeat(rng[:, 0], lens)   # (the ranges partition [0, R) in tile order)
+    before = np.concatenate([[0], np.cumsum(kept)])
+    pos = before[:-1] - before[start]    # position of an entry among the kept entries of its tile
+    return (kept & (pos > 0) & (pos % stride == 0)).astype(np.uint8)
+
+
+def blend_backward_budget(s, dL_dpix, restart_at=None):
+    """blend_backward_exact together with each row's fp32 error budget (gsro_render_backward_budget).
+    Returns float64 arrays that hold only the components the blend defines -- S: dL_dmeans2D (P,2),
+    dL_dconic (P,3) = (.x, .y, .w of the (P,2,2) buffer), dL_dopacity (P,1), dL_dcolors (P,3) -- and, shaped
+    alike under "A", "B" and "E": A = sum |term|, B = sum of the per-term budgets in units of 2^-24, and the
+    row bound E = 2^-24 (B + n A); "n" (P,) is the number of (pixel, Gaussian) terms of the row.
+    restart_at: the marks of restart_positions (default: every CKPT_STRIDE-th position of the oracle's own lists) -- walks that
+    start there from the forward's colour sums, as the kernels' depth segments do, get their allowance; an array of zeros
+    leaves the reference's recurrence alone."""
+    dL_dpix = _f32(dL_dpix)
+    P, W, H = s["P"], s["W"], s["H"]
+    m2 = np.zeros((P, 2), np.float64)
+    con = np.zeros((P, 3), np.float64)
+    op = np.zeros(P, np.float64)
+    col = np.zeros((P, 3), np.float64)
+    n = np.zeros(P, np.float64)
+    A = np.zeros((P, 9), np.float64)
+    B = np.zeros((P, 9), np.float64)
+    colors = s["colors_precomp"] if s["colors_precomp"] is not None else s["rgb"]
+    if P and s["num_rendered"]:
+        restart_at = restart_positions(s) if restart_at is None else np.ascontiguousarray(restart_at, dtype=np.uint8)
+        assert restart_at.shape == (s["num_rendered"],)
+        rc = lib().gsro_render_backward_budget(W, H, _p(s["ranges"], _u), _p(s["point_list"], _u), _p(s["bg"], _f),
+                                               _p(s["means2D"], _f), _p(s["conic_opacity"], _f), _p(colors, _f),
+                                               _p(s["n_contrib"], _u), _p(dL_dpix, _f), _p(m2, _d), _p(con, _d), _p(op, _d),
+                                               _p(col, _d), _p(n, _d), _p(A, _d), _p(B, _d), _p(restart_at, _b))
+        assert rc == 0
+    E = 2.0 ** -24 * (B + n[:, None] * A)
+    out = dict(S=dict(dL_dmeans2D=m2, dL_dconic=con, dL_dopacity=op.reshape(P, 1), dL_dcolors=col), n=n.astype(np.int64))
+    for name, arr in (("A", A), ("B", B), ("E", E)):
+        out[name] = {k: arr[:, c] for k, c in BLEND_COLUMNS.items()}
+    return out
+
+
 def gaussian_backward(s, dL_dmeans2D, dL_dconic, dL_dcolors):
     """Only BACKWARD::preprocess (backward.cu:144-277, 349-399) on caller-supplied blend sums
     (dL_dmeans2D (P,3), dL_dconic (P,2,2), dL_dcolors (P,3), float32): lets a test feed the HIP

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import grad_rows
 import gsr_scene
 import util
 
@@ -74,8 +75,25 @@ def _nerr(a, b):
     return float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max() / max(np.abs(b).max(), 1e-20))
 
 
-def check_grads(h, o, dpix, names, label=None, og=None):
-    """Three levels.
+def check_rows(h, o, dpix, label=None):
+    """The per-row level of check_grads: every row and component of the HIP blend sums (dL_dmeans2D, dL_dconic, dL_dopacity,
+    dL_dcolors of raw_grads) within the row's own float64 bound, |hip - S| <= E = 2^-24 (B + n A) of
+    oracle.blend_backward_budget (derived in tests/test_grad_rows_gpu.py), and +0 bits in every row without terms."""
+    # the depth segments of a heavy tile start every GSR_CKPT_STRIDE-th position of the list the binning kept
+    kept = util.trimmed_expectation(o, h["rshape"], o["W"], o["H"])["kept"] if o["num_rendered"] > 0 else None
+    bud = util.oracle.blend_backward_budget(o, dpix.numpy(), restart_at=util.oracle.restart_positions(o, kept) if o["num_rendered"] > 0 else None)
+    ratios, bad = grad_rows.rows_failures(h["raw_grads"], bud)
+    msg = grad_rows.format_ratios(ratios)
+    print(msg)
+    util.parity_log(f"[{label or 'case'}] blend sums per row: largest |hip - float64| / E\n" + msg)
+    assert not bad, "a row of the blend sums lies outside its float64 bound:\n" + "\n".join(bad) + "\n" + msg
+    return ratios
+
+
+def check_grads(h, o, dpix, names, label=None, og=None, rows=True):
+    """Four levels.
+    (0) per row (check_rows above): every Gaussian's row of the blend sums within its own float64 bound -- the three levels below
+        speak for the few rows with the largest gradients only.  rows=False leaves the level out; a caller says why.
     (1) backward blend kernel alone: its per-Gaussian sums (dL_dmean2D, dL_dconic, dL_dopacity,
         dL_dcolors) against the oracle's double-precision sums, 1e-5 norm-wise.
     (2) per-Gaussian chain alone: the HIP outputs against the oracle's chain evaluated on the HIP
@@ -84,6 +102,8 @@ def check_grads(h, o, dpix, names, label=None, og=None):
         where that is larger: its backward sums with fp32 atomics in hardware order, so two runs
         of the reference differ; the oracle measures that spread by accumulating in fp32 in two
         different tile orders (accum_mode 1 / 2) and the bar is max(1e-5, 2 x spread)."""
+    if rows:
+        check_rows(h, o, dpix, label)
     if og is None:
         og = util.oracle.backward(o, dpix.numpy())
     raw = h["raw_grads"]
