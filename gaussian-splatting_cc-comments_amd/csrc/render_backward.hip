@@ -4,7 +4,11 @@
 // nine fp32 atomicAdd per contributing (pixel, Gaussian) pair, all 256 lanes of a tile hitting the
 // same addresses -- the slowest atomic shape on this chip (MI355X_MICROARCH.md "Global float
 // atomics").  Here one wave64 owns the tile (render_common.h): per surviving instance each lane
-// first adds its four pixels' nine partials in registers; the wave then folds them through LDS --
+// first adds its four pixels' partials in registers -- six sums for the nine words: the five geometric words are moments of
+// f = o g, g = G dL/dalpha, and neither the opacity o (one value per instance) nor dx (one value per lane: its four pixels share
+// their column) varies over a lane's sum, so the lane keeps sum g, sum g dy, sum g dy^2 and the three colour sums, forms
+// dx sum g, dx^2 sum g, dx sum g dy and the five products with o once per reduced instance ("per-lane partial sums" in the
+// kernel; 8 issue slots per evaluated pair instead of 13, 8 more per reduction); the wave then folds the nine values through LDS --
 // lane l stores eight of them as row l of a 64 x 9-word area (odd row stride: 64 rows, 64 banks), the
 // eight lanes of group c add column c (eight rows each).  What is left -- the three DPP steps over
 // each group's column sums, the ninth value's sum over the wave, the epilogue and the stores -- is
@@ -95,15 +99,17 @@ __device__ __forceinline__ float gsr_abs_sum(v2f a) { return __builtin_fabsf(a.x
 // its accum_rec (restarted from ckpt_depth / final_D by the depth segments), (v - accum_rec_D) dL/dD in dL/dalpha -- dL/dA enters
 // through the background term (A = 1 - T_final: -T_final (bg . dL/dpix - dL/dA)), and dL/dv = sum alpha T dL/dD is a tenth reduced
 // partial, written to the slot's pad0.  Same slots, same order, no atomics.
-// ABS (absolute screen-space gradients, include/gsr_absgrad.h): beside the signed moments sum f dx, sum f dy every evaluated pair adds
-// the moduli of its two per-pixel terms of dL/dmean2D, |f (a dx + b dy)| and |f (c dy + b dx)| -- taken per pixel, before any sum --
+// ABS (absolute screen-space gradients, include/gsr_absgrad.h): beside the signed sums every evaluated pair adds
+// the moduli of its two per-pixel terms of dL/dmean2D, |f (a dx + b dy)| and |f (c dy + b dx)| -- taken per pixel, before any sum,
+// so this variant alone still forms f = (o dL/dalpha) G, f dx and f dy per pixel, for the moduli only --
 // into two more partials; both are reduced over the wave like the AUX variant's tenth value and written, scaled by 0.5 W / 0.5 H, to
 // the slot's pad1 / pad2 (gsr_absgrad_fold_kernel, absgrad.hip, adds them per Gaussian).  The ABS instantiations finish every instance
 // on its own, as the AUX ones do; the other nine (ten) words are computed by the same operations as without ABS.
 // Waves per SIMD: four (at most 128 VGPRs) for every instantiation but <AUX, ABS>.  The AUX variant alone fills the 128 (left
 // to itself the compiler takes 130), and the two accumulators, the halved b and the terms' temporaries of ABS on top spill 10
 // registers to scratch at that limit: that instantiation takes 146 VGPRs (144 before the pair modes' staging) and runs three waves per
-// SIMD, without scratch.
+// SIMD, without scratch.  (Those are the counts with nine accumulators.  With six: default 122, ABS 118, AUX 124, <AUX, ABS> 130 VGPRs,
+// the GSR_DEBUG_RECOMPUTE_BANDS twins 128 / 128 / 128 / 140; the same waves per SIMD, no scratch -- profiles/ab_c3_backward_moments.txt.)
 //
 // The band masks (RECOMPUTE = false, the product's kernels).  reach -- gsr_tile_band_mask of the record against this tile -- is the value
 // the forward blend computed for the same list position from the same six record fields and the same tile origin, and stored as that
@@ -361,12 +367,17 @@ __device__ __forceinline__ void gsr_render_backward_wave(
 			float absx = 0.f, absy = 0.f;
 			if constexpr (ABS) CBh = -0.5f * CB;
 			// per-lane partial sums over its pixels (one float2 = two pixels, added at the end).  The
-			// geometric terms are kept as raw moments of f = G * dL/dG (sum f dx, f dy, f dx^2, f dx dy,
-			// f dy^2); the conic and the 0.5*W / 0.5*H / -0.5 factors of backward.cu:574-594 are applied
-			// once per instance after the reduction.
+			// geometric terms are raw moments of f = G * dL/dG = o g with g = G dL/dalpha (sum f dx, f dy, f dx^2, f dx dy,
+			// f dy^2).  Two of f's factors do not vary over a lane's sum: the opacity o is one value per instance, and dx is one
+			// value per lane (its four pixels share their column).  So a lane accumulates only sum g (acc[5], the dL/dopacity
+			// word as it always was), sum g dy (acc[1]) and sum g dy^2 (acc[4]); dx and dx^2 meet the lane's sums once per
+			// reduced instance, and so does the opacity (the reduction below says why not later); the conic and the
+			// 0.5*W / 0.5*H / -0.5 factors of backward.cu:574-594 meet the wave's totals.  Six accumulators of the nine words are left:
+			// acc[i] is the lane's share of word i for i = 1, 4 .. 8; words 0, 2, 3 have none.
 			v2f acc[GSR_BWD_NV + 1];   // [9]: dL/dv (AUX)
 #pragma unroll
-			for (int i = 0; i < GSR_BWD_NV + 1; i++) acc[i] = v2f{-0.f, -0.f};  // x + (-0) is x for every x: the first pair's sums need no add
+			for (int i = 0; i < GSR_BWD_NV + 1; i++)
+				if (i != 0 && i != 2 && i != 3) acc[i] = v2f{-0.f, -0.f};  // x + (-0) is x for every x: the first pair's sums need no add
 			unsigned long long any = 0ull;  // lanes with a hit, kept as a scalar mask: the loop's branches test masks, not ballots of bools
 			// One pair in mode M (its reachable bands: 3 both, 1 the .x band, 2 the .y band): the same operations in the same order
 			// on a v2f or on one half of every register pair.  A band left out could not have hit: its alpha would be forced to 0,
@@ -376,7 +387,6 @@ __device__ __forceinline__ void gsr_render_backward_wave(
 				typedef gsr_half<M> Hf;
 				typedef typename Hf::type V_t;
 				// power = -0.5f * (a*dx*dx + c*dy*dy) - b*dx*dy in the reference's operation order (CA, CC carry the -0.5)
-				const V_t dxh = Hf::get(dx);
 				const V_t dy = Hf::get(Y) - Hf::get(pfy[p]);
 				const V_t power = (Hf::get(ax2) + (Hf::get(CC) * dy) * dy) - Hf::get(bdx) * dy;
 				// __expf(x) = v_exp_f32(x * log2(e)) (the forward's form, same constant, same IEEE product): the two products as one
@@ -446,15 +456,16 @@ __device__ __forceinline__ void gsr_render_backward_wave(
 				Hf::set(acc[6], gsr_fma(dch, Hf::get(dp0[p]), Hf::get(acc[6])));
 				Hf::set(acc[7], gsr_fma(dch, Hf::get(dp1[p]), Hf::get(acc[7])));
 				Hf::set(acc[8], gsr_fma(dch, Hf::get(dp2[p]), Hf::get(acc[8])));
-				Hf::set(acc[5], gsr_fma(G, dla, Hf::get(acc[5])));  // dL/dopacity
-				const V_t f = (Hf::get(OP) * dla) * G;                 // dL/dG * G
-				const V_t fdx = f * dxh, fdy = f * dy;
-				Hf::set(acc[0], Hf::get(acc[0]) + fdx);
-				Hf::set(acc[1], Hf::get(acc[1]) + fdy);
-				Hf::set(acc[2], gsr_fma(fdx, dxh, Hf::get(acc[2])));
-				Hf::set(acc[3], gsr_fma(fdx, dy, Hf::get(acc[3])));
-				Hf::set(acc[4], gsr_fma(fdy, dy, Hf::get(acc[4])));
+				Hf::set(acc[5], gsr_fma(G, dla, Hf::get(acc[5])));  // dL/dopacity = sum g, g = G dL/dalpha: also the x moments' sum
+				const V_t g = G * dla;
+				const V_t gdy = g * dy;
+				Hf::set(acc[1], Hf::get(acc[1]) + gdy);
+				Hf::set(acc[4], gsr_fma(gdy, dy, Hf::get(acc[4])));
 				if constexpr (ABS) {   // a pixel without a hit has f = 0: it adds exact zeros here as above
+					// the per-pixel moduli alone still need f = dL/dG * G and its two products; the nine words come from the sums above
+					const V_t dxh = Hf::get(dx);
+					const V_t f = (Hf::get(OP) * dla) * G;
+					const V_t fdx = f * dxh, fdy = f * dy;
 					const V_t tx = gsr_fma(Hf::get(CA), fdx, Hf::get(CBh) * fdy), ty = gsr_fma(Hf::get(CC), fdy, Hf::get(CBh) * fdx);
 					absx += gsr_abs_sum(tx);
 					absy += gsr_abs_sum(ty);
@@ -484,7 +495,20 @@ __device__ __forceinline__ void gsr_render_backward_wave(
 				GSR_TILE_STAT(st_reductions++;)
 				float v[GSR_BWD_NV];
 #pragma unroll
-				for (int i = 0; i < GSR_BWD_NV; i++) v[i] = gsr_add_halves(acc[i]);
+				for (int i = 0; i < GSR_BWD_NV; i++)
+					if (i != 0 && i != 2 && i != 3) v[i] = gsr_add_halves(acc[i]);
+				// the lane's dx on its sums: sum g dx = dx sum g, sum g dx^2 = dx (dx sum g), sum g dx dy = dx sum g dy
+				v[0] = dx.x * v[5];
+				v[2] = dx.x * v[0];
+				v[3] = dx.x * v[1];
+				// ... and the instance's opacity on the five geometric words: sums of g become sums of f = o g.  Per lane, before the
+				// transposition, not once on the wave's totals (two instructions per reduced instance cheaper, measured first): a
+				// rounding of a whole word is one error of 2^-24 of it that the other words do not share, and dL/dscales and
+				// dL/drotations of a thin splat are differences of the three conic words that cancel a thousandfold -- one heavy-tile
+				// fuzz scene then left dL/drotations 43 % over its end-to-end bar.  64 lanes' roundings average out, as the per-pixel
+				// roundings of f did.
+#pragma unroll
+				for (int i = 0; i < 5; i++) v[i] *= OP.x;
 				// the wave reduction of the first eight values through LDS: 64 x 8 partials in, transposed out -- the cross-lane work
 				// is LDS traffic (its own issue port) plus 7 adds and the 3 DPP steps inside an 8-lane group, instead of 6 lane swaps,
 				// 6 adds, 2 selects and 4 DPP steps on the vector ALU, which is what bounds this kernel.  A wave's LDS operations
