@@ -7,7 +7,11 @@ of the right Euler characteristic whose vertices lie on their grid edges.  The i
 ambiguous nodes, and in each of them (but the grid of one node) pairs are skipped, cut at -sdf_trunc and clamped to 1.
 The end-to-end scene (six cameras on the axes, 3 units from a sphere of radius 0.5, 64 x 64 pixels at focal 100, a 24^3 grid of voxel
 0.0696, sdf_trunc of 3 voxels), fused and meshed by the reference: every vertex within 0.860 voxel_size of the sphere, 0.156 in the
-mean (with the default truncation of 4 voxels it is 1.09: the projective distance at grazing rays).  Nothing here touches a device."""
+mean (with the default truncation of 4 voxels it is 1.09: the projective distance at grazing rays).
+The array form of the reference (mesh_ref_fast, for volumes of a million nodes) equals the loop form byte for byte on every field of
+the GPU's extraction tests; the noise field reaches all 6 x 14 (tetrahedron, case) rows, all seven edge kinds, t = 0 and t = 1, and at
+min_weight = 2.0 suppressed tetrahedra beside emitting ones, unnamed vertices and the planted weights at the threshold; the seam volume
+has counts on both sides of every seam of the plan's scan.  Nothing here touches a device."""
 import ctypes
 import math
 import os
@@ -349,6 +353,109 @@ def test_generic_rule_gives_one_or_two_triangles():
         assert len(tris) == {0: 0, 1: 1, 2: 2, 3: 1, 4: 0}[sum(inside)]
         for t in tris:
             assert all(inside[a] != inside[b] for a, b in t) and len(set(t)) == 3
+
+
+# ---- the array reference, which serves the grids the loops cannot ----
+FIELDS_OF_A_MESH = ("vertices", "lower", "upper", "v0", "v1", "t", "faces", "c0", "c1", "colors", "node", "kind", "cell", "tet", "case")
+
+
+def _pinned(f, loop, min_weight):
+    """mesh_ref_fast of the field, after holding every field of it to the bits of `loop`"""
+    fast = ref.mesh_ref_fast(f.wsum, f.dsum, f.origin, f.voxel_size, min_weight, f.csum)
+    assert len(fast.vertices) == len(loop.vertices) and len(fast.faces) == len(loop.faces)
+    assert np.array_equal(fast.faces, loop.faces)                         # as arrays, in order
+    for name in FIELDS_OF_A_MESH:
+        a, b = getattr(fast, name), getattr(loop, name)
+        assert a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes(), name
+    return fast
+
+
+@pytest.mark.parametrize("dims", ref.MESH_GRIDS)
+@pytest.mark.parametrize("name", ("sphere", "plane", "two_spheres", "slab"))
+def test_array_reference_is_the_loop_reference_bit_for_bit(name, dims):
+    """Every pair of the GPU's extraction test.  No bound: mesh_ref_fast applies mesh_ref's formulas to the same doubles in the same
+    order (t = v0 / (v0 - v1), lo + t (up - lo), c0 + t (c1 - c0), the positions as origin + index * voxel_size), so float64 fields are
+    compared as bytes, and so are the faces and the (node, kind), (cell, tetrahedron, case) that say where each row came from."""
+    f, m = _mesh(name, dims)
+    _pinned(f, m, 1.0)
+
+
+def _noise(dims, min_weight):
+    """the noise field, its loop reference and its census, computed once"""
+    key = ("noise", dims, min_weight)
+    if key not in _meshes:
+        f = ref.noise(dims)
+        _meshes[key] = (f, ref.mesh_ref(f.wsum, f.dsum, f.origin, f.voxel_size, min_weight, f.csum), ref.tet_census(f.wsum, min_weight, f.dsum))
+    return _meshes[key]
+
+
+@pytest.mark.parametrize("min_weight", (1.0, ref.THRESHOLD))
+@pytest.mark.parametrize("dims", ((9, 8, 5), (33, 17, 9)))
+def test_noise_field_reaches_every_row_of_the_rule_and_scattered_validity(dims, min_weight):
+    """Conditions on the inputs of the GPU test, taken from the loop reference (and the array reference pinned to it on the way): all
+    6 x 14 (tetrahedron, case) pairs among the tetrahedra with four valid corners -- once on the small grid at min_weight 1, three times
+    on the larger at both thresholds (at 2.0 the small grid has some fifty whole tetrahedra: no claim) -- all seven edge kinds, vertices
+    at t = 0 and t = 1 exactly, and at the threshold: cells where one tetrahedron emits and another with a crossed edge is suppressed by
+    an invalid corner, vertices that no face names, and the planted nodes: wsum = 2.0 owns a vertex on its +x edge, the float32 below
+    2.0 owns none."""
+    f, m, cen = _noise(dims, min_weight)
+    _pinned(f, m, min_weight)
+    counts = np.zeros((6, 16), np.int64)
+    for T in range(6):
+        counts[T] = np.bincount(cen.case[cen.whole[:, T], T], minlength=16)
+    least = int(counts[:, 1:15].min())
+    emitting = cen.whole & (cen.case > 0) & (cen.case < 15)
+    suppressed = ~cen.whole & cen.crossed
+    both = int((emitting.any(axis=1) & suppressed.any(axis=1)).sum())
+    unnamed = len(m.vertices) - len(np.unique(m.faces))
+    print(f"noise {dims} min_weight {min_weight}: V = {len(m.vertices)}, F = {len(m.faces)}, whole tetrahedra {int(cen.whole.sum())}, least (T, case) count "
+          f"{least}, t = 0: {int((m.t == 0).sum())}, t = 1: {int((m.t == 1).sum())}, cells emitting and suppressed {both}, unnamed vertices {unnamed}")
+    # the faces come from exactly the emitting tetrahedra, in their order
+    per_case = np.array([0] + [2 if bin(c).count("1") == 2 else 1 for c in range(1, 15)] + [0])
+    assert np.array_equal(np.bincount(m.tet * 16 + m.case, minlength=96).reshape(6, 16), counts * per_case[None])
+    if dims == (9, 8, 5):
+        assert min_weight != 1.0 or least >= 1
+    else:
+        assert least >= 3
+    assert sorted(set(m.kind.tolist())) == list(range(7))
+    assert bool((m.t == 0).any()) and bool((m.t == 1).any()) and bool(((m.t >= 0) & (m.t <= 1)).all())
+    assert int((f.dsum == 0).sum()) >= f.dsum.size // 20 and bool(np.signbit(f.dsum[f.dsum == 0]).any()) and not bool(np.signbit(f.dsum[f.dsum == 0]).all())
+    w = f.wsum.reshape(-1)
+    below = np.nextafter(np.float32(ref.THRESHOLD), np.float32(0.0))
+    assert bool((w[f.planted_valid[:, 0]] == np.float32(ref.THRESHOLD)).all()) and bool((w[f.planted_invalid[:, 0]] == below).all())
+    assert len(f.planted_valid) >= 4 and len(f.planted_invalid) >= 4 and bool((w[np.concatenate([f.planted_valid, f.planted_invalid])[:, 1]] >= ref.THRESHOLD).all())
+    owns = lambda n: int(((m.node == n) & (m.kind == 0)).sum())
+    assert all(owns(n) == 1 for n in f.planted_valid[:, 0])
+    if min_weight == 1.0:
+        assert ref.topology(m.faces).manifold and both == 0 and unnamed == 0 and all(owns(n) == 1 for n in f.planted_invalid[:, 0])
+    else:
+        assert both > 0 and unnamed > 0 and not any(int((m.node == n).sum()) for n in f.planted_invalid[:, 0])
+
+
+def _seam():
+    if "seam" not in _meshes:
+        f = ref.seam_field()
+        _meshes["seam"] = (f, ref.mesh_ref_fast(f.wsum, f.dsum, f.origin, f.voxel_size, 1.0, f.csum))
+    return _meshes["seam"]
+
+
+def test_seam_volume_puts_counts_on_both_sides_of_every_seam_of_the_scan():
+    """The layout the GPU test relies on (torch_tsdf.seam_layout asserts it; the GPU test calls the same function): more than 4 096
+    count workgroups; vertices and triangles in workgroups 255 | 256 and 511 | 512 (scan threads 63 | 64, 127 | 128), 4 095 | 4 096 (the
+    second trip of the chunk loop) and in the last workgroup that holds a whole cell; triangles beyond 4 096; 64 or more consecutive
+    workgroups without any; V and F below 400 000.  And where the noise is not, nothing: every count lies in a noisy layer or the one
+    below it."""
+    f, m = _seam()
+    v, t = ref.seam_layout(m)
+    layers = np.flatnonzero((v + t).reshape(ref.SEAM_DIMS[2], -1).sum(axis=1))
+    assert set(layers) <= set(ref.SEAM_LAYERS) | {k - 1 for k in ref.SEAM_LAYERS}
+    assert v[1023] > 0 and v[1024] > 0 and t[1023] > 0 and t[1024] > 0   # and the seam of waves 3 | 4
+    print(f"seam volume {ref.SEAM_DIMS}: V = {len(m.vertices)}, F = {len(m.faces)}, {len(v)} workgroups, {int((v > 0).sum())} with vertices, "
+          f"{int((t > 0).sum())} with triangles, the last with a cell {int(np.flatnonzero(t)[-1])}")
+    # the wave-seam volume: dense counts on either side of workgroups 255 | 256
+    g = ref.noise(ref.WAVE_SEAM_DIMS)
+    v, t = ref.workgroup_counts(ref.mesh_ref_fast(g.wsum, g.dsum, g.origin, g.voxel_size, 1.0), ref.WAVE_SEAM_DIMS)
+    assert len(v) > 256 and bool((v > 0).all()) and bool((t[:260] > 0).all())
 
 
 # ---- the scenes of the GPU tests ----

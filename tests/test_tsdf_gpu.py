@@ -12,9 +12,27 @@ Extraction, the fields of torch_tsdf through from_planes: V, F and the faces (ro
 reference's exactly and in order; vertices and colours lie within 4 * 2^-24 of the edge's extent (the larger modulus of the edge's two
 ends, per coordinate and per channel): the kernel evaluates in double and rounds once, 2^-24 of the value itself, which is at most the
 extent.  The topology checks of the CPU file are repeated on the GPU's own faces.
+Extraction without smoothness, against torch_tsdf.mesh_ref_fast (the array form of the reference, which tests/test_tsdf_cpu.py holds
+to the loop form bit for bit), with the same assertions and the same bar, plus 0 <= faces < V and the vertices at t = 0 or 1 equal to
+the float32 of their node:
+    noise at (9, 8, 5) and (33, 17, 9), min_weight 1.0 and 2.0   reaches every (tetrahedron, case) row of the table (the CPU file
+        counts them), nodes of value +0 and -0 beside negative ones, and at 2.0 scattered invalid nodes: tetrahedra suppressed beside
+        emitting ones in one cell, vertices no face names, nodes without crossings whose cells the face pass does not read, and
+        wsum == min_weight (valid) against the float32 below it (invalid)
+    noise at (65, 64, 17), 277 count workgroups, all with counts   reaches the plan scan's wave seam: threads 63 | 64, the prefix
+        over the wave totals in gsr_tsdf_block_scan<16>
+    the seam volume (128, 128, 66), 4 224 count workgroups         reaches the wave seams 63 | 64, 127 | 128 and 255 | 256 with empty
+        stretches between them, and the chunk seam 4 095 | 4 096: the second trip of the scan's loop and its 64-bit carry, for V
+        and for F, up to the last workgroup that holds a cell
+    not reached: the truncation of the bases to 32 bits, which needs more than 2^31 vertices.
+Each of these breaks of gsr_tsdf_scan_kernel, built apart and run once on the MI355X, fails exactly the tests named and none that
+this file had before them: without the `k < w` prefix in the scan kernel's block scan, the two seam tests; with the bases written
+without the carry, the chunk-seam test.  (Without `carry += tot` the totals themselves are 0, and every extraction test fails.)
 Measured on the MI355X (this file, printed by the tests):
     integration  largest error / bound over all cases: wsum 0.50, dsum 0.17, csum 0.49
     extraction   vertices 0.24, colours 0.25 of the bar (one rounding)
+    noise, seams vertices 0.248, colours 0.249 of the bar; the chunk-seam test takes 0.9 s, 3 to 4 ms of it in _extract (three
+                 extractions and the copies), the rest its reference
     end to end   every vertex within 0.860 voxel_size of the analytic sphere (the float64 reference: 0.860)
 """
 import ctypes
@@ -165,7 +183,7 @@ def _field(name, dims):
     return _cache[key]
 
 
-def _extract(f, color=True):
+def _extract(f, color=True, min_weight=1.0):
     """through from_planes and the entry points themselves, with canaries behind the three outputs -> (vertices, faces, colors) on the host"""
     import fused_tsdf as ft
     w, wb = _padded_plane(f.wsum)
@@ -178,7 +196,7 @@ def _extract(f, color=True):
     scratch = torch.empty(lib.gsr_tsdf_mesh_scratch_bytes(nodes), dtype=torch.uint8, device=DEV)
     plan = ft.MeshPlan()
     stream = torch.cuda.current_stream(DEV).cuda_stream
-    ft._run("gsr_tsdf_mesh_plan", ctypes.byref(vol._grid()), w.data_ptr(), d.data_ptr(), 1.0, scratch.data_ptr(), ctypes.byref(plan), stream)
+    ft._run("gsr_tsdf_mesh_plan", ctypes.byref(vol._grid()), w.data_ptr(), d.data_ptr(), min_weight, scratch.data_ptr(), ctypes.byref(plan), stream)
     V, F = int(plan.V), int(plan.F)
     vert = torch.full((3 * V + GUARD,), CANARY, dtype=torch.float32, device=DEV)
     cols = torch.full((3 * V + GUARD,), CANARY, dtype=torch.float32, device=DEV)
@@ -192,8 +210,8 @@ def _extract(f, color=True):
     torch.cuda.synchronize()
     assert _intact(vert) and _intact(cols) and bool((faces[3 * F:] == -77).all())
     assert all(torch.equal(a, b) for a, b in zip(before, (wb, db, cb)))   # the planes keep their bits
-    again = vol.extract_mesh()                                            # the Python surface: the same bits, twice
-    third = vol.extract_mesh()
+    again = vol.extract_mesh(min_weight=min_weight)                       # the Python surface: the same bits, twice
+    third = vol.extract_mesh(min_weight=min_weight)
     for x, y, z in zip(again, third, (vert[:3 * V].view(V, 3), faces[:3 * F].view(F, 3), cols[:3 * V].view(V, 3) if color else None)):
         assert (x is None and y is None and z is None) or (x.shape == z.shape and x.dtype == z.dtype and torch.equal(x, y) and _same(x, z))
     return vert[:3 * V].view(V, 3).cpu().numpy(), faces[:3 * F].view(F, 3).cpu().numpy(), (cols[:3 * V].view(V, 3).cpu().numpy() if color else None)
@@ -244,6 +262,79 @@ def test_a_volume_without_a_surface_gives_the_empty_mesh(name, dims):
         assert vol.extract_mesh()[1].shape == (0, 3)
         vol.dsum.zero_()    # exactly 0 counts as outside
         assert vol.extract_mesh()[0].shape == (0, 3)
+
+
+# ---- extraction without smoothness: every row of the rule, scattered validity, the scan's seams ----
+def _fast(key, make, min_weight):
+    """a field of torch_tsdf and its array reference (tests/test_tsdf_cpu.py holds that one to the loop reference, bit for bit)"""
+    key = ("fast", key, min_weight)
+    if key not in _cache:
+        f = make()
+        _cache[key] = (f, ref.mesh_ref_fast(f.wsum, f.dsum, f.origin, f.voxel_size, min_weight, f.csum))
+    return _cache[key]
+
+
+def _held_to_the_reference(label, m, v, faces, cols):
+    """the assertions of test_extraction_matches_the_reference_mesh, the indices' range, and the vertices that lie on a node"""
+    assert len(v) == len(m.vertices) and len(faces) == len(m.faces) and len(v) > 0 and len(faces) > 0
+    assert int(faces.min()) >= 0 and int(faces.max()) < len(v)
+    assert np.array_equal(ref.rotate_to_smallest(faces), ref.rotate_to_smallest(m.faces))   # exactly and in order
+    extent = np.maximum(np.abs(m.lower), np.abs(m.upper))
+    ev = np.abs(v.astype(np.float64) - m.vertices) / (4 * U * extent)
+    cext = np.maximum(np.abs(m.c0), np.abs(m.c1))
+    ec = np.abs(cols.astype(np.float64) - m.colors) / (4 * U * cext)
+    on_lower, on_upper = m.t == 0, m.t == 1
+    print(f"{label}: V = {len(v)}, F = {len(faces)}; largest error / bar: vertices {ev.max():.3f}, colours {ec.max():.3f}; on a node: "
+          f"{int(on_lower.sum())} + {int(on_upper.sum())} vertices")
+    assert float(ev.max()) <= 1.0 and float(ec.max()) <= 1.0
+    # t = 0 or 1: the value at one end is +-0, and the vertex is that node, rounded once
+    assert on_lower.any() and on_upper.any()
+    assert np.array_equal(v[on_lower], m.lower[on_lower].astype(np.float32)) and np.array_equal(v[on_upper], m.upper[on_upper].astype(np.float32))
+
+
+@pytest.mark.parametrize("min_weight", (1.0, ref.THRESHOLD))
+@pytest.mark.parametrize("dims", ((9, 8, 5), (33, 17, 9)))
+def test_extraction_of_noise_with_scattered_invalid_nodes(dims, min_weight):
+    """torch_tsdf.noise: values without smoothness, a tenth of them +-0, and at min_weight = 2.0 about half the nodes invalid at random,
+    with planted nodes of wsum = 2.0 (valid) and the float32 below it (invalid).  tests/test_tsdf_cpu.py shows what that reaches: all
+    6 x 14 rows of the kernel's table (three times and more on the larger grid, at either threshold), cells with emitting and suppressed
+    tetrahedra, vertices no face names.  _extract checks the canaries, the planes' bits and extract_mesh(min_weight=) against the entry
+    points."""
+    f, m = _fast(("noise", dims), lambda: ref.noise(dims), min_weight)
+    v, faces, cols = _extract(f, min_weight=min_weight)
+    _held_to_the_reference(f"noise {dims} min_weight {min_weight}", m, v, faces, cols)
+    if min_weight == 1.0:
+        assert ref.topology(faces).manifold
+    else:   # a weight of exactly min_weight is valid, the float32 below it is not
+        owned = lambda n: int((m.node == n).sum())
+        assert all(owned(n) > 0 for n in f.planted_valid[:, 0]) and not any(owned(n) for n in f.planted_invalid[:, 0])
+
+
+def test_extraction_across_the_wave_seam_of_the_plan_scan():
+    """noise over (65, 64, 17): 277 count workgroups, each with vertices, so scan threads 0..69 hold data and the prefix over the scan's
+    wave totals (`k < w` in gsr_tsdf_block_scan<16>) moves workgroups 256..276 by the whole of wave 0.  Reaches: the wave seam 63 | 64."""
+    f, m = _fast("wave seam", lambda: ref.noise(ref.WAVE_SEAM_DIMS), 1.0)
+    v, faces, cols = _extract(f)
+    _held_to_the_reference(f"noise {ref.WAVE_SEAM_DIMS}", m, v, faces, cols)
+
+
+def test_extraction_across_the_chunk_seam_of_the_plan_scan():
+    """torch_tsdf.seam_field, (128, 128, 66): 4 224 count workgroups, more than the 4 096 the scan takes in one trip.  Noise sits in
+    thin bands placed by n // 256 and the constant outside value everywhere else, so that (seam_layout asserts it on the reference
+    before anything runs) vertices and triangles lie in workgroups 255 | 256 and 511 | 512 (scan threads 63 | 64 and 127 | 128: two wave
+    seams), 1 023 | 1 024, 4 095 | 4 096 (the second trip: its bases are the 64-bit carry plus a prefix that starts again at 0) and in the
+    last workgroup with a whole cell, 4 159, with 384 empty workgroups in between where the prefix must stay flat.  Every vertex id and
+    face index behind a seam is wrong by a whole wave's or trip's total if the seam is: the faces are compared exactly and in order.
+    Not reached: the truncation of the bases to 32 bits ("emit is refused where they do not fit"), which needs more than 2^31
+    vertices."""
+    import time
+    f, m = _fast("seam", ref.seam_field, 1.0)
+    per_group_v, _ = ref.seam_layout(m)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    v, faces, cols = _extract(f)
+    wall = time.perf_counter() - t0
+    _held_to_the_reference(f"seam volume {ref.SEAM_DIMS} ({len(per_group_v)} workgroups, _extract took {1e3 * wall:.0f} ms)", m, v, faces, cols)
 
 
 # ---- end to end ----

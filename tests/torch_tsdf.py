@@ -2,7 +2,8 @@
 rule and sharing no table with the kernels: the triangles of a tetrahedron come from the generic rule (one corner apart: a triangle;
 two inside: a quadrilateral split by the header's sentence) and their orientation from a cross product against the gradient of the
 tetrahedron's linear interpolant.  Also the test scenes and fields, so that the CPU tests that qualify them and the GPU tests that use
-them look at the same numbers, and the topology checks both apply."""
+them look at the same numbers, and the topology checks both apply.  mesh_ref is the rule as three loops; mesh_ref_fast is the same
+rule in array operations, for volumes large enough to reach the seams of the plan's scan, with its table filled in from tet_triangles."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -207,7 +208,8 @@ def tet_triangles(corners, inside):
 def mesh_ref(wsum, dsum, origin, voxel_size, min_weight=1.0, csum=None):
     """wsum, dsum (NZ,NY,NX) float32, csum (3,NZ,NY,NX) or None -> a namespace: vertices (V,3) float64, colors (V,3) float64 or None,
     faces (F,3) int64, and per vertex: lower (V,3) and upper (V,3) the positions of its edge's nodes, v0, v1 (V,) their values, t (V,),
-    c0, c1 (V,3) their colours."""
+    c0, c1 (V,3) their colours, node, kind (V,) the lower node's index and the rank of the edge's kind; per face: cell (the index of the
+    cell's node), tet (0..5) and case (sum of 2^l over the inside path corners l) of the tetrahedron that emits it."""
     NZ, NY, NX = wsum.shape
     w, d = wsum.astype(np.float64), dsum.astype(np.float64)
     with np.errstate(invalid="ignore"):
@@ -230,8 +232,9 @@ def mesh_ref(wsum, dsum, origin, voxel_size, min_weight=1.0, csum=None):
                     t = v0 / (v0 - v1)
                     lo, up = org + np.array([i, j, k]) * vs, org + np.array([i1, j1, k1]) * vs
                     ids[(i, j, k, kind)] = len(rows)
-                    rows.append((lo + t * (up - lo), lo, up, v0, v1, t, None if col is None else col[:, k, j, i], None if col is None else col[:, k1, j1, i1]))
-    faces = []
+                    rows.append((lo + t * (up - lo), lo, up, v0, v1, t, None if col is None else col[:, k, j, i], None if col is None else col[:, k1, j1, i1],
+                                 i + NX * (j + NY * k), kind))
+    faces, emitters = [], []
     for k in range(NZ - 1):
         for j in range(NY - 1):
             for i in range(NX - 1):
@@ -241,6 +244,7 @@ def mesh_ref(wsum, dsum, origin, voxel_size, min_weight=1.0, csum=None):
                     if not all(valid[q] for q in at):
                         continue
                     for tri in tet_triangles(corners, [bool(inside[q]) for q in at]):
+                        emitters.append((i + NX * (j + NY * k), AXIS_ORDERS.index(axes), sum(int(inside[q]) << l for l, q in enumerate(at))))
                         face = []
                         for lo, hi in tri:
                             cl, ch = corners[lo], corners[hi]
@@ -250,10 +254,109 @@ def mesh_ref(wsum, dsum, origin, voxel_size, min_weight=1.0, csum=None):
     V = len(rows)
     col3 = lambda n: np.array([r[n] for r in rows], np.float64).reshape(V, 3)
     out = SimpleNamespace(vertices=col3(0), lower=col3(1), upper=col3(2), v0=np.array([r[3] for r in rows]), v1=np.array([r[4] for r in rows]),
-                          t=np.array([r[5] for r in rows]), faces=np.array(faces, np.int64).reshape(-1, 3), colors=None)
+                          t=np.array([r[5] for r in rows]), faces=np.array(faces, np.int64).reshape(-1, 3), colors=None,
+                          node=np.array([r[8] for r in rows], np.int64), kind=np.array([r[9] for r in rows], np.int64))
+    out.cell, out.tet, out.case = (np.array([e[n] for e in emitters], np.int64) for n in range(3))
     if col is not None:
         out.c0, out.c1 = col3(6), col3(7)
         out.colors = out.c0 + out.t[:, None] * (out.c1 - out.c0)
+    return out
+
+
+_rule = {}
+
+
+def _rule_tables():
+    """The generic rule laid out for array indexing, derived here from tet_triangles (and so from the cross product of _orientation),
+    never typed in -> count (6, 16): the triangles of tetrahedron T in case m; lo (6, 16, 2, 3, 3): the cell corner (dx, dy, dz) that
+    owns the edge of vertex s of triangle r; kind (6, 16, 2, 3): that edge's rank in KINDS."""
+    if not _rule:
+        count, lo, kind = np.zeros((6, 16), np.int64), np.zeros((6, 16, 2, 3, 3), np.int64), np.zeros((6, 16, 2, 3), np.int64)
+        for T, axes in enumerate(AXIS_ORDERS):
+            corners = [_corner(s, axes) for s in range(4)]
+            for m in range(16):
+                tris = tet_triangles(corners, [bool(m >> l & 1) for l in range(4)])
+                count[T, m] = len(tris)
+                for r, tri in enumerate(tris):
+                    for s, (a, b) in enumerate(tri):
+                        lo[T, m, r, s] = corners[a]
+                        kind[T, m, r, s] = KINDS.index(tuple(corners[b][x] - corners[a][x] for x in range(3)))
+        _rule.update(count=count, lo=lo, kind=kind)
+    return _rule["count"], _rule["lo"], _rule["kind"]
+
+
+def tet_census(wsum, min_weight, dsum):
+    """Every tetrahedron of every cell, in arrays -> a namespace over the cells in cell index order (x fastest, cells only: NX - 1 by
+    NY - 1 by NZ - 1): cell (cells,) the index of the cell's node, whole (cells, 6): all four corners valid, case (cells, 6): the sum of
+    2^l over the path corners l that are valid and inside, crossed (cells, 6): some edge of the tetrahedron has two valid ends on
+    different sides (it holds a vertex, whether or not the tetrahedron emits)."""
+    NZ, NY, NX = wsum.shape
+    with np.errstate(invalid="ignore"):
+        valid = wsum.astype(np.float64) >= float(np.float32(min_weight))
+    inside = valid & (dsum.astype(np.float64) / np.where(valid, wsum.astype(np.float64), 1.0) < 0)
+    k, j, i = (a.reshape(-1) for a in np.meshgrid(np.arange(NZ - 1), np.arange(NY - 1), np.arange(NX - 1), indexing="ij"))
+    cells = len(i)
+    whole, case, crossed = np.ones((cells, 6), bool), np.zeros((cells, 6), np.int64), np.zeros((cells, 6), bool)
+    for T, axes in enumerate(AXIS_ORDERS):
+        at = [(k + c[2], j + c[1], i + c[0]) for c in (_corner(s, axes) for s in range(4))]
+        for l in range(4):
+            whole[:, T] &= valid[at[l]]
+            case[:, T] |= inside[at[l]].astype(np.int64) << l
+            for l2 in range(l):
+                crossed[:, T] |= valid[at[l]] & valid[at[l2]] & (inside[at[l]] != inside[at[l2]])
+    return SimpleNamespace(cell=i + NX * (j + NY * k), whole=whole, case=case, crossed=crossed)
+
+
+def mesh_ref_fast(wsum, dsum, origin, voxel_size, min_weight=1.0, csum=None):
+    """mesh_ref in array operations, for grids its loops cannot serve: the same arguments, the same namespace, and in every float64 field
+    the same formula applied to the same doubles in the same order, so the bits are mesh_ref's (tests/test_tsdf_cpu.py holds it to that).
+    Order by construction: the crossings as a (nodes, 7) array read in row-major order are the vertices in (node, kind) order; the
+    triangle slots as a (cells, 6, 2) array read in row-major order are the faces in (cell, tetrahedron, triangle) order.  The rule
+    comes from _rule_tables, that is from tet_triangles."""
+    NZ, NY, NX = wsum.shape
+    nodes = NX * NY * NZ
+    w, d = wsum.astype(np.float64), dsum.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        valid = w >= float(np.float32(min_weight))
+    val = np.where(valid, d / np.where(valid, w, 1.0), np.nan)
+    inside = valid & (val < 0)
+    col = None if csum is None else np.where(valid[None], csum.astype(np.float64) / np.where(valid, w, 1.0)[None], np.nan)
+    org, vs = np.asarray(origin, np.float64), float(voxel_size)
+    # vertices: crossing[n, kind], and ids[n, kind] = how many crossings come before it
+    crossing = np.zeros((NZ, NY, NX, 7), bool)
+    for kind, (dx, dy, dz) in enumerate(KINDS):
+        low, up = (slice(0, NZ - dz), slice(0, NY - dy), slice(0, NX - dx)), (slice(dz, NZ), slice(dy, NY), slice(dx, NX))
+        crossing[low + (kind,)] = valid[low] & valid[up] & (inside[low] != inside[up])
+    crossing = crossing.reshape(nodes, 7)
+    ids = (np.cumsum(crossing.reshape(-1), dtype=np.int64).reshape(nodes, 7) - 1)
+    ids[~crossing] = -1
+    node, kind = np.nonzero(crossing)
+    ijk = np.stack([node % NX, (node // NX) % NY, node // (NX * NY)], axis=1)
+    ijk1 = ijk + np.array(KINDS, np.int64)[kind]
+    at0, at1 = (ijk[:, 2], ijk[:, 1], ijk[:, 0]), (ijk1[:, 2], ijk1[:, 1], ijk1[:, 0])
+    v0, v1 = val[at0], val[at1]
+    t = v0 / (v0 - v1)
+    lo, up = org[None, :] + ijk * vs, org[None, :] + ijk1 * vs
+    out = SimpleNamespace(vertices=lo + t[:, None] * (up - lo), lower=lo, upper=up, v0=v0, v1=v1, t=t, colors=None, node=node.astype(np.int64),
+                          kind=kind.astype(np.int64))
+    if col is not None:
+        out.c0, out.c1 = col[(slice(None),) + at0].T.copy(), col[(slice(None),) + at1].T.copy()
+        out.colors = out.c0 + out.t[:, None] * (out.c1 - out.c0)
+    # faces: the cells that emit at all, then every triangle slot of theirs
+    count, lo_corner, edge_kind = _rule_tables()
+    cen = tet_census(wsum, min_weight, dsum)
+    case = np.where(cen.whole, cen.case, 0)
+    live = (count[np.arange(6)[None, :], case] > 0).any(axis=1)
+    cell, case = cen.cell[live], case[live]
+    Tn = np.broadcast_to(np.arange(6)[None, :], case.shape)
+    emits = np.arange(2)[None, None, :] < count[Tn, case][:, :, None]                      # (cells, 6, 2)
+    c = lo_corner[Tn, case]                                                                # (cells, 6, 2, 3, 3)
+    owner = cell[:, None, None, None] + c[..., 0] + NX * (c[..., 1] + NY * c[..., 2])      # (cells, 6, 2, 3)
+    faces = ids[np.where(emits[..., None], owner, 0), edge_kind[Tn, case]][emits]
+    assert bool((faces >= 0).all())   # every vertex a triangle names is a crossing
+    out.faces = faces.reshape(-1, 3)
+    which = np.nonzero(emits)
+    out.cell, out.tet, out.case = cell[which[0]], which[1].astype(np.int64), case[which[0], which[1]]
     return out
 
 
@@ -354,6 +457,93 @@ def field(name, dims):
     if name == "invalid":
         w[:] = 0.0
     return SimpleNamespace(dims=dims, origin=origin, voxel_size=vs, wsum=w, dsum=dsum, csum=csum, value=value, gradient=gradient, spheres=spheres)
+
+
+NOISE_SEED = 5
+THRESHOLD = 2.0   # the min_weight at which the planted nodes of `noise` sit: wsum = 2.0 is valid, the float32 below it is not
+# the scan's seams (tests/test_tsdf_gpu.py): 4 224 count workgroups of 256 nodes, a z layer is 64 of them and a workgroup two y rows
+SEAM_DIMS, SEAM_ROWS, SEAM_LAYERS = (128, 128, 66), tuple(range(0, 8)) + tuple(range(120, 128)), (0, 1, 3, 4, 5, 7, 8, 15, 16, 62, 63, 64, 65)
+WAVE_SEAM_DIMS = (65, 64, 17)   # 277 workgroups, every one with counts: the scan's first wave seam under dense data
+
+
+def noise(dims, seed=NOISE_SEED, where=None):
+    """A field without any smoothness, for the tables and the validity logic -> the namespace of `field` (without value and gradient),
+    and planted_valid, planted_invalid: (4, 2) arrays of (node, its +x neighbour).
+    wsum = fp32(1 + 2 u), u uniform in [0, 1); value i.i.d. uniform in (-1, 1); dsum = fp32(w value); then 5 % of the nodes get
+    dsum = +0.0 and another 5 % dsum = -0.0: "outside", with their vertices on the node itself (t = 0 or 1).  At min_weight = THRESHOLD
+    about half the nodes are invalid, scattered.  Planted: four nodes with wsum = THRESHOLD exactly and four with the float32 just below
+    it, each with a +x neighbour of wsum >= THRESHOLD and dsum != 0 (none of them planted) and a value of the other sign: the edge between
+    them is a vertex exactly where the comparison is >=.
+    where (NZ, NY, NX) bool or None: outside it the field is the constant +0.3 of field("outside") -- valid, and no crossing between two
+    such nodes."""
+    vs = np.float32(0.1)
+    origin = np.array([-0.05 * (n - 1) + 0.013 for n in dims], np.float32) + np.float32(0.5)
+    x = node_positions(dims, origin, vs)
+    ext = 0.1 * (np.array(dims) - 1)
+    shape = dims[::-1]
+    rng = np.random.default_rng(seed)
+    w = (1.0 + 2.0 * rng.random(shape)).astype(np.float32)
+    value = rng.uniform(-1.0, 1.0, shape)
+    if where is not None:
+        value = np.where(where, value, 0.3)
+    dsum = (w.astype(np.float64) * value).astype(np.float32)
+    r = rng.random(shape)
+    if where is not None:
+        r = np.where(where, r, 1.0)
+    dsum[r < 0.05] = 0.0
+    dsum[(r >= 0.05) & (r < 0.10)] = -0.0
+    # the planted nodes, drawn from a shuffle of the nodes that have a +x neighbour
+    NX = dims[0]
+    wf, df = w.reshape(-1), dsum.reshape(-1)
+    used, planted = set(), []
+    noisy = np.ones(wf.size, bool) if where is None else where.reshape(-1)
+    for n in (int(n) for n in rng.permutation(wf.size)):
+        if len(planted) == 8:
+            break
+        if n % NX == NX - 1 or not noisy[n] or n in used or n + 1 in used or not wf[n + 1] >= np.float32(THRESHOLD) or df[n + 1] == 0:
+            continue
+        used.update((n, n + 1))   # neither a planted node nor its witness is touched again
+        wf[n] = np.float32(THRESHOLD) if len(planted) < 4 else np.nextafter(np.float32(THRESHOLD), np.float32(0.0))
+        df[n] = np.float32(float(wf[n]) * (-0.4 if df[n + 1] > 0 else 0.4))
+        planted.append((n, n + 1))
+    assert len(planted) == 8
+    rgb = np.stack([0.5 + 0.5 * np.sin(3.0 * x[:, 0] + 1.0), 0.5 + 0.5 * np.cos(2.0 * x[:, 1]), 0.2 + 0.6 * (x[:, 2] - x[:, 2].min()) / max(ext[2], 0.1)])
+    csum = (w.astype(np.float64)[None] * rgb.reshape((3,) + shape)).astype(np.float32)
+    return SimpleNamespace(dims=dims, origin=origin, voxel_size=vs, wsum=w, dsum=dsum, csum=csum, spheres=0,
+                           planted_valid=np.array(planted[:4], np.int64), planted_invalid=np.array(planted[4:], np.int64))
+
+
+def seam_field():
+    """noise in the rows SEAM_ROWS of the layers SEAM_LAYERS of SEAM_DIMS, the constant outside value elsewhere: counts on both sides of
+    workgroups 255 | 256 and 511 | 512 (threads 63 | 64 and 127 | 128 of the plan's scan), 1 023 | 1 024, 4 095 | 4 096 (its second trip,
+    with the carry) and in the last workgroup that holds a whole cell; nothing at all in the layers between."""
+    where = np.zeros(SEAM_DIMS[::-1], bool)
+    for k in SEAM_LAYERS:
+        where[k, list(SEAM_ROWS), :] = True
+    return noise(SEAM_DIMS, where=where)
+
+
+def workgroup_counts(m, dims, threads=256):
+    """-> (vertices, triangles) of the mesh `m` per count workgroup: node or cell index // threads"""
+    groups = (dims[0] * dims[1] * dims[2] + threads - 1) // threads
+    return np.bincount(m.node // threads, minlength=groups), np.bincount(m.cell // threads, minlength=groups)
+
+
+def seam_layout(m, dims=SEAM_DIMS):
+    """The conditions on the seam volume's reference mesh that make it a test of the scan, asserted; -> (vertices, triangles) per
+    workgroup.  A scan thread takes 4 totals, a wave 256, a trip 4 096."""
+    v, f = workgroup_counts(m, dims)
+    groups = len(v)
+    assert groups > 4096
+    last = (dims[0] * (dims[1] - 2 + dims[1] * (dims[2] - 2))) // 256   # the workgroup of the last cell's node
+    for g in (255, 256, 511, 512, 4095, 4096, last):
+        assert v[g] > 0 and f[g] > 0, (g, v[g], f[g])
+    assert last > 4096 and bool((f[4097:] > 0).any())                   # the carry feeds F as well as V
+    quiet = (v == 0) & (f == 0)
+    runs = np.diff(np.flatnonzero(np.diff(np.concatenate(([0], quiet.view(np.int8), [0])))))[::2]
+    assert runs.size and int(runs.max()) >= 64                          # a stretch of the prefix that must stay flat
+    assert len(m.vertices) < 400000 and len(m.faces) < 400000
+    return v, f
 
 
 # ---- the end-to-end scene: six cameras around an analytic sphere ----
