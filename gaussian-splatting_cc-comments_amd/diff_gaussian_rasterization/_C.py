@@ -16,6 +16,8 @@ from typing import NamedTuple, Optional
 
 import torch
 
+from . import _binding
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(os.path.dirname(_HERE), "libgsr_hip.so")   # nothing in the environment changes this: see use_library()
 _lib = None
@@ -125,6 +127,89 @@ def _dbg(debug):
     return int(debug) if (isinstance(debug, int) and not isinstance(debug, bool)) else int(bool(debug))
 
 
+# ---- the entry points this module calls, header by header (_binding.declare; tests/test_binding_cpu.py holds them to include/*.h) ----
+_str, _u32, _dbl, _pi64 = ctypes.c_char_p, ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(_i64)
+_pa, _pb, _pm = ctypes.POINTER(AuxArgs), ctypes.POINTER(BackwardArgs), ctypes.POINTER(CameraModelArgs)
+_PRE = [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 5 + [_f, _f, _i, _vp, _vp, _pi64, _vp, _i]        # gsr_forward_preprocess
+_PRE_LEAF = [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp, _pi64, _vp, _i]   # gsr_forward_preprocess_leaf
+_RENDER = [_i, _i64, _i, _i] + [_vp] * 7 + [_i]                                               # gsr_forward_render
+_STATE = [_i, _i64, _i, _i] + [_vp] * 3    # the sizes and the three state buffers in front of a replay pass's own arguments
+_binding.declare("gsr.h", {
+    "gsr_last_error": (_str, []), "gsr_version": (_str, []), "gsr_thread_release": (_i, []),
+    "gsr_geometry_bytes": (_sz, [_i]), "gsr_image_bytes": (_sz, [_i, _i]), "gsr_binning_bytes": (_sz, [_i, _i64, _i, _i]),
+    "gsr_backward_scratch_bytes": (_sz, [_i, _i64]),
+    "gsr_geometry_layout_of": (_i, [_i, ctypes.POINTER(GeometryLayout)]),
+    "gsr_image_layout_of": (_i, [_i, _i, ctypes.POINTER(ImageLayout)]),
+    "gsr_binning_layout_of": (_i, [_i, _i64, _i, _i, ctypes.POINTER(BinningLayout)]),
+    "gsr_get_higher_msb": (_u32, [_u32]),
+    "gsr_forward_preprocess": (_i, _PRE), "gsr_forward_render": (_i, _RENDER),
+    "gsr_backward": (_i, [_i, _i, _i, _i64, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 5 + [_f, _f] + [_vp] * 16 + [_i]),
+    "gsr_backward_blend": (_i, [_pb]), "gsr_backward_gaussians": (_i, [_pb, _i, _i, _i]),
+    "gsr_mark_visible": (_i, [_i] + [_vp] * 5),
+    "gsr_sh_grad_from_views": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "gsr_profile_begin": (_i, [_vp]), "gsr_profile_begin_only": (_i, [_vp, _str]),
+    "gsr_profile_end": (_i, [_vp, ctypes.POINTER(KernelTime), _i]),
+    # the leaf-parameter forward (fused_params.py), its one-call backward (bound, not called: the two stages serve every variant) and
+    # the optimiser step (its groups: fused_params.AdamGroup)
+    "gsr_forward_preprocess_leaf": (_i, _PRE_LEAF),
+    "gsr_backward_leaf": (_i, [_i, _i, _i, _i64, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f] + [_vp] * 15 + [_i]),
+    "gsr_adam_step": (_i, [_i, _vp, _dbl, _dbl, _dbl, _vp, _vp]),
+}, {"gsr_geometry_layout": GeometryLayout, "gsr_image_layout": ImageLayout, "gsr_binning_layout": BinningLayout,
+    "gsr_kernel_time": KernelTime, "gsr_backward_args": BackwardArgs})
+# depth and alpha maps, the screen-space filter, a camera model: the same calls with leading arguments
+_binding.declare("gsr_aux.h", {
+    "gsr_aux_bytes": (_sz, [_i64, _i, _i]), "gsr_aux_layout_of": (_i, [_i64, _i, _i, ctypes.POINTER(AuxLayout)]),
+    "gsr_forward_preprocess_aux": (_i, [_pa] + _PRE), "gsr_forward_preprocess_leaf_aux": (_i, [_pa] + _PRE_LEAF),
+    "gsr_forward_render_aux": (_i, [_pa] + _RENDER),
+    "gsr_backward_blend_aux": (_i, [_pb, _pa]), "gsr_backward_gaussians_aux": (_i, [_pb, _pa, _i, _i, _i]),
+}, {"gsr_aux_args": AuxArgs, "gsr_aux_layout": AuxLayout})
+_binding.declare("gsr_aa.h", {
+    "gsr_forward_preprocess_aa": (_i, [_i, _pa] + _PRE), "gsr_forward_preprocess_leaf_aa": (_i, [_i, _pa] + _PRE_LEAF),
+    "gsr_backward_gaussians_aa": (_i, [_pb, _i, _vp, _pa, _i, _i, _i]),
+})
+_binding.declare("gsr_camera_model.h", {
+    "gsr_forward_preprocess_cm": (_i, [_pm, _i, _pa] + _PRE), "gsr_forward_preprocess_leaf_cm": (_i, [_pm, _i, _pa] + _PRE_LEAF),
+    "gsr_backward_gaussians_cm": (_i, [_pb, _pm, _i, _vp, _pa, _i, _i, _i]),
+}, {"gsr_camera_model": CameraModelArgs})
+_binding.declare("gsr_cam.h", {
+    "gsr_cam_bytes": (_sz, [_i]),
+    "gsr_backward_gaussians_cam": (_i, [_pb, _i, _vp, _pa, ctypes.POINTER(CamArgs), _i, _i, _i]),
+}, {"gsr_cam_args": CamArgs})
+_binding.declare("gsr_cam_cm.h", {
+    "gsr_cam_cm_bytes": (_sz, [_i]),
+    "gsr_backward_gaussians_cam_cm": (_i, [_pb, _pm, _i, _vp, _pa, ctypes.POINTER(CamCmArgs), _i, _i, _i]),
+}, {"gsr_cam_cm_args": CamCmArgs})
+_binding.declare("gsr_absgrad.h", {
+    "gsr_backward_blend_abs": (_i, [_pb, _pa, _i]), "gsr_absgrad_fold": (_i, [_pb, ctypes.POINTER(AbsgradArgs), _i, _i]),
+}, {"gsr_absgrad_args": AbsgradArgs})
+# passes that replay the forward's state: blend-weight statistics, feature channels, the distortion and median-depth maps
+_binding.declare("gsr_contrib.h", {
+    "gsr_contrib_scratch_bytes": (_sz, [_i, _i64]), "gsr_contributions": (_i, _STATE + [_vp] * 6 + [_i]),
+})
+_binding.declare("gsr_features.h", {
+    "gsr_features_scratch_bytes": (_sz, [_i, _i64, _i]),
+    "gsr_features_forward": (_i, [_i, _i64, _i, _i, _i] + [_vp] * 6 + [_i]),
+    "gsr_features_backward": (_i, [_pb, _i, _vp, _vp, _vp, _vp, _i]),
+})
+_binding.declare("gsr_distortion.h", {
+    "gsr_distortion_state_bytes": (_sz, [_i, _i]), "gsr_distortion_forward": (_i, _STATE + [_vp] * 3 + [_i]),
+    "gsr_distortion_backward": (_i, [_pb, _vp, _vp]),
+})
+_binding.declare("gsr_median.h", {
+    "gsr_median_state_bytes": (_sz, [_i, _i]), "gsr_median_forward": (_i, _STATE + [_vp] * 6 + [_i]),
+    "gsr_median_backward": (_i, [_pb, _vp, _vp]),
+})
+# per-Gaussian normals, depth normals and the normal-consistency loss (fused_geometry.py)
+_binding.declare("gsr_normals.h", {
+    "gsr_gaussian_normals": (_i, [_i] + [_vp] * 4 + [_i, _vp, _vp]),
+    "gsr_gaussian_normals_backward": (_i, [_i] + [_vp] * 4 + [_i, _vp, _vp, _vp]),
+    "gsr_normals_scratch_bytes": (_sz, [_i, _i]),
+    "gsr_depth_normals": (_i, [_i, _i, _vp, _f, _f, _vp, _vp]),
+    "gsr_depth_normals_backward": (_i, [_i, _i, _vp, _f, _f, _vp, _vp, _vp]),
+    "gsr_normal_consistency_loss": (_i, [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+})
+
+
 def library_path():
     return _LIB_PATH
 
@@ -148,146 +233,12 @@ def lib():
         raise RuntimeError(
             f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the rasterizer.")
-    L = ctypes.CDLL(_LIB_PATH)
-    L.gsr_last_error.restype = ctypes.c_char_p
-    L.gsr_version.restype = ctypes.c_char_p
-    L.gsr_geometry_bytes.restype = _sz
-    L.gsr_geometry_bytes.argtypes = [_i]
-    L.gsr_image_bytes.restype = _sz
-    L.gsr_image_bytes.argtypes = [_i, _i]
-    L.gsr_binning_bytes.restype = _sz
-    L.gsr_binning_bytes.argtypes = [_i, _i64, _i, _i]
-    L.gsr_backward_scratch_bytes.restype = _sz
-    L.gsr_backward_scratch_bytes.argtypes = [_i, _i64]
-    L.gsr_geometry_layout_of.argtypes = [_i, ctypes.POINTER(GeometryLayout)]
-    L.gsr_image_layout_of.argtypes = [_i, _i, ctypes.POINTER(ImageLayout)]
-    L.gsr_binning_layout_of.argtypes = [_i, _i64, _i, _i, ctypes.POINTER(BinningLayout)]
-    L.gsr_get_higher_msb.restype = ctypes.c_uint32
-    L.gsr_get_higher_msb.argtypes = [ctypes.c_uint32]
-    L.gsr_forward_preprocess.restype = _i
-    L.gsr_forward_preprocess.argtypes = [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp,
-                                         _f, _f, _i, _vp, _vp, ctypes.POINTER(_i64), _vp, _i]
-    L.gsr_forward_render.restype = _i
-    L.gsr_forward_render.argtypes = [_i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]
-    L.gsr_backward.restype = _i
-    L.gsr_backward.argtypes = [_i, _i, _i, _i64, _i, _i] + [_vp] * 5 + [_f] + [_vp] * 5 + [_f, _f] + [_vp] * 16 + [_i]
-    L.gsr_mark_visible.restype = _i
-    L.gsr_mark_visible.argtypes = [_i, _vp, _vp, _vp, _vp, _vp]
-    L.gsr_sh_grad_from_views.restype = _i
-    L.gsr_sh_grad_from_views.argtypes = [_i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp]
-    L.gsr_backward_blend.restype = _i
-    L.gsr_backward_blend.argtypes = [ctypes.POINTER(BackwardArgs)]
-    L.gsr_backward_gaussians.restype = _i
-    L.gsr_backward_gaussians.argtypes = [ctypes.POINTER(BackwardArgs), _i, _i, _i]
-    L.gsr_thread_release.restype = _i
-    L.gsr_thread_release.argtypes = []
-    L.gsr_profile_begin.restype = _i
-    L.gsr_profile_begin.argtypes = [_vp]
-    L.gsr_profile_begin_only.restype = _i
-    L.gsr_profile_begin_only.argtypes = [_vp, ctypes.c_char_p]
-    L.gsr_profile_end.restype = _i
-    L.gsr_profile_end.argtypes = [_vp, ctypes.POINTER(KernelTime), _i]
-    # include/gsr.h: the leaf-parameter forward (fused_params.py) and the optimiser step (its groups: fused_params.AdamGroup)
-    leaf_pre = [_i] * 5 + [_vp] * 5 + [_f] + [_vp] * 4 + [_f, _f, _i, _vp, _vp, ctypes.POINTER(_i64), _vp, _i]
-    L.gsr_forward_preprocess_leaf.restype = _i
-    L.gsr_forward_preprocess_leaf.argtypes = leaf_pre
-    L.gsr_adam_step.restype = _i
-    L.gsr_adam_step.argtypes = [_i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _vp]
-    # include/gsr_aux.h (depth and alpha maps) and include/gsr_aa.h (screen-space filter): the same calls with leading arguments
-    pa, pb = ctypes.POINTER(AuxArgs), ctypes.POINTER(BackwardArgs)
-    L.gsr_aux_bytes.restype = _sz
-    L.gsr_aux_bytes.argtypes = [_i64, _i, _i]
-    L.gsr_aux_layout_of.restype = _i
-    L.gsr_aux_layout_of.argtypes = [_i64, _i, _i, ctypes.POINTER(AuxLayout)]
-    for name, argtypes in (("gsr_forward_preprocess_aux", [pa] + list(L.gsr_forward_preprocess.argtypes)),
-                           ("gsr_forward_preprocess_leaf_aux", [pa] + leaf_pre),
-                           ("gsr_forward_render_aux", [pa] + list(L.gsr_forward_render.argtypes)),
-                           ("gsr_backward_blend_aux", [pb, pa]),
-                           ("gsr_backward_gaussians_aux", [pb, pa, _i, _i, _i]),
-                           ("gsr_forward_preprocess_aa", [_i, pa] + list(L.gsr_forward_preprocess.argtypes)),
-                           ("gsr_forward_preprocess_leaf_aa", [_i, pa] + leaf_pre),
-                           ("gsr_backward_gaussians_aa", [pb, _i, _vp, pa, _i, _i, _i])):
-        getattr(L, name).restype = _i
-        getattr(L, name).argtypes = argtypes
-    # include/gsr_cam.h: camera gradients
-    L.gsr_cam_bytes.restype = _sz
-    L.gsr_cam_bytes.argtypes = [_i]
-    L.gsr_backward_gaussians_cam.restype = _i
-    L.gsr_backward_gaussians_cam.argtypes = [pb, _i, _vp, pa, ctypes.POINTER(CamArgs), _i, _i, _i]
-    # include/gsr_absgrad.h: absolute screen-space gradients
-    L.gsr_backward_blend_abs.restype = _i
-    L.gsr_backward_blend_abs.argtypes = [pb, pa, _i]
-    L.gsr_absgrad_fold.restype = _i
-    L.gsr_absgrad_fold.argtypes = [pb, ctypes.POINTER(AbsgradArgs), _i, _i]
-    # include/gsr_contrib.h: per-Gaussian blend-weight statistics
-    L.gsr_contrib_scratch_bytes.restype = _sz
-    L.gsr_contrib_scratch_bytes.argtypes = [_i, _i64]
-    L.gsr_contributions.restype = _i
-    L.gsr_contributions.argtypes = [_i, _i64, _i, _i] + [_vp] * 8 + [_vp, _i]
-    # include/gsr_features.h: K blended feature channels and their gradients
-    L.gsr_features_scratch_bytes.restype = _sz
-    L.gsr_features_scratch_bytes.argtypes = [_i, _i64, _i]
-    L.gsr_features_forward.restype = _i
-    L.gsr_features_forward.argtypes = [_i, _i64, _i, _i, _i] + [_vp] * 5 + [_vp, _i]
-    L.gsr_features_backward.restype = _i
-    L.gsr_features_backward.argtypes = [pb, _i, _vp, _vp, _vp, _vp, _i]
-    # include/gsr_distortion.h: the depth-distortion map of an aux-mode forward and its gradient.  (An older library loaded through
-    # use_library() for an A/B run has no such entry points: a call then fails with AttributeError, nothing stands in for them.)
-    if hasattr(L, "gsr_distortion_forward"):
-        L.gsr_distortion_state_bytes.restype = _sz
-        L.gsr_distortion_state_bytes.argtypes = [_i, _i]
-        L.gsr_distortion_forward.restype = _i
-        L.gsr_distortion_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 5 + [_vp, _i]
-        L.gsr_distortion_backward.restype = _i
-        L.gsr_distortion_backward.argtypes = [pb, _vp, _vp]
-    # include/gsr_median.h: the median-depth map, the per-pixel index maps and the median depth's gradient (the same holds for an
-    # older library)
-    if hasattr(L, "gsr_median_forward"):
-        L.gsr_median_state_bytes.restype = _sz
-        L.gsr_median_state_bytes.argtypes = [_i, _i]
-        L.gsr_median_forward.restype = _i
-        L.gsr_median_forward.argtypes = [_i, _i64, _i, _i] + [_vp] * 9 + [_i]
-        L.gsr_median_backward.restype = _i
-        L.gsr_median_backward.argtypes = [pb, _vp, _vp]
-    # include/gsr_normals.h: per-Gaussian normals, depth normals and the normal-consistency loss (fused_geometry.py; the same holds
-    # for an older library)
-    if hasattr(L, "gsr_gaussian_normals"):
-        L.gsr_gaussian_normals.restype = _i
-        L.gsr_gaussian_normals.argtypes = [_i] + [_vp] * 4 + [_i, _vp, _vp]
-        L.gsr_gaussian_normals_backward.restype = _i
-        L.gsr_gaussian_normals_backward.argtypes = [_i] + [_vp] * 4 + [_i, _vp, _vp, _vp]
-        L.gsr_normals_scratch_bytes.restype = _sz
-        L.gsr_normals_scratch_bytes.argtypes = [_i, _i]
-        L.gsr_depth_normals.restype = _i
-        L.gsr_depth_normals.argtypes = [_i, _i, _vp, _f, _f, _vp, _vp]
-        L.gsr_depth_normals_backward.restype = _i
-        L.gsr_depth_normals_backward.argtypes = [_i, _i, _vp, _f, _f, _vp, _vp, _vp]
-        L.gsr_normal_consistency_loss.restype = _i
-        L.gsr_normal_consistency_loss.argtypes = [_i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]
-    # include/gsr_camera_model.h: the *_aa calls with a camera model (the same holds for an older library)
-    if hasattr(L, "gsr_forward_preprocess_cm"):
-        pm = ctypes.POINTER(CameraModelArgs)
-        for name, argtypes in (("gsr_forward_preprocess_cm", [pm] + list(L.gsr_forward_preprocess_aa.argtypes)),
-                               ("gsr_forward_preprocess_leaf_cm", [pm] + list(L.gsr_forward_preprocess_leaf_aa.argtypes)),
-                               ("gsr_backward_gaussians_cm", [pb, pm, _i, _vp, pa, _i, _i, _i])):
-            getattr(L, name).restype = _i
-            getattr(L, name).argtypes = argtypes
-    # include/gsr_cam_cm.h: camera gradients under a camera model (the same holds for an older library)
-    if hasattr(L, "gsr_backward_gaussians_cam_cm"):
-        L.gsr_cam_cm_bytes.restype = _sz
-        L.gsr_cam_cm_bytes.argtypes = [_i]
-        L.gsr_backward_gaussians_cam_cm.restype = _i
-        L.gsr_backward_gaussians_cam_cm.argtypes = [pb, ctypes.POINTER(CameraModelArgs), _i, _vp, pa, ctypes.POINTER(CamCmArgs), _i, _i, _i]
-    _lib = L
-    return L
+    _lib = _binding.bind(ctypes.CDLL(_LIB_PATH))
+    return _lib
 
 
 _aux_lib = _aa_lib = lib   # every entry point is declared by lib()
-
-
-def _check(rc):
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {lib().gsr_last_error().decode()}")
+_check = _binding.check    # the status of an entry point: anything but 0 raises with the library's message
 
 
 def _ptr(t):

@@ -18,7 +18,8 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
+from diff_gaussian_rasterization._binding import ptr
 
 
 class BilagridArgs(ctypes.Structure):   # include/gsr_bilagrid.h gsr_bilagrid_args
@@ -28,31 +29,13 @@ class BilagridArgs(ctypes.Structure):   # include/gsr_bilagrid.h gsr_bilagrid_ar
 
 
 _WANT = ("grid", "image")
-
-
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_bilagrid_bound", False):
-        L.gsr_bilagrid_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_bilagrid_scratch_bytes.argtypes = [ctypes.c_int] * 5
-        L.gsr_bilagrid_slice.restype = ctypes.c_int
-        L.gsr_bilagrid_slice.argtypes = [ctypes.POINTER(BilagridArgs)]
-        L.gsr_bilagrid_slice_backward.restype = ctypes.c_int
-        L.gsr_bilagrid_slice_backward.argtypes = [ctypes.POINTER(BilagridArgs)]
-        L.gsr_bilagrid_tv_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_bilagrid_tv_scratch_bytes.argtypes = [ctypes.c_int] * 4
-        L.gsr_bilagrid_tv.restype = ctypes.c_int
-        L.gsr_bilagrid_tv.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 5
-        L._gsr_bilagrid_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_lib, _run = _binding.declare("gsr_bilagrid.h", {
+    "gsr_bilagrid_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "gsr_bilagrid_slice": (ctypes.c_int, [ctypes.POINTER(BilagridArgs)]),
+    "gsr_bilagrid_slice_backward": (ctypes.c_int, [ctypes.POINTER(BilagridArgs)]),
+    "gsr_bilagrid_tv_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "gsr_bilagrid_tv": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.c_void_p] * 5),
+}, {"gsr_bilagrid_args": BilagridArgs})
 
 
 def _check_grid_shape(name, shape):
@@ -117,7 +100,6 @@ def _slice_backward_raw(grid, image, grad_out, want):
         if "image" in want:
             grads["image"] = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         scratch = torch.empty(lib.gsr_bilagrid_scratch_bytes(H, W, L, GH, GW), dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
         a = BilagridArgs(H=H, W=W, L=L, GH=GH, GW=GW, grid=g.data_ptr(), img=x.data_ptr(), dL_dout=go.data_ptr(),
                          dL_dgrid=ptr(grads.get("grid")), dL_dimg=ptr(grads.get("image")), scratch=scratch.data_ptr(),
                          stream=torch.cuda.current_stream(dev).cuda_stream)

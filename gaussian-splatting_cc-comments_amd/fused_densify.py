@@ -21,11 +21,13 @@ never touched.  No atomics: every result is bitwise reproducible.  HIP tensors o
 plain torch and run wherever their tensors are.
 """
 import ctypes
+import functools
 import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+import fused_mcmc
+from diff_gaussian_rasterization import _binding
 from fused_mcmc import LEAF_NAMES
 
 KEEP, PRUNE, CLONE, SPLIT = 0, 1, 2, 3     # include/gsr_densify.h GSR_DENSIFY_KEEP ..
@@ -48,56 +50,20 @@ class DensifyArgs(ctypes.Structure):       # include/gsr_densify.h gsr_densify_a
                 ("src_of", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
 
 
-def bind(L):
-    """restype and argtypes of the three entry points on a loaded library"""
-    L.gsr_densify_scratch_bytes.restype = ctypes.c_size_t
-    L.gsr_densify_scratch_bytes.argtypes = [ctypes.c_int]
-    L.gsr_densify_plan.restype = ctypes.c_int
-    L.gsr_densify_plan.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4
-    L.gsr_densify_apply.restype = ctypes.c_int
-    L.gsr_densify_apply.argtypes = [ctypes.POINTER(DensifyArgs)]
-    return L
-
-
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_densify_bound", False):
-        bind(L)
-        L._gsr_densify_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
-
-
-def _leaf_groups(optimizer):
-    """The param groups of an optimiser that hold one row per Gaussian, by their `name` -> [(name, group)]"""
-    found = [(g.get("name"), g) for g in optimizer.param_groups if g.get("name") in LEAF_NAMES]
-    names = [n for n, _ in found]
-    if not found or len(set(names)) != len(names):
-        raise RuntimeError(f"the optimizer needs param groups named as the reference names them, each once (the names taken: {LEAF_NAMES}); "
-                           f"got {[g.get('name') for g in optimizer.param_groups]}")
-    for n, g in found:
-        if len(g["params"]) != 1:
-            raise RuntimeError(f"group {n!r}: one tensor per group, as the reference builds its optimiser; got {len(g['params'])}")
-    return found
+_lib, _run = _binding.declare("gsr_densify.h", {
+    "gsr_densify_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "gsr_densify_plan": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "gsr_densify_apply": (ctypes.c_int, [ctypes.POINTER(DensifyArgs)]),
+}, {"gsr_densify_group": DensifyGroup, "gsr_densify_args": DensifyArgs})
+bind = _binding.bind   # restype and argtypes on a library loaded by hand (tests load one beside the product's)
+# the leaf groups as fused_mcmc finds them, but any of them will do: a densification names the ones it needs itself
+_leaf_groups = functools.partial(fused_mcmc._leaf_groups, need=(), needs="param groups named as the reference names them, each once")
 
 
 def _rows(groups, xyz_index, scaling_index, rotation_index):
     """groups -> ([(param, exp_avg or None, exp_avg_sq or None)], names or None, (xyz, scaling, rotation) indices, -1 for none)"""
     if isinstance(groups, torch.optim.Optimizer):
-        found = _leaf_groups(groups)
-        rows = []
-        for _, g in found:
-            p = g["params"][0]
-            st = groups.state.get(p, {})
-            rows.append((p, st.get("exp_avg"), st.get("exp_avg_sq")))
-        names = [n for n, _ in found]
+        rows, names = fused_mcmc._optimizer_rows(groups, _leaf_groups(groups))
         return rows, names, tuple(names.index(n) if n in names else -1 for n in ("xyz", "scaling", "rotation"))
     rows = [tuple(r) for r in groups]
     if not rows or any(len(r) != 3 for r in rows):

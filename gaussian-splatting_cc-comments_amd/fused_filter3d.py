@@ -17,11 +17,13 @@ When the filter is recomputed stays with the training loop.  No floating-point a
 reproducible, the sweep under any permutation of the cameras.  HIP tensors only (no CPU fallback).
 """
 import ctypes
+import functools
 import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _C, _binding
+from diff_gaussian_rasterization._binding import ptr
 
 THREADS = 256            # include/gsr_filter3d.h GSR_FILTER3D_THREADS
 CAMERA_FLOATS = 20       # GSR_FILTER3D_CAMERA_FLOATS
@@ -33,56 +35,23 @@ class FilterCamera(ctypes.Structure):   # include/gsr_filter3d.h gsr_filter3d_ca
                 ("cy", ctypes.c_float), ("W", ctypes.c_float), ("H", ctypes.c_float), ("pad", ctypes.c_float * 2)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_filter3d_bound", False):
-        vp = ctypes.c_void_p
-        L.gsr_filter3d_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_filter3d_scratch_bytes.argtypes = [ctypes.c_int]
-        L.gsr_filter3d_compute.restype = ctypes.c_int
-        L.gsr_filter3d_compute.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
-        for name in ("gsr_filter3d_activate", "gsr_filter3d_bake"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [ctypes.c_int] + [vp] * 6
-        L.gsr_filter3d_activate_backward.restype = ctypes.c_int
-        L.gsr_filter3d_activate_backward.argtypes = [ctypes.c_int] + [vp] * 8
-        L.gsr_filter3d_reset_opacity.restype = ctypes.c_int
-        L.gsr_filter3d_reset_opacity.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_double, vp, vp, vp]
-        L._gsr_filter3d_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_i, _vp = ctypes.c_int, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_filter3d.h", {
+    "gsr_filter3d_scratch_bytes": (ctypes.c_size_t, [_i]),
+    "gsr_filter3d_compute": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "gsr_filter3d_activate": (_i, [_i] + [_vp] * 6),
+    "gsr_filter3d_bake": (_i, [_i] + [_vp] * 6),
+    "gsr_filter3d_activate_backward": (_i, [_i] + [_vp] * 8),
+    "gsr_filter3d_reset_opacity": (_i, [_i, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
+}, {"gsr_filter3d_camera": FilterCamera})
+_COLS = {"xyz": 3, "opacity": 1, "scaling": 3, "filter_3d": 1}
+_check_device = functools.partial(_binding.check_device, "3D-filter kernels")
 
 
 def _check(**named):
     """Every refusal of the tensors a call names (xyz (P,3), opacity (P,1), scaling (P,3), filter_3d (P,1)) but the device's, before the
     kernel library is touched.  -> P"""
-    cols = {"xyz": 3, "opacity": 1, "scaling": 3, "filter_3d": 1}
-    named = [(n, t) for n, t in named.items() if n in cols]
-    for n, t in named:
-        if not torch.is_tensor(t):
-            raise TypeError(f"{n} must be a tensor")
-    first = named[0][1]
-    P = int(first.shape[0]) if first.dim() else 0
-    for n, t in named:
-        if tuple(t.shape) != (P, cols[n]) or P < 1:
-            raise RuntimeError(f"{n} must be (P, {cols[n]}) with P >= 1 rows as {named[0][0]}; got {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be float32; got {t.dtype}")
-    return P
-
-
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("the tensors must be HIP (cuda) tensors on one device; the 3D-filter kernels have no CPU path")
-    return dev
+    return _binding.check_rows([(n, t) for n, t in named.items() if n in _COLS], _COLS)
 
 
 def _camera_scalars(cameras):
@@ -166,7 +135,6 @@ def _forward(entry, opacity, scaling, filter_3d, want):
         l, ls, f = (t.detach().contiguous() for t in (opacity, scaling, filter_3d))
         out = {k: torch.empty_like(t) for k, t in (("opacity", l), ("scaling", ls)) if k in want}
         if out:
-            ptr = lambda t: None if t is None else t.data_ptr()
             _run(entry, P, l.data_ptr(), ls.data_ptr(), f.data_ptr(), ptr(out.get("opacity")), ptr(out.get("scaling")),
                  torch.cuda.current_stream(dev).cuda_stream)
     return out
@@ -201,7 +169,6 @@ class _FilteredActivations(torch.autograd.Function):
             gs = None if g_scales is None else g_scales.to(torch.float32).contiguous()
             d_o = torch.empty_like(l) if need_o else None
             d_s = torch.empty_like(ls) if need_s else None
-            ptr = lambda t: None if t is None else t.data_ptr()
             _run("gsr_filter3d_activate_backward", P, l.data_ptr(), ls.data_ptr(), f.data_ptr(), ptr(go), ptr(gs), ptr(d_o), ptr(d_s),
                  torch.cuda.current_stream(dev).cuda_stream)
         return d_o, d_s, None
@@ -254,6 +221,6 @@ def reset_opacity(optimizer, filter_3d, max_opacity=0.01):
     dev = _check_device(*(t for t in (p, scaling, filter_3d, m, v) if t is not None))
     with torch.cuda.device(dev):
         ls, f = scaling.detach().contiguous(), filter_3d.detach().contiguous()
-        _run("gsr_filter3d_reset_opacity", P, p.data_ptr(), ls.data_ptr(), f.data_ptr(), float(max_opacity), None if m is None else m.data_ptr(),
-             None if v is None else v.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _run("gsr_filter3d_reset_opacity", P, p.data_ptr(), ls.data_ptr(), f.data_ptr(), float(max_opacity), ptr(m), ptr(v),
+             torch.cuda.current_stream(dev).cuda_stream)
     return p

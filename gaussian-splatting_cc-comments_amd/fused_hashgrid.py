@@ -23,7 +23,7 @@ import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
 
 MAX_LEVELS = 32          # include/gsr_hashgrid.h GSR_HASHGRID_MAX_LEVELS
 MAX_LOG2_SIZE = 24       # GSR_HASHGRID_MAX_LOG2_SIZE
@@ -38,60 +38,16 @@ class HashGridDesc(ctypes.Structure):
                 ("y_stride", ctypes.c_longlong), ("dy_stride", ctypes.c_longlong), ("dx_stride", ctypes.c_longlong)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_hashgrid_bound", False):
-        vp, dp = ctypes.c_void_p, ctypes.POINTER(HashGridDesc)
-        L.gsr_hashgrid_layout.restype = ctypes.c_int
-        L.gsr_hashgrid_layout.argtypes = [dp, vp, vp, vp]
-        L.gsr_hashgrid_level_scale.restype = ctypes.c_float
-        L.gsr_hashgrid_level_scale.argtypes = [dp, ctypes.c_int]
-        L.gsr_hashgrid_level_path.restype = ctypes.c_int
-        L.gsr_hashgrid_level_path.argtypes = [dp, ctypes.c_int]
-        L.gsr_hashgrid_scratch_bytes.restype = ctypes.c_int
-        L.gsr_hashgrid_scratch_bytes.argtypes = [dp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]
-        L.gsr_hashgrid_forward.restype = ctypes.c_int
-        L.gsr_hashgrid_forward.argtypes = [dp, vp, vp, vp, vp]
-        L.gsr_hashgrid_backward.restype = ctypes.c_int
-        L.gsr_hashgrid_backward.argtypes = [dp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.gsr_last_error.restype = ctypes.c_char_p
-        L._gsr_hashgrid_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
-
-
-def _check_int(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"{name} must be an int, got {v!r}")
-    if not lo <= v <= hi:
-        raise ValueError(f"{name} must lie in {lo}..{hi}; got {v}")
-
-
-def _check_matrix(name, t):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.dim() != 2:
-        raise RuntimeError(f"{name} must have two dimensions; got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32; got {t.dtype}")
-
-
-def _strided(t):
-    """A 2-D tensor whose second dimension is dense and whose rows do not overlap (else a contiguous copy)"""
-    dense = t.shape[1] <= 1 or t.stride(1) == 1
-    apart = t.shape[0] <= 1 or t.stride(0) >= max(1, t.shape[1])
-    return t if dense and apart else t.contiguous()
-
-
-def _stride0(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+_i, _vp, _sz, _dp = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(HashGridDesc)
+_lib, _run = _binding.declare("gsr_hashgrid.h", {
+    "gsr_hashgrid_layout": (_i, [_dp, _vp, _vp, _vp]),
+    "gsr_hashgrid_level_scale": (ctypes.c_float, [_dp, _i]),
+    "gsr_hashgrid_level_path": (_i, [_dp, _i]),
+    "gsr_hashgrid_scratch_bytes": (_i, [_dp, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]),
+    "gsr_hashgrid_forward": (_i, [_dp, _vp, _vp, _vp, _vp]),
+    "gsr_hashgrid_backward": (_i, [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}, {"gsr_hashgrid_desc": HashGridDesc})
+_check_int, _check_matrix, _strided, _stride0 = _binding.check_int, _binding.check_matrix, _binding.strided, _binding.stride0
 
 
 def check_config(in_dim, levels, features, log2_hashmap_size, base_resolution, per_level_scale):

@@ -19,50 +19,30 @@ backward (tools/knn_bench.py: 3 to 10 times the speed of the indexing expression
 fallback).
 """
 import ctypes
+import functools
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _C, _binding
 
 MAX_K = 32   # include/gsr_knn.h GSR_KNN_MAX_K
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_knn_graph_bound", False):
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        L.gsr_knn_search_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_knn_search_scratch_bytes.argtypes = [i, i]
-        L.gsr_knn_search.restype = i
-        L.gsr_knn_search.argtypes = [i, vp, i, vp, i, vp, vp, vp, vp]
-        L.gsr_knn_graph_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_knn_graph_scratch_bytes.argtypes = [i, i]
-        L.gsr_knn_graph_build.restype = i
-        L.gsr_knn_graph_build.argtypes = [i, vp, i, vp, vp, vp, vp, vp]
-        L.gsr_knn_gather.restype = i
-        L.gsr_knn_gather.argtypes = [i, i, i, vp, vp, vp, vp]
-        L.gsr_knn_gather_backward.restype = i
-        L.gsr_knn_gather_backward.argtypes = [i, i, vp, vp, vp, vp, vp]
-        L._gsr_knn_graph_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_i, _vp = ctypes.c_int, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_knn.h", {
+    "gsr_knn_search_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
+    "gsr_knn_search": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "gsr_knn_graph_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
+    "gsr_knn_graph_build": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_knn_gather": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gsr_knn_gather_backward": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+})
+_check_device = functools.partial(_binding.check_device, "neighbour-graph kernels")
 
 
 def _check_cloud(name, t):
     """A (rows, 3) float32 tensor, any strides -> rows"""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise RuntimeError(f"{name} must have dimensions (rows, 3); got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32; got {t.dtype}")
+    _binding.check_matrix(name, t, "dimensions (rows, 3)", 3)
     return int(t.shape[0])
 
 
@@ -87,13 +67,6 @@ def _check_idx(idx, num_points, check):
     return int(idx.shape[0]), int(idx.shape[1])
 
 
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("the tensors must be HIP (cuda) tensors on one device; the neighbour-graph kernels have no CPU path")
-    return dev
-
-
 @torch.no_grad()
 def knn(points, K, queries=None):
     """The K nearest points of every query -> (dist2 (Q, K) float32, idx (Q, K) int32).
@@ -105,10 +78,7 @@ def knn(points, K, queries=None):
     Inputs are detached and may have any strides; the work runs on the tensors' device and the current stream."""
     P = _check_cloud("points", points)
     Q = P if queries is None else _check_cloud("queries", queries)
-    if isinstance(K, bool) or not isinstance(K, int):
-        raise TypeError(f"K must be an int, got {K!r}")
-    if not 1 <= K <= MAX_K:
-        raise ValueError(f"K must lie in 1..{MAX_K}; got {K}")
+    _binding.check_int("K", K, 1, MAX_K)
     dev = _check_device(*((points,) if queries is None else (points, queries)))
     if Q * K >= 2 ** 31:
         raise RuntimeError(f"Q * K = {Q * K} entries; the kernels index them with 31 bits")

@@ -12,18 +12,14 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
+from diff_gaussian_rasterization._binding import ptr
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_loss_bound", False):
-        L.gsr_loss_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_loss_scratch_bytes.argtypes = [ctypes.c_int] * 3
-        L.gsr_l1_ssim_loss.restype = ctypes.c_int
-        L.gsr_l1_ssim_loss.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_float] + [ctypes.c_void_p] * 4
-        L._gsr_loss_bound = True
-    return L
+_lib, _run = _binding.declare("gsr.h", {
+    "gsr_loss_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "gsr_l1_ssim_loss": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2 + [ctypes.c_float] + [ctypes.c_void_p] * 4),
+})
 
 
 def l1_ssim_loss_and_grad(image, gt, lambda_dssim=0.2, want_grad=True):
@@ -41,11 +37,8 @@ def l1_ssim_loss_and_grad(image, gt, lambda_dssim=0.2, want_grad=True):
         vals = torch.empty(3, dtype=torch.float32, device=dev)
         grad = torch.empty((C, H, W), dtype=torch.float32, device=dev) if want_grad else None
         scratch = torch.empty(L.gsr_loss_scratch_bytes(C, H, W), dtype=torch.uint8, device=dev)
-        rc = L.gsr_l1_ssim_loss(C, H, W, img.data_ptr(), g.data_ptr(), float(lambda_dssim), vals.data_ptr(),
-                                grad.data_ptr() if want_grad else None, scratch.data_ptr(),
-                                torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+        _run("gsr_l1_ssim_loss", C, H, W, img.data_ptr(), g.data_ptr(), float(lambda_dssim), vals.data_ptr(),
+             grad.data_ptr() if want_grad else None, scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         scratch.record_stream(torch.cuda.current_stream(dev))
     return vals, grad
 
@@ -96,15 +89,10 @@ class LossExtArgs(ctypes.Structure):   # include/gsr_loss_ext.h gsr_loss_ext_arg
 _WANT = ("image", "exposure", "invdepth")
 
 
-def _lib_ext():
-    L = _C.lib()
-    if not getattr(L, "_gsr_loss_ext_bound", False):
-        L.gsr_loss_ext_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_loss_ext_scratch_bytes.argtypes = [ctypes.c_int] * 3
-        L.gsr_l1_ssim_loss_ext.restype = ctypes.c_int
-        L.gsr_l1_ssim_loss_ext.argtypes = [ctypes.POINTER(LossExtArgs)]
-        L._gsr_loss_ext_bound = True
-    return L
+_lib_ext = _binding.declare("gsr_loss_ext.h", {
+    "gsr_loss_ext_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "gsr_l1_ssim_loss_ext": (ctypes.c_int, [ctypes.POINTER(LossExtArgs)]),
+}, {"gsr_loss_ext_args": LossExtArgs})[0]
 
 
 def _check_training_loss(image, gt, mask, exposure, invdepth, invdepth_prior, invdepth_mask, invdepth_weight, want):
@@ -180,14 +168,11 @@ def training_loss_and_grads(image, gt, lambda_dssim=0.2, *, mask=None, exposure=
         if "invdepth" in want and d is not None:
             grads["invdepth"] = torch.empty(tuple(invdepth.shape), dtype=torch.float32, device=dev)
         scratch = torch.empty(L.gsr_loss_ext_scratch_bytes(C, H, W), dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
         a = LossExtArgs(C=C, H=H, W=W, lambda_dssim=float(lambda_dssim), img=ptr(img), gt=ptr(g), mask=ptr(m), exposure=ptr(E),
                         invdepth=ptr(d), invdepth_prior=ptr(dp), invdepth_mask=ptr(dk), invdepth_weight=float(invdepth_weight),
                         vals=ptr(vals), dL_dimg=ptr(grads.get("image")), dL_dexposure=ptr(grads.get("exposure")),
                         dL_dinvdepth=ptr(grads.get("invdepth")), scratch=ptr(scratch), stream=torch.cuda.current_stream(dev).cuda_stream)
-        rc = L.gsr_l1_ssim_loss_ext(ctypes.byref(a))
-        if rc != 0:
-            raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+        _run("gsr_l1_ssim_loss_ext", ctypes.byref(a))
         scratch.record_stream(torch.cuda.current_stream(dev))
     return vals, grads
 

@@ -20,7 +20,8 @@ import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
+from diff_gaussian_rasterization._binding import ptr
 
 MAX_GROUPS = 8               # include/gsr.h GSR_ADAM_MAX_GROUPS
 MAX_RATIO = 51               # include/gsr_mcmc.h GSR_MCMC_MAX_RATIO
@@ -41,43 +42,21 @@ class RelocateArgs(ctypes.Structure):   # include/gsr_mcmc.h gsr_mcmc_relocate_a
                 ("stream", ctypes.c_void_p)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_mcmc_bound", False):
-        L.gsr_mcmc_noise.restype = ctypes.c_int
-        L.gsr_mcmc_noise.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_float, ctypes.c_void_p]
-        L.gsr_mcmc_relocate.restype = ctypes.c_int
-        L.gsr_mcmc_relocate.argtypes = [ctypes.POINTER(RelocateArgs)]
-        L.gsr_mcmc_regularizer_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_mcmc_regularizer_scratch_bytes.argtypes = [ctypes.c_int]
-        L.gsr_mcmc_regularizer.restype = ctypes.c_int
-        L.gsr_mcmc_regularizer.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float] + [ctypes.c_void_p] * 5
-        L._gsr_mcmc_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_mcmc.h", {
+    "gsr_mcmc_noise": (_i, [_i] + [_vp] * 5 + [_f, _vp]),
+    "gsr_mcmc_relocate": (_i, [ctypes.POINTER(RelocateArgs)]),
+    "gsr_mcmc_regularizer_scratch_bytes": (ctypes.c_size_t, [_i]),
+    "gsr_mcmc_regularizer": (_i, [_i, _vp, _vp, _f, _f] + [_vp] * 5),
+}, {"gsr_mcmc_group": McmcGroup, "gsr_mcmc_relocate_args": RelocateArgs})
+_COLS = {"xyz": 3, "opacity": 1, "scaling": 3, "rotation": 4, "noise": 3}
 
 
 def _check_leaves(xyz=None, opacity=None, scaling=None, rotation=None, noise=None):
     """Every refusal of the leaf tensors a call names, before the kernel library is touched.  -> P"""
     named = [(n, t) for n, t in (("xyz", xyz), ("opacity", opacity), ("scaling", scaling), ("rotation", rotation), ("noise", noise))
              if t is not None]
-    for n, t in named:
-        if not torch.is_tensor(t):
-            raise TypeError(f"{n} must be a tensor")
-    P = int(named[0][1].shape[0]) if named[0][1].dim() else 0
-    want = {"xyz": (P, 3), "opacity": (P, 1), "scaling": (P, 3), "rotation": (P, 4), "noise": (P, 3)}
-    for n, t in named:
-        if tuple(t.shape) != want[n] or P < 1:
-            raise RuntimeError(f"{n} must be (P, {want[n][1]}) with P >= 1 rows as {named[0][0]}; got {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be float32; got {t.dtype}")
+    P = _binding.check_rows(named, _COLS)
     dev = named[0][1].device
     if dev.type != "cuda" or any(t.device != dev for _, t in named):
         raise RuntimeError("the leaves must be HIP (cuda) tensors on one device; the MCMC kernels have no CPU path")
@@ -102,12 +81,13 @@ def inject_noise(xyz, opacity, scaling, rotation, scaler, noise=None, generator=
     return xyz
 
 
-def _leaf_groups(optimizer):
-    """The param groups of an optimiser that hold one row per Gaussian, by their `name` -> [(name, group)]"""
+def _leaf_groups(optimizer, need=("opacity", "scaling"), needs="one param group named 'opacity' and one named 'scaling'"):
+    """The param groups of an optimiser that hold one row per Gaussian, by their `name` -> [(name, group)].  need: the names that must
+    be among them; needs: how the refusal words that (fused_densify asks for at least one group, whichever)."""
     found = [(g.get("name"), g) for g in optimizer.param_groups if g.get("name") in LEAF_NAMES]
     names = [n for n, _ in found]
-    if "opacity" not in names or "scaling" not in names or len(set(names)) != len(names):
-        raise RuntimeError(f"the optimizer needs one param group named 'opacity' and one named 'scaling' (the names taken: {LEAF_NAMES}); "
+    if not found or any(n not in names for n in need) or len(set(names)) != len(names):
+        raise RuntimeError(f"the optimizer needs {needs} (the names taken: {LEAF_NAMES}); "
                            f"got {[g.get('name') for g in optimizer.param_groups]}")
     for n, g in found:
         if len(g["params"]) != 1:
@@ -115,16 +95,20 @@ def _leaf_groups(optimizer):
     return found
 
 
+def _optimizer_rows(optimizer, found):
+    """The groups _leaf_groups found -> ([(param, exp_avg or None, exp_avg_sq or None)], their names)"""
+    rows = []
+    for _, g in found:
+        p = g["params"][0]
+        st = optimizer.state.get(p, {})
+        rows.append((p, st.get("exp_avg"), st.get("exp_avg_sq")))
+    return rows, [n for n, _ in found]
+
+
 def _rows(groups, opacity_index, scaling_index):
     """groups -> ([(param, exp_avg or None, exp_avg_sq or None)], opacity index, scaling index)"""
     if isinstance(groups, torch.optim.Optimizer):
-        found = _leaf_groups(groups)
-        rows = []
-        for _, g in found:
-            p = g["params"][0]
-            st = groups.state.get(p, {})
-            rows.append((p, st.get("exp_avg"), st.get("exp_avg_sq")))
-        names = [n for n, _ in found]
+        rows, names = _optimizer_rows(groups, _leaf_groups(groups))
         return rows, names.index("opacity"), names.index("scaling")
     rows = [tuple(r) for r in groups]
     if any(len(r) != 3 for r in rows):
@@ -232,7 +216,6 @@ def regularizer_and_grads(opacity, scaling, opacity_reg=0.01, scale_reg=0.01, wa
         val = torch.empty(1, dtype=torch.float32, device=dev)
         grads = {k: torch.empty_like(t) for k, t in (("opacity", o), ("scaling", s)) if k in want}
         scratch = torch.empty(lib.gsr_mcmc_regularizer_scratch_bytes(P), dtype=torch.uint8, device=dev)
-        ptr = lambda t: None if t is None else t.data_ptr()
         _run("gsr_mcmc_regularizer", P, o.data_ptr(), s.data_ptr(), float(opacity_reg), float(scale_reg), val.data_ptr(),
              ptr(grads.get("opacity")), ptr(grads.get("scaling")), scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         scratch.record_stream(torch.cuda.current_stream(dev))

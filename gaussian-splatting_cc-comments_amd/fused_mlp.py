@@ -20,7 +20,7 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
 
 MAX_LAYERS = 5      # include/gsr_mlp.h GSR_MLP_MAX_LAYERS
 MAX_WIDTH = 128     # GSR_MLP_MAX_WIDTH
@@ -39,33 +39,15 @@ class MlpDesc(ctypes.Structure):
                 ("max_workgroups", ctypes.c_int)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_mlp_bound", False):
-        vp, dp = ctypes.c_void_p, ctypes.POINTER(MlpDesc)
-        L.gsr_mlp_tile_rows.restype = ctypes.c_int
-        L.gsr_mlp_tile_rows.argtypes = [dp]
-        L.gsr_mlp_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_mlp_scratch_bytes.argtypes = [dp]
-        L.gsr_mlp_forward.restype = ctypes.c_int
-        L.gsr_mlp_forward.argtypes = [dp, vp, vp, vp, vp, vp, vp]
-        L.gsr_mlp_backward.restype = ctypes.c_int
-        L.gsr_mlp_backward.argtypes = [dp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L._gsr_mlp_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
-
-
-def _pointers(tensors):
-    """A list of tensors (or None) -> a C array of their addresses"""
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+_vp, _dp = ctypes.c_void_p, ctypes.POINTER(MlpDesc)
+_lib, _run = _binding.declare("gsr_mlp.h", {
+    "gsr_mlp_tile_rows": (ctypes.c_int, [_dp]),
+    "gsr_mlp_scratch_bytes": (ctypes.c_size_t, [_dp]),
+    "gsr_mlp_forward": (ctypes.c_int, [_dp] + [_vp] * 6),
+    "gsr_mlp_backward": (ctypes.c_int, [_dp] + [_vp] * 9),
+}, {"gsr_mlp_desc": MlpDesc})
+_pointers, _check_int, _check_matrix, _strided, _stride0 = (
+    _binding.pointers, _binding.check_int, _binding.check_matrix, _binding.strided, _binding.stride0)
 
 
 def _choice(name, v, table):
@@ -74,33 +56,6 @@ def _choice(name, v, table):
     if v not in table:
         raise ValueError(f"{name} must be one of {tuple(table)}, got {v!r}")
     return table[v]
-
-
-def _check_int(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"{name} must be an int, got {v!r}")
-    if not lo <= v <= hi:
-        raise ValueError(f"{name} must lie in {lo}..{hi}; got {v}")
-
-
-def _check_matrix(name, t):
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.dim() != 2:
-        raise RuntimeError(f"{name} must have two dimensions; got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32; got {t.dtype}")
-
-
-def _strided(t):
-    """A 2-D tensor whose second dimension is dense and whose rows do not overlap (else a contiguous copy)"""
-    dense = t.shape[1] <= 1 or t.stride(1) == 1
-    apart = t.shape[0] <= 1 or t.stride(0) >= max(1, t.shape[1])
-    return t if dense and apart else t.contiguous()
-
-
-def _stride0(t):
-    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
 
 
 def check(x, weights, biases, activation, output_activation, frequencies, layout, out_layout, max_workgroups=0):

@@ -18,7 +18,7 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import OPTION_INPUTS, _C, after_backward, after_render, before_backward, camera_positions
+from diff_gaussian_rasterization import OPTION_INPUTS, _binding, _C, after_backward, after_render, before_backward, camera_positions
 
 _vp, _i64, _d = ctypes.c_void_p, ctypes.c_int64, ctypes.c_double
 ADAM_MAX_GROUPS = 8
@@ -29,6 +29,8 @@ class AdamGroup(ctypes.Structure):
     _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("numel", _i64), ("step", _i64),
                 ("lr", _d), ("row", ctypes.c_int32)]
 
+
+_binding.declare("gsr.h", {}, {"gsr_adam_group": AdamGroup})   # the mirror alone: _C declares gsr_adam_step with the rest of gsr.h
 
 def _leaf_forward(mode, xyz, features_dc, features_rest, opacity, scaling, rotation, raster_settings, antialiasing, camera_model=None):
     st = raster_settings

@@ -24,23 +24,17 @@ import ctypes
 import torch
 
 import fused_knn
-from diff_gaussian_rasterization import _C
-from fused_knn import MAX_K, NeighborGraph, _check_cloud, _check_device, _check_idx, _run
+from diff_gaussian_rasterization import _C, _binding
+from fused_knn import MAX_K, NeighborGraph, _check_cloud, _check_device, _check_idx
 
 GRADS = ("xyz", "rotation")
 LANES = 8   # csrc/rigidity.hip GSR_RIG_LANES: the lanes that share a point's edges
 
-
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_rigidity_bound", False):
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.gsr_rigidity_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_rigidity_scratch_bytes.argtypes = [i, i]
-        L.gsr_rigidity_loss.restype = i
-        L.gsr_rigidity_loss.argtypes = [i, i] + [vp] * 9 + [f, f, f] + [vp] * 5
-        L._gsr_rigidity_bound = True
-    return L
+_i, _f, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_rigidity.h", {   # the graph a state holds is built through fused_knn's table
+    "gsr_rigidity_scratch_bytes": (ctypes.c_size_t, [_i, _i]),
+    "gsr_rigidity_loss": (_i, [_i, _i] + [_vp] * 9 + [_f, _f, _f] + [_vp] * 5),
+}, needs=("gsr_knn.h",))
 
 
 def _check_table(name, t, shape, dtype=torch.float32):
@@ -53,21 +47,13 @@ def _check_table(name, t, shape, dtype=torch.float32):
 
 
 def _check_rotation(rotation, P):
-    if not torch.is_tensor(rotation):
-        raise TypeError("rotation must be a tensor")
-    if rotation.dim() != 2 or rotation.shape[1] != 4:
-        raise RuntimeError(f"rotation must have dimensions (rows, 4); got {tuple(rotation.shape)}")
-    if rotation.dtype != torch.float32:
-        raise RuntimeError(f"rotation must be float32; got {rotation.dtype}")
+    _binding.check_matrix("rotation", rotation, "dimensions (rows, 4)", 4)
     if rotation.shape[0] != P:
         raise RuntimeError(f"xyz has {P} rows; rotation has {rotation.shape[0]}")
 
 
 def _check_K(K):
-    if isinstance(K, bool) or not isinstance(K, int):
-        raise TypeError(f"K must be an int, got {K!r}")
-    if not 1 <= K <= MAX_K:
-        raise ValueError(f"K must lie in 1..{MAX_K}; got {K}")
+    _binding.check_int("K", K, 1, MAX_K)
 
 
 def tables_from_search(xyz, rotation, dist2, ids, weight_lambda=2000.0, rows=None):

@@ -14,11 +14,12 @@ Everything is evaluated in double from the float32 leaves and rounded once; the 
 every result is bitwise reproducible.  HIP tensors only (no CPU fallback).
 """
 import ctypes
+import functools
 import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
 
 THREADS = 256      # include/gsr_slice4d.h GSR_SLICE4D_THREADS
 MAX_N = 3          # GSR_HARMONIC_MAX_N
@@ -27,61 +28,26 @@ LEAVES = ("xyz", "t", "scaling", "scaling_t", "rotation", "rotation_r", "opacity
 _COLS = {"xyz": 3, "t": 1, "scaling": 3, "scaling_t": 1, "rotation": 4, "rotation_r": 4, "opacity": 1}
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_slice4d_bound", False):
-        vp, dbl = ctypes.c_void_p, ctypes.c_double
-        L.gsr_slice4d_forward.restype = ctypes.c_int
-        L.gsr_slice4d_forward.argtypes = [ctypes.c_int] + [vp] * 7 + [dbl] * 3 + [vp] * 5
-        L.gsr_slice4d_backward.restype = ctypes.c_int
-        L.gsr_slice4d_backward.argtypes = [ctypes.c_int] + [vp] * 7 + [dbl] * 3 + [vp] * 12
-        L.gsr_harmonic_features.restype = ctypes.c_int
-        L.gsr_harmonic_features.argtypes = [ctypes.c_int] * 3 + [vp, vp, dbl, dbl, vp, vp]
-        L.gsr_harmonic_features_backward.restype = ctypes.c_int
-        L.gsr_harmonic_features_backward.argtypes = [ctypes.c_int] * 3 + [vp, vp, dbl, dbl, vp, vp, vp, vp]
-        L._gsr_slice4d_bound = True
-    return L
+_vp, _dbl = ctypes.c_void_p, ctypes.c_double
+_lib, _run = _binding.declare("gsr_slice4d.h", {
+    "gsr_slice4d_forward": (ctypes.c_int, [ctypes.c_int] + [_vp] * 7 + [_dbl] * 3 + [_vp] * 5),
+    "gsr_slice4d_backward": (ctypes.c_int, [ctypes.c_int] + [_vp] * 7 + [_dbl] * 3 + [_vp] * 12),
+    "gsr_harmonic_features": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp, _vp, _dbl, _dbl, _vp, _vp]),
+    "gsr_harmonic_features_backward": (ctypes.c_int, [ctypes.c_int] * 3 + [_vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+})
+_ptr, _number = _binding.ptr, _binding.check_number
+_check_device = functools.partial(_binding.check_device, "4D slice kernels")
 
 
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+def _features_shape(n, t, P):
+    if t.dim() != 4 or t.shape[0] != P or P < 1 or t.shape[3] != 3 or not 1 <= t.shape[1] <= MAX_N + 1 or not 1 <= t.shape[2] <= MAX_M:
+        raise RuntimeError(f"features_t must be (P, N + 1, M, 3) with P >= 1, 0 <= N <= {MAX_N} and 1 <= M <= {MAX_M}; got {tuple(t.shape)}")
 
 
 def _check(**named):
     """Every refusal of the tensors a call names (the seven leaves by their names; features_t (P, N+1, M, 3)) but the device's, before
     the kernel library is touched.  -> P"""
-    for n, t in named.items():
-        if not torch.is_tensor(t):
-            raise TypeError(f"{n} must be a tensor")
-    first_name, first = next(iter(named.items()))
-    P = int(first.shape[0]) if first.dim() else 0
-    for n, t in named.items():
-        if n == "features_t":
-            if t.dim() != 4 or t.shape[0] != P or P < 1 or t.shape[3] != 3 or not 1 <= t.shape[1] <= MAX_N + 1 or not 1 <= t.shape[2] <= MAX_M:
-                raise RuntimeError(f"features_t must be (P, N + 1, M, 3) with P >= 1, 0 <= N <= {MAX_N} and 1 <= M <= {MAX_M}; got {tuple(t.shape)}")
-        elif tuple(t.shape) != (P, _COLS[n]) or P < 1:
-            raise RuntimeError(f"{n} must be (P, {_COLS[n]}) with P >= 1 rows as {first_name}; got {tuple(t.shape)}")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be float32; got {t.dtype}")
-    return P
-
-
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("the tensors must be HIP (cuda) tensors on one device; the 4D slice kernels have no CPU path")
-    return dev
-
-
-def _number(name, v):
-    """a Python number that is not a bool -> float"""
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise TypeError(f"{name} must be a Python float, got {type(v).__name__}")
-    return float(v)
+    return _binding.check_rows(list(named.items()), _COLS, _features_shape)
 
 
 def _check_scalars(time, scaling_modifier, cutoff):
@@ -93,9 +59,6 @@ def _check_scalars(time, scaling_modifier, cutoff):
     if not 0.0 <= c < 1.0:
         raise ValueError(f"cutoff must lie in [0, 1); got {c}")
     return time, m, c
-
-
-_ptr = lambda t: None if t is None else t.data_ptr()
 
 
 class _SliceAt(torch.autograd.Function):

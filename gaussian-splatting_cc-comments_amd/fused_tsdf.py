@@ -23,11 +23,12 @@ mesh, or decimating it (marching tetrahedra gives about twice the triangles of m
 (fused_filter3d.pack_cameras raises NotImplementedError for them).  HIP tensors only (no CPU fallback).
 """
 import ctypes
+import functools
 import math
 
 import torch
 
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
 from fused_filter3d import CAMERA_FLOATS, _camera_scalars, pack_cameras
 
 THREADS = 256            # include/gsr_tsdf.h GSR_TSDF_THREADS
@@ -43,47 +44,22 @@ class MeshPlan(ctypes.Structure):   # gsr_tsdf_mesh_plan_t
                 ("scratch", ctypes.c_void_p), ("min_weight", ctypes.c_float), ("magic", ctypes.c_int)]
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_tsdf_bound", False):
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.gsr_tsdf_integrate.restype = ctypes.c_int
-        L.gsr_tsdf_integrate.argtypes = [ctypes.POINTER(Grid), vp, vp, vp, i, vp, vp, i, i, vp, vp, vp, f, f, vp]
-        L.gsr_tsdf_mesh_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_tsdf_mesh_scratch_bytes.argtypes = [ctypes.c_longlong]
-        L.gsr_tsdf_mesh_plan.restype = ctypes.c_int
-        L.gsr_tsdf_mesh_plan.argtypes = [ctypes.POINTER(Grid), vp, vp, f, vp, ctypes.POINTER(MeshPlan), vp]
-        L.gsr_tsdf_mesh_emit.restype = ctypes.c_int
-        L.gsr_tsdf_mesh_emit.argtypes = [ctypes.POINTER(MeshPlan), ctypes.c_longlong, ctypes.c_longlong, vp, vp, vp, vp, vp]
-        L._gsr_tsdf_bound = True
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_i, _f, _ll, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_tsdf.h", {
+    "gsr_tsdf_integrate": (_i, [ctypes.POINTER(Grid), _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp]),
+    "gsr_tsdf_mesh_scratch_bytes": (ctypes.c_size_t, [_ll]),
+    "gsr_tsdf_mesh_plan": (_i, [ctypes.POINTER(Grid), _vp, _vp, _f, _vp, ctypes.POINTER(MeshPlan), _vp]),
+    "gsr_tsdf_mesh_emit": (_i, [ctypes.POINTER(MeshPlan), _ll, _ll, _vp, _vp, _vp, _vp, _vp]),
+}, {"gsr_tsdf_grid": Grid, "gsr_tsdf_mesh_plan_t": MeshPlan})
+_ptr = _binding.ptr
+_check_device = functools.partial(_binding.check_device, "TSDF kernels")
 
 
 def _positive(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise TypeError(f"{name} must be a number, got {v!r}")
-    if not (math.isfinite(v) and v > 0.0):
+    x = _binding.check_number(name, v, "a number", repr)
+    if not (math.isfinite(x) and x > 0.0):
         raise ValueError(f"{name} must be finite and positive; got {v}")
-    return float(v)
-
-
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("the tensors must be HIP (cuda) tensors on one device; the TSDF kernels have no CPU path")
-    return dev
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return x
 
 
 class TSDFVolume:

@@ -17,12 +17,13 @@ result has the same bits every run.  HIP tensors only (no CPU fallback); the con
 any device.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
 
 import fused_knn
-from diff_gaussian_rasterization import _C
+from diff_gaussian_rasterization import _binding
 
 MAX_D = 64      # include/gsr_vq.h GSR_VQ_MAX_D
 MAX_K = 65536   # include/gsr_vq.h GSR_VQ_MAX_K
@@ -30,37 +31,19 @@ FORMAT_VERSION = 1
 LEAVES = ("xyz", "features_dc", "features_rest", "scaling", "rotation", "opacity")   # gsr_model.GaussianParams, in its order
 
 
-def _lib():
-    L = _C.lib()
-    if not getattr(L, "_gsr_vq_bound", False):
-        vp, i = ctypes.c_void_p, ctypes.c_int
-        L.gsr_vq_assign_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_vq_assign_scratch_bytes.argtypes = [i, i, i]
-        L.gsr_vq_assign.restype = i
-        L.gsr_vq_assign.argtypes = [i, i, vp, i, vp, vp, vp, vp, vp]
-        L.gsr_vq_update.restype = i
-        L.gsr_vq_update.argtypes = [i, i, vp, vp, i, vp, vp, vp, vp, vp, vp]
-        L._gsr_vq_bound = True
-    fused_knn._lib()   # the graph-build entry point
-    return L
-
-
-def _run(name, *args):
-    """The one place a kernel entry point is called from."""
-    L = _lib()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"gsr error {rc}: {L.gsr_last_error().decode()}")
+_i, _vp = ctypes.c_int, ctypes.c_void_p
+_lib, _run = _binding.declare("gsr_vq.h", {   # update() groups the rows by code with fused_knn.NeighborGraph, through its table
+    "gsr_vq_assign_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "gsr_vq_assign": (_i, [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gsr_vq_update": (_i, [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+}, needs=("gsr_knn.h",))
+_check_device = functools.partial(_binding.check_device, "quantisation kernels")
+_check_int = _binding.check_int   # (name, v, least)
 
 
 def _check_matrix(name, t, cols=None):
     """A (rows, D) float32 tensor, any strides -> (rows, D)"""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.dim() != 2:
-        raise RuntimeError(f"{name} must have dimensions (rows, D); got {tuple(t.shape)}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32; got {t.dtype}")
+    _binding.check_matrix(name, t, "dimensions (rows, D)")
     if cols is not None and t.shape[1] != cols:
         raise RuntimeError(f"{name} must have {cols} columns as x has; got {tuple(t.shape)}")
     if not 1 <= t.shape[1] <= MAX_D:
@@ -82,20 +65,6 @@ def _check_rows(name, t, N, dtype):
         raise RuntimeError(f"{name} must have dimensions ({N},); got {tuple(t.shape)}")
     if t.dtype != dtype:
         raise RuntimeError(f"{name} must be {str(dtype).replace('torch.', '')}; got {t.dtype}")
-
-
-def _check_device(*tensors):
-    dev = tensors[0].device
-    if dev.type != "cuda" or any(t.device != dev for t in tensors):
-        raise RuntimeError("the tensors must be HIP (cuda) tensors on one device; the quantisation kernels have no CPU path")
-    return dev
-
-
-def _check_int(name, v, least):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise TypeError(f"{name} must be an int, got {v!r}")
-    if v < least:
-        raise ValueError(f"{name} must be at least {least}; got {v}")
 
 
 @torch.no_grad()

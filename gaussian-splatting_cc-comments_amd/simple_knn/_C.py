@@ -9,7 +9,12 @@ import ctypes
 
 import torch
 
-from diff_gaussian_rasterization import _C as _gsr
+from diff_gaussian_rasterization import _binding
+
+_lib, _run = _binding.declare("gsr.h", {
+    "gsr_knn_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "gsr_knn_mean_dist2": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4),
+})
 
 
 def distCUDA2(points):
@@ -17,13 +22,7 @@ def distCUDA2(points):
         raise RuntimeError("points must be a HIP (cuda) tensor; distCUDA2 has no CPU path")
     if points.dim() != 2 or points.size(1) != 3:
         raise RuntimeError("points must have dimensions (num_points, 3)")
-    L = _gsr.lib()
-    if not getattr(L, "_gsr_knn_bound", False):
-        L.gsr_knn_scratch_bytes.restype = ctypes.c_size_t
-        L.gsr_knn_scratch_bytes.argtypes = [ctypes.c_int]
-        L.gsr_knn_mean_dist2.restype = ctypes.c_int
-        L.gsr_knn_mean_dist2.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4
-        L._gsr_knn_bound = True
+    L = _lib()
     dev = points.device
     P = int(points.size(0))
     pts = points.detach().to(torch.float32).contiguous()
@@ -31,7 +30,6 @@ def distCUDA2(points):
         means = torch.empty((P,), dtype=torch.float32, device=dev)  # spatial.cu:19-20 (torch.full 0.0; fully overwritten)
         if P:
             scratch = torch.empty((L.gsr_knn_scratch_bytes(P),), dtype=torch.uint8, device=dev)
-            _gsr._check(L.gsr_knn_mean_dist2(P, pts.data_ptr(), means.data_ptr(), scratch.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream))
+            _run("gsr_knn_mean_dist2", P, pts.data_ptr(), means.data_ptr(), scratch.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             scratch.record_stream(torch.cuda.current_stream(dev))
     return means
